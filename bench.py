@@ -34,6 +34,15 @@ process is one rank.  Started plainly as `python bench.py --gpus N` with N > 1 a
 process only SPAWNS the N ranks -- as child processes, before it has imported the library or touched a
 GPU (never a re-exec of a process that has initialised the GPU) --, relays rank 0's JSON line and exits
 non-zero if any rank failed.
+Plain run vs --full: a plain run sets up, warms up, times the K steps (no HIP events on the stream) and
+prints the headline line.  --full also times the graded kernel pair with HIP events inside the timed steps
+(roofline), times --spread-segments further segments one by one, runs a per-kernel HIP-event pass, the CPU
+baselines (--no-cpu-baseline skips them), the clustered-tracks and full-size cfg5 extras of the default
+workload and, with N > 1, the multi-GPU extras (--no-extras skips them).
+--dump-outputs DIR: right after the K timed steps, what a caller of the LM loop holds -- the refined camera
+and point parameters and the LM result's initial and final cost -- as float64 DIR/<name>.npy (see
+dump_outputs).  The inputs are generated from fixed seeds or read from tests/golden/data, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -359,14 +368,16 @@ def run_steps(h, n, segment):
     return done, tries, res
 
 
-def timed_pass(rk, h, prob, steps, warmup, segment, spread_segments=0, settle=True):
+def timed_pass(rk, h, prob, steps, warmup, segment, settle=True, events=True):
     """Settle, W untimed warm-up iterations, then EXACTLY `steps` LM iterations between barriers, MAX over
-    ranks.  Returns a dict (elapsed seconds, steps done, tries, totals over ranks, the graded pair's time)."""
-    # HIP events on the graded kernel only during the timed region (every timed launch costs two
-    # event records on the stream); the other kernel classes are timed in an extra pass afterwards.
+    ranks.  Returns a dict (elapsed seconds, steps done, tries, totals over ranks, the graded pair's time:
+    NaN without `events`)."""
+    # events (--full): HIP events on the graded kernel only during the timed region (every timed launch
+    # costs two event records on the stream); the other kernel classes are timed in an extra pass afterwards.
     # Enabled before anything runs, so that the event pool is created AND used before the timing
     # starts (growing the runtime's signal pool has been seen to stall the stream for ~0.8 ms).
-    h.profile_enable(int(os.environ.get("PSBA_BENCH_PROF_MASK", 1 << capi.K_SCHUR)))
+    if events:
+        h.profile_enable(int(os.environ.get("PSBA_BENCH_PROF_MASK", 1 << capi.K_SCHUR)))
     # device wake-up, before the W warm-up steps: a fresh process (more so on a fresh box) runs
     # its first milliseconds of sustained load at a lower clock and has been seen to stall ~0.8 ms
     # once or twice early on (PSBA_BENCH_DEBUG=1 prints the segment times).  Untimed segments are
@@ -392,20 +403,48 @@ def timed_pass(rk, h, prob, steps, warmup, segment, spread_segments=0, settle=Tr
     rk.barrier()
     elapsed = rk.max(t1 - t0)
     n_obs_total, n_pts_total = rk.sum_ints([prob["nO"], prob["nP"]])
-    # PSBA_K_SCHUR alone in the mask = ONE span over k_schur_lds + k_schur_reduce: S does not exist
-    # before the reduce ends, so the pair is what the roofline is quoted on
-    ms, n = h.profile_get(capi.K_SCHUR)
-    pair_us = 1e3 * ms / max(n, 1)
-    # spread: further segments, each timed by itself (max over ranks), outside the K timed steps
+    pair_us = float("nan")
+    if events:
+        # PSBA_K_SCHUR alone in the mask = ONE span over k_schur_lds + k_schur_reduce: S does not exist
+        # before the reduce ends, so the pair is what the roofline is quoted on
+        ms, n = h.profile_get(capi.K_SCHUR)
+        pair_us = 1e3 * ms / max(n, 1)
+        h.profile_enable(0)
+    return {"elapsed": elapsed, "steps_done": steps_done, "tries": tries_done, "res": res, "n_obs": n_obs_total,
+            "n_pts": n_pts_total, "pair_us": pair_us}
+
+
+def spread_pass(rk, h, n, segment):
+    """--full: n further segments, each timed by itself (max over ranks), outside the K timed steps; ms per LM
+    iteration of each."""
     seg_ms = []
-    h.profile_enable(0)
-    for _ in range(max(spread_segments, 0)):
+    for _ in range(max(n, 0)):
         rk.barrier()
         ts = time.perf_counter()
         d_, _, _ = run_steps(h, segment, segment)
         seg_ms.append(1e3 * rk.max(time.perf_counter() - ts) / max(d_, 1))
-    return {"elapsed": elapsed, "steps_done": steps_done, "tries": tries_done, "res": res, "n_obs": n_obs_total,
-            "n_pts": n_pts_total, "pair_us": pair_us, "seg_ms": seg_ms}
+    return seg_ms
+
+
+DUMP_BYTES = 64 * 10**6
+
+
+def dump_outputs(h, res, out_dir, rank, world):
+    """--dump-outputs: the handle's current parameters right after the last timed step and that step's LM
+    result, as a caller of psba_levmar receives them: cameras.npy (n_cams x camera block), points.npy
+    (n_pts x 3; points_rank<r>.npy per rank when N > 1) and lm_cost.npy ([initial cost, final cost] of the
+    last segment), all float64.  Points beyond the 64 MB budget are written as a fixed sample: the rows
+    numpy.random.default_rng(0) draws without replacement, in ascending order."""
+    os.makedirs(out_dir, exist_ok=True)
+    cams, pts = h.get_params()
+    budget = (DUMP_BYTES - cams.nbytes - (64 << 10)) // world  # 64 KiB: the costs and the .npy headers
+    if pts.nbytes > budget:
+        rows = np.random.default_rng(0).choice(len(pts), budget // pts[0].nbytes, replace=False)
+        pts = pts[np.sort(rows)]
+    if rank == 0:  # the cameras are the same on every rank
+        np.save(os.path.join(out_dir, "cameras.npy"), cams)
+        np.save(os.path.join(out_dir, "lm_cost.npy"), np.array([res.init_err, res.final_err]))
+    np.save(os.path.join(out_dir, "points.npy" if world == 1 else f"points_rank{rank}.npy"), pts)
 
 
 def per_kernel_pass(h, steps, segment):
@@ -447,16 +486,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="venice-shaped")
     ap.add_argument("--segment", type=int, default=10, help="LM iterations per restart segment")
-    ap.add_argument("--cpu-iters", type=int, default=30, help="LM iterations of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-iters", type=int, default=30, help="--full: LM iterations of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="N > 1: strong = ONE problem split over the ranks (north star, BASELINE configs[3]); "
                          "weak = one shard of the workload's size per rank")
-    ap.add_argument("--no-extras", action="store_true", help="N > 1: skip the weak-scaling and sharded-cfg5 extra keys")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N > 1: skip the weak-scaling and sharded-cfg5 extra keys")
     ap.add_argument("--cfg5-points", type=int, default=200000, help="points of the cfg5 workload (2000000 = full)")
     ap.add_argument("--spread-segments", type=int, default=10,
-                    help="extra segments timed one by one after the K steps, for the median / spread fields")
+                    help="--full: extra segments timed one by one after the K steps, for the median / spread fields")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, spread, per-kernel, CPU-baseline and extra-configuration measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the parameters and costs after the last timed step as DIR/<name>.npy "
+                         "(bench_out/ is kept out of git)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: this process becomes the launcher.  Nothing above has touched a GPU runtime.
@@ -469,24 +515,21 @@ def main():
 
     load_library()
     rk = Ranks()
-    rank, local_rank = rk.rank, rk.local_rank
+    rank = rk.rank
 
     file_workload = args.workload in ("54cams", "trafalgar21")
     strong = args.scaling == "strong" or file_workload
     prob, data_kind = load_workload(args.workload, rank, world, strong, args.cfg5_points)
     h = rk.handle(prob)
     chol_sharded = world > 1 and bool(h.chol_dist_shape()[2]) and not os.environ.get("PSBA_CHOL_REPLICATED")
-    r = timed_pass(rk, h, prob, args.steps, args.warmup, args.segment, args.spread_segments)
+    r = timed_pass(rk, h, prob, args.steps, args.warmup, args.segment, events=args.full)
     elapsed, steps_done, tries_done, res = r["elapsed"], r["steps_done"], r["tries"], r["res"]
-    n_obs_total, n_pts_total, pair_us, seg_ms = r["n_obs"], r["n_pts"], r["pair_us"], r["seg_ms"]
-    kern = per_kernel_pass(h, args.steps, args.segment)
+    n_obs_total, n_pts_total, pair_us = r["n_obs"], r["n_pts"], r["pair_us"]
+    if args.dump_outputs:
+        dump_outputs(h, res, args.dump_outputs, rank, world)
 
     out = None
     if rank == 0:
-        sch_bytes = h.algorithmic_bytes(capi.K_SCHUR)
-        sch_us = pair_us
-        achieved = sch_bytes / (sch_us * 1e-6) / 1e9 if sch_us == sch_us and sch_us > 0 else float("nan")
-        seg_sorted = sorted(seg_ms)
         config = {"workload": args.workload + ("" if world == 1 else
                                                (f" split over {world} ranks" if strong else f" x{world} shards")),
                   "n_cams": int(prob["nC"]), "n_pts": n_pts_total, "n_obs": n_obs_total,
@@ -505,23 +548,46 @@ def main():
             "config": config,
             "steps_completed": steps_done, "damping_tries": tries_done, "lm_flag": res.flag, "segment": args.segment,
             "init_cost": res.init_err, "final_cost": res.final_err,
-            # the K timed steps are one sample; these are further segments of the same length timed one
-            # by one right after it (ms per LM iteration)
-            "ms_per_step_segments": ({"n": len(seg_ms), "median": seg_sorted[len(seg_sorted) // 2],
-                                      "min": seg_sorted[0], "max": seg_sorted[-1]} if seg_ms else None),
             "schur_path": {0: "lds-partitions", 1: "owner (products sorted by camera pair)", 2: "global-atomics",
                            3: "ring (experiment)", 4: "block-sparse (owner)"}.get(h.schur_path(), str(h.schur_path())),
-            "kernels_us": {k: round(v["avg_us"], 3) for k, v in kern.items()},
-            "roofline": {"kernel": "schur assemble (W/Y/S/ea): k_schur_lds + k_schur_reduce, one HIP-event span over both",
-                         "bound": "hbm", "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "algorithmic_bytes_per_launch": sch_bytes, "avg_launch_us": sch_us,
-                         "traffic": None},
         }
         if world > 1 or os.environ.get("PSBA_BENCH_REHEARSE"):
             out["multi_gpu"] = {"hardware_note": "first N > 1 measurements come from the driver's node: the builder has one GPU",
                                 "dense_factorization": "wide update sharded by 64-column block" if chol_sharded else "replicated",
                                 "bytes_per_try_per_rank": collective_bytes(int(prob["nC"]), world, chol_sharded)}
+    if args.full:
+        full_measurements(args, rk, h, prob, res, pair_us, out)
+    h.close()
+    if args.full:
+        full_extras(args, rk, strong, out)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if rk.dist is not None:
+        rk.dist.destroy_process_group()
+
+
+def full_measurements(args, rk, h, prob, res, pair_us, out):
+    """--full, on the headline's handle after its timed steps: spread segments, per-kernel HIP-event pass,
+    roofline of the graded pair (its HIP events ran inside the timed steps), CPU baselines.  Every rank takes
+    part in the spread segments; the keys go into rank 0's line (`out`)."""
+    seg_ms = spread_pass(rk, h, args.spread_segments, args.segment)
+    kern = per_kernel_pass(h, args.steps, args.segment)
+    world = rk.world
+    if rk.rank == 0:
+        sch_bytes = h.algorithmic_bytes(capi.K_SCHUR)
+        sch_us = pair_us
+        achieved = sch_bytes / (sch_us * 1e-6) / 1e9 if sch_us == sch_us and sch_us > 0 else float("nan")
+        seg_sorted = sorted(seg_ms)
+        # the K timed steps are one sample; these are further segments of the same length timed one
+        # by one right after it (ms per LM iteration)
+        out["ms_per_step_segments"] = ({"n": len(seg_ms), "median": seg_sorted[len(seg_sorted) // 2],
+                                        "min": seg_sorted[0], "max": seg_sorted[-1]} if seg_ms else None)
+        out["kernels_us"] = {k: round(v["avg_us"], 3) for k, v in kern.items()}
+        out["roofline"] = {"kernel": "schur assemble (W/Y/S/ea): k_schur_lds + k_schur_reduce, one HIP-event span over both",
+                           "bound": "hbm", "achieved": achieved,
+                           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                           "algorithmic_bytes_per_launch": sch_bytes, "avg_launch_us": sch_us,
+                           "traffic": None}
         # SURVEY 8(d) also asks for the kernel's FP64 rate: nP*50 (V^-1) + nO*(108 Y + 36 e_a) +
         # P_sym*216 flops per launch, P_sym = sum_i k_i (k_i + 1) / 2 products
         ii = np.asarray(prob["iidx"])
@@ -589,7 +655,12 @@ def main():
                               f"oracle/psba_oracle.c built with OpenMP ({threads} threads)",
                     "final_cost": pres.final_err,
                 }
-    h.close()
+
+
+def full_extras(args, rk, strong, out):
+    """--full, after the headline's handle is closed: the other measured configurations as extra keys of
+    rank 0's line (`out`)."""
+    rank, world, local_rank = rk.rank, rk.world, rk.local_rank
     # N > 1, default workload: the other two multi-GPU configurations as extra keys (every rank takes part).
     # (PSBA_BENCH_REHEARSE=1: the same code path on ONE GPU -- a one-rank RCCL communicator, the extras included --
     # which is all of the multi-GPU flow a single-GPU box can rehearse)
@@ -619,9 +690,6 @@ def main():
                 out["cfg5_full_size"] = cfg5_extra(local_rank)
             except Exception as e:  # the headline line must not depend on the extra
                 out["cfg5_full_size"] = {"error": repr(e)}
-        print(json.dumps(out), flush=True)
-    if rk.dist is not None:
-        rk.dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -6,11 +6,9 @@ cd $REPO
 for round in 1 2; do
 for v in "$@"; do
   if [ "$v" = "-" ]; then e=""; else e="$v"; fi
-  env $e python bench.py --no-cpu-baseline --steps 300 --warmup 20 > gpurun_out/envb.json 2> gpurun_out/envb.err
-  python - <<PY
-import json
-b=json.loads(open("gpurun_out/envb.json").read().strip().splitlines()[-1])
-print("$v", round(b["ms_per_step"],5), b["kernels_us"], round(b["roofline"]["avg_launch_us"],2))
-PY
+  env $e python bench.py --full --no-cpu-baseline --steps 300 --warmup 20 | python -c "
+import json,sys
+b=json.loads(sys.stdin.read().strip().splitlines()[-1])
+print('$v', round(b['ms_per_step'],5), b['kernels_us'], round(b['roofline']['avg_launch_us'],2))"
 done
 done

@@ -3,7 +3,7 @@
 # bench.py --workload cfg5 --cfg5-points 2000000.
 export PSBA_SCHUR_SLAB_MAX_GB=${SLAB_MAX_GB:-16}
 for v in "$@"; do
-  PSBA_SCHUR_SPLIT=$v python bench.py --workload cfg5 --cfg5-points 2000000 --steps 3 --warmup 0 --segment 3 --spread-segments 0 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+  PSBA_SCHUR_SPLIT=$v python bench.py --full --workload cfg5 --cfg5-points 2000000 --steps 3 --warmup 0 --segment 3 --spread-segments 0 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 b=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=b['kernels_us']

@@ -8,5 +8,5 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$REPO/bench.py --workload cfg5 --cfg5-points $PTS --steps 4 --warmup 1 --segment 2 --spread-segments 0 --no-cpu-baseline"
+ARGS="$REPO/bench.py --full --workload cfg5 --cfg5-points $PTS --steps 4 --warmup 1 --segment 2 --spread-segments 0 --no-cpu-baseline"
 rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT -f csv -d $OUT/pmc_clk -- python3 $ARGS > $OUT/bench_clk.json 2> $OUT/clk.log
