@@ -103,6 +103,31 @@ int psba_get_dims(psba_handle h, int *nCams, int *n3Dpts, int *n2Dprojs);
 #define PSBA_CAMERA_FREE_K 1
 int psba_set_camera_model(psba_handle h, int model);
 int psba_camera_block(psba_handle h, int *cnp); /* 6 or 11 */
+
+/* ---- lens distortion and per-observation image covariances --------------------------
+ * Model (the same in psba_amd/csrc/camera_model.h and DESIGN.md): P = R'(q) M + t, (x, y) = (Px, Py) / Pz,
+ * r2 = x^2 + y^2, kc = (k1, k2, k3, k4, k5) in the Camera Calibration Toolbox order (the column order of the
+ * 17-column sba cams files: K5, kc(1:5), quaternion, translation):
+ *   radial = 1 + k1 r2 + k2 r2^2 + k5 r2^3
+ *   xd = radial x + 2 k3 x y + k4 (r2 + 2 x^2),   yd = radial y + k3 (r2 + 2 y^2) + 2 k4 x y
+ *   u = fu xd + s yd + u0,   v = fu ar yd + v0,   e = m - (u, v)
+ * Covariances: observation a has an SPD 2x2 Sigma_a and the cost is sum e_a^T Sigma_a^-1 e_a.  The library
+ * factors Sigma_a^-1 = L_a^T L_a (L_a upper triangular) once, here, and the kernels whiten right after the
+ * projection (e <- L e, A <- L A, B <- L B).  Every verb then works on the whitened quantities: psba_residual,
+ * the try scalars and the loop logs report the weighted cost, and psba_compute_exQT / psba_compute_jacobiQT
+ * (and the U, V, W, g, S, e_a of the mirror) return the whitened e, A and B.
+ * The fixed-intrinsics camera block only: PSBA_E_STATE before psba_upload_problem and under PSBA_CAMERA_FREE_K.
+ * Call after psba_upload_problem (a new upload resets both to none), while no try is in flight; setting either
+ * discards a linearization queued ahead.  The reference reads both and uses neither (PSBA/readparams.cpp:272-283,
+ * 380-412; PSBA/main.cpp:112): PARITY UNPINNED -- checked against an independent numpy twin that is itself pinned to
+ * the oracle where the models coincide (kc = 0, Sigma = I). */
+/* kc: nCams * 5 (camera order of the upload); NULL = no distortion */
+int psba_set_distortion(psba_handle h, const double *kc);
+/* cov: n2Dprojs * 4 (row-major 2x2 per observation, in the uploaded observation order; under a rank layout, this
+ * rank's observations); NULL = none.  PSBA_E_INVALID for a Sigma that is not SPD or not symmetric to 1e-12
+ * relative (the error text names the observation) */
+int psba_set_obs_covariance(psba_handle h, const double *cov);
+int psba_lens_model(psba_handle h, int *has_distortion, int *has_covariance);
 /* which S-assembly route the uploaded problem takes: 0 = LDS-resident partitions of the block
  * triangle with the static schedule (fewer than 2048 cameras, up to 8 GB of partial-sum slabs on
  * this rank), 1 = the owner route for larger problems (one thread per block segment,
@@ -317,6 +342,16 @@ typedef struct {
 int psba_read_problem(const char *cams_file, const char *pts_file, const double *fixedK,
                       psba_problem *out);
 void psba_free_problem(psba_problem *p);
+/* The same reader, plus what psba_read_problem skips (see psba_set_distortion for the model): kc[nCams * 5] when the
+ * cams file has 17 columns (K5, kc(1:5), q, t), else NULL; cov[n2Dprojs * 4] (row-major 2x2 per observation, in
+ * the returned observation order; the 3-value form xx xy yy expanded) when the pts file carries covariances, else
+ * NULL.  base is exactly what psba_read_problem returns.  Released with psba_free_problem_ex. */
+typedef struct {
+  psba_problem base;
+  double *kc, *cov;
+} psba_problem_ex;
+int psba_read_problem_ex(const char *cams_file, const char *pts_file, const double *fixedK, psba_problem_ex *out);
+void psba_free_problem_ex(psba_problem_ex *p);
 /* The writer the reference declares and keeps commented out (printSBAMotionData /
  * printSBAStructureData / printSBAData, PSBA/readparams.h:13-25; output filter vec2quat,
  * PSBA/misc.cpp:60-85): cams file with one line per camera -- K5 when with_K != 0, then the full
@@ -330,6 +365,10 @@ int psba_write_problem(const char *cams_file, const char *pts_file, int nCams, i
  * down +z, image y negated, K = (f,0,0,1,0); the radial terms k1, k2 are dropped (the reference
  * has no distortion) and their largest magnitude is returned in *max_abs_k (may be NULL). */
 int psba_convert_bal(const char *bal_file, const char *cams_out, const char *pts_out, double *max_abs_k);
+/* The same conversion with the radial terms kept: 17-column cams "f 0 0 1 0 k1 k2 0 0 0 q t".  BAL's normalised
+ * point p = -P / P.z becomes (x', y') = (p.x, -p.y) here, with the same |p|^2, so BAL's f (1 + k1 |p|^2 + k2 |p|^4) p
+ * is exactly the distortion model of psba_set_distortion with kc = (k1, k2, 0, 0, 0). */
+int psba_convert_bal_kd(const char *bal_file, const char *cams_out, const char *pts_out);
 
 /* ---- measurement ----------------------------------------------------------------------
  * HIP-event timing of the kernels launched by the fused verbs, on the handle's stream. */

@@ -64,6 +64,10 @@ class CProblem(C.Structure):
                 ("jidx", _ip)]
 
 
+class CProblemEx(C.Structure):
+    _fields_ = [("base", CProblem), ("kc", _dp), ("cov", _dp)]
+
+
 # every symbol include/psba_hip.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ("psba_create", C.c_int, [C.c_int, C.POINTER(_h)]),
@@ -142,6 +146,12 @@ SIGNATURES = [
     ("psba_set_sparse_pattern", C.c_int, [_h, C.POINTER(C.c_ubyte), C.c_longlong]),
     ("psba_set_camera_model", C.c_int, [_h, C.c_int]),
     ("psba_camera_block", C.c_int, [_h, _ip]),
+    ("psba_set_distortion", C.c_int, [_h, _dp]),
+    ("psba_set_obs_covariance", C.c_int, [_h, _dp]),
+    ("psba_lens_model", C.c_int, [_h, _ip, _ip]),
+    ("psba_read_problem_ex", C.c_int, [C.c_char_p, C.c_char_p, _dp, C.POINTER(CProblemEx)]),
+    ("psba_free_problem_ex", None, [C.POINTER(CProblemEx)]),
+    ("psba_convert_bal_kd", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
     ("psba_chol_dist_exchange_plan", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int]),
     ("psba_chol_dist_shape", C.c_int, [_h, _ip, _ip, _ip]),
     ("psba_chol_dist_begin", C.c_int, [_h]),
@@ -206,6 +216,15 @@ def sparse_pattern(prob):
     return flags
 
 
+def _problem_from(cp):
+    nC, nP, nO = cp.nCams, cp.n3Dpts, cp.n2Dprojs
+    arr = lambda p, n, shape: np.ctypeslib.as_array(p, shape=(n,)).copy().reshape(shape)
+    return Problem(K=arr(cp.Kparas, 5 * nC, (nC, 5)), initrot=arr(cp.initrot, 4 * nC, (nC, 4)),
+                  cams=arr(cp.camsEx, 6 * nC, (nC, 6)), pts=arr(cp.pts3D, 3 * nP, (nP, 3)),
+                  impts=arr(cp.impts, 2 * nO, (nO, 2)), iidx=arr(cp.iidx, nO, (nO,)).astype(np.int32),
+                  jidx=arr(cp.jidx, nO, (nO,)).astype(np.int32), nC=nC, nP=nP, nO=nO)
+
+
 def read_problem(cams_file, pts_file, fixedK=None):
     """psba_read_problem -> Problem (host only, works without a GPU)."""
     cp = CProblem()
@@ -213,13 +232,24 @@ def read_problem(cams_file, pts_file, fixedK=None):
     rc = lib.psba_read_problem(os.fsencode(cams_file), os.fsencode(pts_file), _d(k), C.byref(cp))
     if rc != 0:
         raise PsbaError(rc, f"psba_read_problem({cams_file}, {pts_file}) failed")
-    nC, nP, nO = cp.nCams, cp.n3Dpts, cp.n2Dprojs
-    arr = lambda p, n, shape: np.ctypeslib.as_array(p, shape=(n,)).copy().reshape(shape)
-    out = Problem(K=arr(cp.Kparas, 5 * nC, (nC, 5)), initrot=arr(cp.initrot, 4 * nC, (nC, 4)),
-                  cams=arr(cp.camsEx, 6 * nC, (nC, 6)), pts=arr(cp.pts3D, 3 * nP, (nP, 3)),
-                  impts=arr(cp.impts, 2 * nO, (nO, 2)), iidx=arr(cp.iidx, nO, (nO,)).astype(np.int32),
-                  jidx=arr(cp.jidx, nO, (nO,)).astype(np.int32), nC=nC, nP=nP, nO=nO)
+    out = _problem_from(cp)
     lib.psba_free_problem(C.byref(cp))
+    return out
+
+
+def read_problem_ex(cams_file, pts_file, fixedK=None):
+    """psba_read_problem_ex -> Problem with two more keys: kc [nC, 5] (17-column cams file) and cov [nO, 2, 2]
+    (pts file with covariances, observation order), each None when the files do not carry it."""
+    cp = CProblemEx()
+    k = None if fixedK is None else _c(fixedK)
+    rc = lib.psba_read_problem_ex(os.fsencode(cams_file), os.fsencode(pts_file), _d(k), C.byref(cp))
+    if rc != 0:
+        raise PsbaError(rc, f"psba_read_problem_ex({cams_file}, {pts_file}) failed")
+    out = _problem_from(cp.base)
+    nC, nO = out["nC"], out["nO"]
+    out["kc"] = np.ctypeslib.as_array(cp.kc, shape=(5 * nC,)).copy().reshape(nC, 5) if cp.kc else None
+    out["cov"] = np.ctypeslib.as_array(cp.cov, shape=(4 * nO,)).copy().reshape(nO, 2, 2) if cp.cov else None
+    lib.psba_free_problem_ex(C.byref(cp))
     return out
 
 
@@ -242,6 +272,13 @@ def convert_bal(bal_file, cams_out, pts_out):
     if rc != 0:
         raise PsbaError(rc, f"psba_convert_bal({bal_file}) failed")
     return k.value
+
+
+def convert_bal_kd(bal_file, cams_out, pts_out):
+    """psba_convert_bal_kd: 17-column cams with kc = (k1, k2, 0, 0, 0) (read back with read_problem_ex)."""
+    rc = lib.psba_convert_bal_kd(bal_file.encode(), cams_out.encode(), pts_out.encode())
+    if rc != 0:
+        raise PsbaError(rc, f"psba_convert_bal_kd({bal_file}) failed")
 
 
 def partition_points(n_pts, iidx, nranks):
@@ -348,15 +385,21 @@ def ring_plan(n_cams, n_pts, iidx, jidx):
 
 def shard_problem(prob, nranks, rank):
     """The sub-problem rank `rank` owns: a contiguous point range and its observations;
-    cameras are replicated."""
+    cameras are replicated.  A problem with kc / cov keys (read_problem_ex) keeps kc and the cov rows of
+    the observations it keeps."""
     bounds = partition_points(prob["nP"], prob["iidx"], nranks)
     p0, p1 = int(bounds[rank]), int(bounds[rank + 1])
     iidx = np.asarray(prob["iidx"])
     sel = (iidx >= p0) & (iidx < p1)
-    return Problem(K=prob["K"], initrot=prob["initrot"], cams=prob["cams"], pts=prob["pts"][p0:p1],
-                   impts=np.asarray(prob["impts"])[sel], iidx=(iidx[sel] - p0).astype(np.int32),
-                   jidx=np.asarray(prob["jidx"])[sel].astype(np.int32), nC=prob["nC"], nP=p1 - p0,
-                   nO=int(sel.sum()))
+    out = Problem(K=prob["K"], initrot=prob["initrot"], cams=prob["cams"], pts=prob["pts"][p0:p1],
+                  impts=np.asarray(prob["impts"])[sel], iidx=(iidx[sel] - p0).astype(np.int32),
+                  jidx=np.asarray(prob["jidx"])[sel].astype(np.int32), nC=prob["nC"], nP=p1 - p0,
+                  nO=int(sel.sum()))
+    if "kc" in prob:
+        out["kc"] = prob["kc"]
+    if "cov" in prob:
+        out["cov"] = None if prob["cov"] is None else np.asarray(prob["cov"])[sel]
+    return out
 
 
 class Psba:
@@ -389,6 +432,27 @@ class Psba:
     def set_camera_model(self, free_k):
         """PSBA_CAMERA_FREE_K: camera blocks of 11 (fu, u0, v0, ar, s | rotation | translation); before upload."""
         self._ck(lib.psba_set_camera_model(self._h, 1 if free_k else 0))
+
+    def set_distortion(self, kc):
+        """psba_set_distortion: kc [nC, 5] = (k1, k2, k3, k4, k5) per camera, None = no distortion."""
+        k = None if kc is None else _c(kc).reshape(-1)
+        if k is not None and k.size != 5 * self.nC:
+            raise PsbaError(-1, f"set_distortion: {k.size} values for {self.nC} cameras (5 each)")
+        self._ck(lib.psba_set_distortion(self._h, _d(k)))
+
+    def set_obs_covariance(self, cov):
+        """psba_set_obs_covariance: cov [nO, 2, 2] (or [nO, 4] row-major) in the uploaded observation order,
+        None = none."""
+        c = None if cov is None else _c(cov).reshape(-1)
+        if c is not None and c.size != 4 * self.nO:
+            raise PsbaError(-1, f"set_obs_covariance: {c.size} values for {self.nO} observations (4 each)")
+        self._ck(lib.psba_set_obs_covariance(self._h, _d(c)))
+
+    def lens_model(self):
+        """psba_lens_model -> (has_distortion, has_covariance)"""
+        d, c = C.c_int(), C.c_int()
+        self._ck(lib.psba_lens_model(self._h, C.byref(d), C.byref(c)))
+        return bool(d.value), bool(c.value)
 
     def camera_block(self):
         n = C.c_int()

@@ -156,6 +156,170 @@ PSBA_HD void linearize_obs_freek(const double *p, const double *q0, const double
   }
 }
 
+// ---- lens distortion and per-observation covariances (the reference reads both and never uses them) ----
+// With (x, y) = (Px, Py) / Pz, r2 = x^2 + y^2 and kc = (k1, k2, k3, k4, k5) (Camera Calibration Toolbox order, the
+// column order of the 17-column sba cams files):
+//   radial = 1 + k1 r2 + k2 r2^2 + k5 r2^3
+//   xd = radial x + 2 k3 x y + k4 (r2 + 2 x^2),   yd = radial y + k3 (r2 + 2 y^2) + 2 k4 x y
+//   u = fu xd + s yd + u0,   v = fu ar yd + v0,   e = m - (u, v)
+// Covariances: observation a has an SPD 2x2 Sigma_a; the host factors Sigma_a^-1 = L_a^T L_a with L_a upper
+// triangular, stored (l00, l01, l11, 0).  The kernels whiten right after the projection (e <- L e, A <- L A,
+// B <- L B), so the cost is sum e^T Sigma^-1 e and everything downstream is the same normal equations.
+// The lens model of a kernel instantiation: bit 0 distortion, bit 1 covariances.
+enum { LENS_PLAIN = 0, LENS_DIST = 1, LENS_COV = 2, LENS_BOTH = 3 };
+constexpr int LENS_WSTRIDE = 4;  // doubles per observation of the whitening factors (l00, l01, l11, pad)
+
+// (xd, yd) and, when J is given, d(xd, yd) / d(x, y) row-major
+PSBA_HD void distort(const double *kc, double x, double y, double &xd, double &yd, double *J = nullptr) {
+  const double r2 = x * x + y * y;
+  const double radial = 1.0 + r2 * (kc[0] + r2 * (kc[1] + r2 * kc[4]));
+  const double xy = x * y;
+  xd = radial * x + 2.0 * kc[2] * xy + kc[3] * (r2 + 2.0 * x * x);
+  yd = radial * y + kc[2] * (r2 + 2.0 * y * y) + 2.0 * kc[3] * xy;
+  if (J) {
+    const double dr = kc[0] + r2 * (2.0 * kc[1] + 3.0 * kc[4] * r2);  // d radial / d r2
+    J[0] = radial + 2.0 * x * x * dr + 2.0 * kc[2] * y + 6.0 * kc[3] * x;
+    J[1] = 2.0 * xy * dr + 2.0 * kc[2] * x + 2.0 * kc[3] * y;
+    J[2] = 2.0 * xy * dr + 2.0 * kc[2] * x + 2.0 * kc[3] * y;
+    J[3] = radial + 2.0 * y * y * dr + 6.0 * kc[2] * y + 2.0 * kc[3] * x;
+  }
+}
+
+PSBA_HD void residual_obs_dist(const double *K, const double *q0, const double *cam, const double *M, const double *kc,
+                               double mx, double my, double &e0, double &e1) {
+  double sl, R[9];
+  const Quat q = compose_quat(q0, cam[0], cam[1], cam[2], sl);
+  quat_matrix(q, R);
+  const double Px = R[0] * M[0] + R[1] * M[1] + R[2] * M[2] + cam[3];
+  const double Py = R[3] * M[0] + R[4] * M[1] + R[5] * M[2] + cam[4];
+  const double Pz = R[6] * M[0] + R[7] * M[1] + R[8] * M[2] + cam[5];
+  const double inv = 1.0 / Pz;
+  double xd, yd;
+  distort(kc, Px * inv, Py * inv, xd, yd);
+  e0 = mx - (K[0] * xd + K[4] * yd + K[1]);
+  e1 = my - (K[0] * K[3] * yd + K[2]);
+}
+
+// residual + Jacobian blocks with distortion.  D = d(u, v) / dP = Kmat d(xd, yd) / d(x, y) d(x, y) / dP is a
+// full 2 x 3 matrix (d10 != 0), so A[9] and the R[0..2] terms of B[3..5] are not the zeros of linearize_obs.
+PSBA_HD void linearize_obs_dist(const double *K, const double *q0, const double *cam, const double *M, const double *kc,
+                                double mx, double my, double *e, double *A, double *B) {
+  double sl, R[9];
+  const Quat q = compose_quat(q0, cam[0], cam[1], cam[2], sl);
+  quat_matrix(q, R);
+  const double Px = R[0] * M[0] + R[1] * M[1] + R[2] * M[2] + cam[3];
+  const double Py = R[3] * M[0] + R[4] * M[1] + R[5] * M[2] + cam[4];
+  const double Pz = R[6] * M[0] + R[7] * M[1] + R[8] * M[2] + cam[5];
+  const double inv = 1.0 / Pz;
+  const double x = Px * inv, y = Py * inv;
+  double xd, yd, J[4];
+  distort(kc, x, y, xd, yd, J);
+  e[0] = mx - (K[0] * xd + K[4] * yd + K[1]);
+  e[1] = my - (K[0] * K[3] * yd + K[2]);
+  // G = Kmat J, Kmat = [fu s; 0 fu ar]; d(x, y) / dP = [1 0 -x; 0 1 -y] / Pz
+  const double fa = K[0] * K[3];
+  const double g00 = K[0] * J[0] + K[4] * J[2], g01 = K[0] * J[1] + K[4] * J[3];
+  const double g10 = fa * J[2], g11 = fa * J[3];
+  double D[6];
+  D[0] = g00 * inv;
+  D[1] = g01 * inv;
+  D[2] = -(g00 * x + g01 * y) * inv;
+  D[3] = g10 * inv;
+  D[4] = g11 * inv;
+  D[5] = -(g10 * x + g11 * y) * inv;
+#pragma unroll
+  for (int r = 0; r < 2; r++) {
+    A[6 * r + 3] = D[3 * r];
+    A[6 * r + 4] = D[3 * r + 1];
+    A[6 * r + 5] = D[3 * r + 2];
+#pragma unroll
+    for (int c = 0; c < 3; c++) B[3 * r + c] = D[3 * r] * R[c] + D[3 * r + 1] * R[3 + c] + D[3 * r + 2] * R[6 + c];
+  }
+  // rotation columns: dP / dv_k as in linearize_obs
+  const double s0 = q0[0], a0 = q0[1], a1 = q0[2], a2 = q0[3];
+  const double isl = 1.0 / sl;
+  const double udM = q.u0 * M[0] + q.u1 * M[1] + q.u2 * M[2];
+  const double c0 = q.u1 * M[2] - q.u2 * M[1];
+  const double c1 = q.u2 * M[0] - q.u0 * M[2];
+  const double c2 = q.u0 * M[1] - q.u1 * M[0];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double dsl = -cam[k] * isl;
+    const double ak = (k == 0) ? a0 : (k == 1 ? a1 : a2);
+    const double ds = dsl * s0 - ak;
+    const double x0 = (k == 0) ? 0.0 : (k == 1 ? a2 : -a1);
+    const double x1 = (k == 0) ? -a2 : (k == 1 ? 0.0 : a0);
+    const double x2 = (k == 0) ? a1 : (k == 1 ? -a0 : 0.0);
+    const double du0 = ((k == 0) ? s0 : 0.0) + dsl * a0 + x0;
+    const double du1 = ((k == 1) ? s0 : 0.0) + dsl * a1 + x1;
+    const double du2 = ((k == 2) ? s0 : 0.0) + dsl * a2 + x2;
+    const double dudM = du0 * M[0] + du1 * M[1] + du2 * M[2];
+    const double udu = q.u0 * du0 + q.u1 * du1 + q.u2 * du2;
+    const double g = q.s * ds - udu;
+    const double m0 = du1 * M[2] - du2 * M[1];
+    const double m1 = du2 * M[0] - du0 * M[2];
+    const double m2 = du0 * M[1] - du1 * M[0];
+    const double dP0 = 2.0 * (du0 * udM + q.u0 * dudM + g * M[0] + ds * c0 + q.s * m0);
+    const double dP1 = 2.0 * (du1 * udM + q.u1 * dudM + g * M[1] + ds * c1 + q.s * m1);
+    const double dP2 = 2.0 * (du2 * udM + q.u2 * dudM + g * M[2] + ds * c2 + q.s * m2);
+    A[k] = D[0] * dP0 + D[1] * dP1 + D[2] * dP2;
+    A[6 + k] = D[3] * dP0 + D[4] * dP1 + D[5] * dP2;
+  }
+}
+
+// e <- L e, A <- L A, B <- L B with L = [l00 l01; 0 l11] (w = (l00, l01, l11))
+PSBA_HD void whiten2(const double *w, double &e0, double &e1) {
+  const double t = w[0] * e0 + w[1] * e1;
+  e1 = w[2] * e1;
+  e0 = t;
+}
+PSBA_HD void whiten_obs(const double *w, double *e, double *A, double *B) {
+  whiten2(w, e[0], e[1]);
+#pragma unroll
+  for (int k = 0; k < 6; k++) whiten2(w, A[k], A[6 + k]);
+#pragma unroll
+  for (int k = 0; k < 3; k++) whiten2(w, B[k], B[3 + k]);
+}
+
+// loads of camera j's kc and observation a's whitening factors (nothing under a model without them)
+template <int LM>
+PSBA_HD void lens_load_kc(const double *src, size_t j, double *kc) {
+  if constexpr ((LM & LENS_DIST) != 0) {
+#pragma unroll
+    for (int k = 0; k < 5; k++) kc[k] = src[5 * j + k];
+  }
+}
+template <int LM>
+PSBA_HD void lens_load_w(const double *src, size_t a, double *w) {
+  if constexpr ((LM & LENS_COV) != 0) {
+    const double2 w01 = reinterpret_cast<const double2 *>(src)[2 * a];
+    w[0] = w01.x;
+    w[1] = w01.y;
+    w[2] = src[LENS_WSTRIDE * a + 2];
+  }
+}
+
+// the per-observation entry points of the fixed-intrinsics kernels: LM = LENS_PLAIN is exactly linearize_obs /
+// residual_obs (kc and w are not read)
+template <int LM>
+PSBA_HD void lens_linearize(const double *cc, const double *cam, const double *M, const double *kc, const double *w,
+                            double mx, double my, double *e, double *A, double *B) {
+  if constexpr ((LM & LENS_DIST) != 0)
+    linearize_obs_dist(cc, cc + 5, cam, M, kc, mx, my, e, A, B);
+  else
+    linearize_obs(cc, cc + 5, cam, M, mx, my, e, A, B);
+  if constexpr ((LM & LENS_COV) != 0) whiten_obs(w, e, A, B);
+}
+template <int LM>
+PSBA_HD void lens_residual(const double *cc, const double *cam, const double *M, const double *kc, const double *w,
+                           double mx, double my, double &e0, double &e1) {
+  if constexpr ((LM & LENS_DIST) != 0)
+    residual_obs_dist(cc, cc + 5, cam, M, kc, mx, my, e0, e1);
+  else
+    residual_obs(cc, cc + 5, cam, M, mx, my, e0, e1);
+  if constexpr ((LM & LENS_COV) != 0) whiten2(w, e0, e1);
+}
+
 // symmetric 3x3 inverse by the closed form the reference uses (T = -det,
 // CL_files/compute_Vinv.cl:29,76-86).  v = (v00,v01,v02,v11,v12,v22) -> same packing.
 // Returns true when |T| < 1e-16 (the reference's singular flag).

@@ -31,13 +31,14 @@ struct BackArgs {
   int nC, nA, nTiles;
   int cam_terms;       // 1 on the rank that owns the camera terms of the scalar sums
   int mode;            // development ablation (PSBA_BACK_MODE): 1 no residual pass, 2 no W^T dpa pass
+  const double *kc, *wl;  // lens model (camera_model.h): read only by the LENS_DIST / LENS_COV instantiations
 };
 
 // RECOMP: W_ij^T dpa_j = coeff B_ij^T (A_ij dpa_j) from the Jacobian blocks recomputed at the current
 // parameters (~300 flop per observation) instead of from the stored W (144 bytes per observation:
 // 50 of the kernel's 66 MB at venice size); the camera constants and parameters loaded for it are
 // the ones the residual pass needs anyway.  (PSBA_BACK_READ_W=1: the W-reading form.)
-template <bool DUMP, bool RECOMP>
+template <bool DUMP, bool RECOMP, int LM>
 __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p) {
   __shared__ double sT[TILE_OBS][3];   // W_a^T dpa_j per observation
   __shared__ double sNP[TILE_OBS][3];  // proposed point per point of the tile
@@ -86,10 +87,12 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p) {
       pb1 = p.ptr[p0 + tid + 1] - o0;
     }
     __syncthreads();
-    double cc[9], cam[6], da[6];
+    double cc[9], cam[6], da[6], kc[5], wl[3];
     if (RECOMP && a < o1) {
 #pragma unroll
       for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * j + k];
+      lens_load_kc<LM>(p.kc, j, kc);
+      lens_load_w<LM>(p.wl, a, wl);
 #pragma unroll
       for (int k = 0; k < 6; k++) {
         cam[k] = p.cams[6 * j + k];
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p) {
         double M[3], e[2], A[12], B[6];
 #pragma unroll
         for (int k = 0; k < 3; k++) M[k] = p.pts[3 * (size_t)i + k];
-        linearize_obs(cc, cc + 5, cam, M, 0.0, 0.0, e, A, B);
+        lens_linearize<LM>(cc, cam, M, kc, wl, 0.0, 0.0, e, A, B);
         double s0 = 0.0, s1 = 0.0;
 #pragma unroll
         for (int k = 0; k < 6; k++) {
@@ -182,12 +185,14 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p) {
         for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * j + k];
 #pragma unroll
         for (int k = 0; k < 6; k++) cam[k] = p.cams[6 * j + k] + p.dp[6 * j + k];
+        lens_load_kc<LM>(p.kc, j, kc);
+        lens_load_w<LM>(p.wl, a, wl);
       } else {
 #pragma unroll
         for (int k = 0; k < 6; k++) cam[k] += da[k];
       }
       const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
-      residual_obs(cc, cc + 5, cam, sNP[i - p0], m.x, m.y, e0, e1);
+      lens_residual<LM>(cc, cam, sNP[i - p0], kc, wl, m.x, m.y, e0, e1);
       s_cost += e0 * e0 + e1 * e1;
     }
     dsc = dn;
@@ -218,7 +223,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p) {
 // A point seen by more than TILE_OBS cameras (compute_eb.cl:28-37 loops over all cameras): one
 // workgroup walks its observations twice, TILE_OBS at a time -- sum of W_ij^T dpa_j (from the
 // stored W), then dpb_i and the proposed point by one thread, then the residuals at the proposal.
-template <bool DUMP>
+template <bool DUMP, int LM>
 __global__ __launch_bounds__(TILE_OBS) void k_backsub_long(BackArgs p, const int *long_pts) {
   __shared__ double sRed[TILE_OBS / 64][4];
   __shared__ double sNP[3];
@@ -278,13 +283,15 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub_long(BackArgs p, const int
   __syncthreads();
   for (int a = o0 + tid; a < o1; a += TILE_OBS) {
     const int j = p.jidx[a];
-    double cc[9], cam[6], e0, e1;
+    double cc[9], cam[6], e0, e1, kc[5], wl[3];
 #pragma unroll
     for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * (size_t)j + k];
 #pragma unroll
     for (int k = 0; k < 6; k++) cam[k] = p.cams[6 * (size_t)j + k] + p.dp[6 * (size_t)j + k];
+    lens_load_kc<LM>(p.kc, j, kc);
+    lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
-    residual_obs(cc, cc + 5, cam, sNP, m.x, m.y, e0, e1);
+    lens_residual<LM>(cc, cam, sNP, kc, wl, m.x, m.y, e0, e1);
     s_cost += e0 * e0 + e1 * e1;
   }
   __syncthreads();
@@ -318,6 +325,25 @@ int launch_publish_scal(psba_ctx *h, hipStream_t s) {
   return PSBA_OK;
 }
 
+// K3 for lens model LM (psba_ctx::lens)
+template <int LM>
+static void enqueue_backsub(psba_ctx *h, const BackArgs &a, int grid, bool dump, bool read_w) {
+  if (dump && read_w)
+    hipLaunchKernelGGL((k_backsub<true, false, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+  else if (dump)
+    hipLaunchKernelGGL((k_backsub<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+  else if (read_w)
+    hipLaunchKernelGGL((k_backsub<false, false, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+  else
+    hipLaunchKernelGGL((k_backsub<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+  if (h->nLong) {  // points seen by more cameras than a tile holds
+    if (dump)
+      hipLaunchKernelGGL((k_backsub_long<true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts);
+    else
+      hipLaunchKernelGGL((k_backsub_long<false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts);
+  }
+}
+
 int launch_backsub(psba_ctx *h, double mu, bool dump) {
   if (h->cnp != 6) return dump ? fail(h, PSBA_E_STATE, "the sba_func.h mirror is six-parameter only") : launch_backsub_fk(h, mu);
   const Dims &d = h->d;
@@ -345,6 +371,8 @@ int launch_backsub(psba_ctx *h, double mu, bool dump) {
   a.nA = d.nA;
   a.nTiles = d.nTiles;
   a.cam_terms = h->rank == 0 ? 1 : 0;
+  a.kc = h->lens_kc;
+  a.wl = h->lens_w;
   {
     const char *m = getenv("PSBA_BACK_MODE");
     a.mode = m ? atoi(m) : 0;
@@ -359,19 +387,11 @@ int launch_backsub(psba_ctx *h, double mu, bool dump) {
   {
     ProfScope ps(h, PSBA_K_BACKSUB);
     const bool read_w = getenv("PSBA_BACK_READ_W") != nullptr;
-    if (dump && read_w)
-      hipLaunchKernelGGL((k_backsub<true, false>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
-    else if (dump)
-      hipLaunchKernelGGL((k_backsub<true, true>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
-    else if (read_w)
-      hipLaunchKernelGGL((k_backsub<false, false>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
-    else
-      hipLaunchKernelGGL((k_backsub<false, true>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
-    if (h->nLong) {  // points seen by more cameras than a tile holds
-      if (dump)
-        hipLaunchKernelGGL(k_backsub_long<true>, dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts);
-      else
-        hipLaunchKernelGGL(k_backsub_long<false>, dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts);
+    switch (h->lens) {
+      case LENS_DIST: enqueue_backsub<LENS_DIST>(h, a, grid, dump, read_w); break;
+      case LENS_COV: enqueue_backsub<LENS_COV>(h, a, grid, dump, read_w); break;
+      case LENS_BOTH: enqueue_backsub<LENS_BOTH>(h, a, grid, dump, read_w); break;
+      default: enqueue_backsub<LENS_PLAIN>(h, a, grid, dump, read_w); break;
     }
   }
   PSBA_HIP(h, hipGetLastError());

@@ -33,11 +33,14 @@ struct LinArgs {
   const double *pub_src;
   double *pub_dst;  // nullptr: nothing to publish
   double pub_stamp;
+  // lens model (camera_model.h): [nC][5] distortion, [nO][LENS_WSTRIDE] whitening factors; read only by the
+  // LENS_DIST / LENS_COV instantiations
+  const double *kc, *wl;
 };
 
 // GACC: many cameras -- the 27 sums per camera do not fit the LDS.  They are then formed by a
 // camera-major pass of their own (k_cam_sums) and this kernel leaves them out.
-template <bool DUMP, bool GACC>
+template <bool DUMP, bool GACC, int LM>
 __global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p) {
   __shared__ double sBE[TILE_OBS][9];  // B(6) | e(2) per observation of the tile (+1: odd row stride)
   __shared__ double sW[(TILE_OBS / 2) * 19];  // W blocks of half a tile (staged in two halves: LDS for three workgroups per CU)
@@ -79,15 +82,17 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p) {
     }
     double Wv[18];
     if (a < o1) {
-      double cc[9], cam[6], M[3], e[2], A[12], B[6];
+      double cc[9], cam[6], M[3], e[2], A[12], B[6], kc[5], wl[3];
 #pragma unroll
       for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * j + k];
 #pragma unroll
       for (int k = 0; k < 6; k++) cam[k] = p.cams[6 * j + k];
 #pragma unroll
       for (int k = 0; k < 3; k++) M[k] = p.pts[3 * i + k];
+      lens_load_kc<LM>(p.kc, j, kc);
+      lens_load_w<LM>(p.wl, a, wl);
       const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
-      linearize_obs(cc, cc + 5, cam, M, m.x, m.y, e, A, B);
+      lens_linearize<LM>(cc, cam, M, kc, wl, m.x, m.y, e, A, B);
       if (DUMP) {
         p.dbg_ex[2 * a] = e[0];
         p.dbg_ex[2 * a + 1] = e[1];
@@ -200,7 +205,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p) {
 //  * the LDS that B / e needed holds the second half of W: one staging, one barrier, one flush per tile;
 //  * the NEXT tile's indices and the eighteen parameter doubles they lead to are fetched as soon as this tile's
 //    Jacobian is done, so their latency runs under the camera atomics, the scan and the W flush.
-template <bool DUMP, bool GACC>
+template <bool DUMP, bool GACC, int LM>
 __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p) {
   __shared__ double sW[TILE_OBS * 19];          // W blocks of the tile (row stride 19 doubles: odd, conflict-free stores)
   __shared__ double sCarV[TILE_OBS / 64][9];    // a wave's last lane: its scan values (the tail of its last segment)
@@ -220,7 +225,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p) {
   int tile = blockIdx.x;
   int4 dsc = tile < p.nTiles ? p.tile_desc[tile] : make_int4(0, 0, 0, 0);
   int i = 0, j = 0;
-  double cc[9], cam[6], M[3];
+  double cc[9], cam[6], M[3], kc[5], wl[3];
   double2 m = make_double2(0.0, 0.0);
   // prologue: the first tile's operands
   if (dsc.z + tid < dsc.w) {
@@ -232,6 +237,8 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p) {
     for (int k = 0; k < 6; k++) cam[k] = p.cams[6 * j + k];
 #pragma unroll
     for (int k = 0; k < 3; k++) M[k] = p.pts[3 * (size_t)i + k];
+    lens_load_kc<LM>(p.kc, j, kc);
+    lens_load_w<LM>(p.wl, dsc.z + tid, wl);
     m = reinterpret_cast<const double2 *>(p.impts)[dsc.z + tid];
   }
   for (; tile < p.nTiles; tile += gridDim.x) {
@@ -247,7 +254,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p) {
     const int jc = j;
     if (act) {
       double e[2], A[12], B[6];
-      linearize_obs(cc, cc + 5, cam, M, m.x, m.y, e, A, B);
+      lens_linearize<LM>(cc, cam, M, kc, wl, m.x, m.y, e, A, B);
       if (DUMP) {
         p.dbg_ex[2 * (size_t)a] = e[0];
         p.dbg_ex[2 * (size_t)a + 1] = e[1];
@@ -293,6 +300,8 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p) {
       for (int k = 0; k < 6; k++) cam[k] = p.cams[6 * j + k];
 #pragma unroll
       for (int k = 0; k < 3; k++) M[k] = p.pts[3 * (size_t)i + k];
+      lens_load_kc<LM>(p.kc, j, kc);
+      lens_load_w<LM>(p.wl, dn.z + tid, wl);
       m = reinterpret_cast<const double2 *>(p.impts)[dn.z + tid];
     }
     // segmented inclusive scan over the lanes of a point
@@ -355,7 +364,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p) {
 // time.  W as in k_linearize; V_i and g_b,i summed over the workgroup; the camera sums go with global
 // fp64 atomics into one extra slab of the per-workgroup camera sums (zeroed before the launch) that
 // k_cam_reduce adds like any other -- with GACC the camera-major pass covers these observations anyway.
-template <bool DUMP, bool GACC>
+template <bool DUMP, bool GACC, int LM>
 __global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const int *long_pts, double *cam_slab) {
   __shared__ double sRed[TILE_OBS / 64][9];
   const int tid = threadIdx.x, i = long_pts[blockIdx.x];
@@ -367,13 +376,15 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const in
   for (int k = 0; k < 9; k++) acc[k] = 0.0;
   for (int a = o0 + tid; a < o1; a += TILE_OBS) {
     const int j = p.jidx[a];
-    double cc[9], cam[6], e[2], A[12], B[6];
+    double cc[9], cam[6], e[2], A[12], B[6], kc[5], wl[3];
 #pragma unroll
     for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * (size_t)j + k];
 #pragma unroll
     for (int k = 0; k < 6; k++) cam[k] = p.cams[6 * (size_t)j + k];
+    lens_load_kc<LM>(p.kc, j, kc);
+    lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
-    linearize_obs(cc, cc + 5, cam, M, m.x, m.y, e, A, B);
+    lens_linearize<LM>(cc, cam, M, kc, wl, m.x, m.y, e, A, B);
     if (DUMP) {
       p.dbg_ex[2 * (size_t)a] = e[0];
       p.dbg_ex[2 * (size_t)a + 1] = e[1];
@@ -425,6 +436,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const in
 // ascending), the Jacobian block recomputed from the parameters, 27 sums in registers, one set of
 // fp64 atomic adds per segment.  (Through per-observation atomics from the point-major kernel the
 // same sums took 25 ms at 20 M observations; the reference scans all points per output scalar.)
+template <int LM>
 __global__ __launch_bounds__(256) void k_cam_sums(LinArgs p, const int *cam_obs, const int4 *units, int nUnits) {
   // one wave per unit (a segment of at most 256 observations of one camera): the lanes stride
   // through the segment, the 27 sums are folded across the wave, lane 0 adds them to the camera's
@@ -435,21 +447,23 @@ __global__ __launch_bounds__(256) void k_cam_sums(LinArgs p, const int *cam_obs,
   if (u >= nUnits) return;
   const int4 un = units[u];
   const int j = un.x;
-  double cc[9], cam[6], acc[CAM_ACC];
+  double cc[9], cam[6], acc[CAM_ACC], kc[5];
 #pragma unroll
   for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * (size_t)j + k];
 #pragma unroll
   for (int k = 0; k < 6; k++) cam[k] = p.cams[6 * (size_t)j + k];
+  lens_load_kc<LM>(p.kc, j, kc);
 #pragma unroll
   for (int k = 0; k < CAM_ACC; k++) acc[k] = 0.0;
   for (int t = un.y + lane; t < un.z; t += 64) {
     const int a = cam_obs[t];
     const int i = p.iidx[a];
-    double M[3], e[2], A[12], B[6];
+    double M[3], e[2], A[12], B[6], wl[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) M[k] = p.pts[3 * (size_t)i + k];
+    lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
-    linearize_obs(cc, cc + 5, cam, M, m.x, m.y, e, A, B);
+    lens_linearize<LM>(cc, cam, M, kc, wl, m.x, m.y, e, A, B);
     int k = 0;
 #pragma unroll
     for (int r = 0; r < 6; r++)
@@ -526,23 +540,27 @@ __global__ __launch_bounds__(1024) void k_cam_reduce(const double *campart, int 
 }
 
 // ---- residual: kern_compute_exQT + the host compute_L2_sq (PSBA/misc.cpp:151-157) -------
+template <int LM>
 __global__ __launch_bounds__(256) void k_residual(const double *camconst, const double *cams,
                                                   const double *pts, const double *impts,
                                                   const int *iidx, const int *jidx, int nO,
-                                                  double *ex_out, double *cost) {
+                                                  double *ex_out, double *cost, const double *kcs,
+                                                  const double *wls) {
   __shared__ double sRed[4];
   double sum = 0.0;
   for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < nO; a += gridDim.x * blockDim.x) {
     const int i = iidx[a], j = jidx[a];
-    double cc[9], cam[6], M[3], e0, e1;
+    double cc[9], cam[6], M[3], e0, e1, kc[5], wl[3];
 #pragma unroll
     for (int k = 0; k < 9; k++) cc[k] = camconst[9 * j + k];
 #pragma unroll
     for (int k = 0; k < 6; k++) cam[k] = cams[6 * j + k];
 #pragma unroll
     for (int k = 0; k < 3; k++) M[k] = pts[3 * i + k];
+    lens_load_kc<LM>(kcs, j, kc);
+    lens_load_w<LM>(wls, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(impts)[a];
-    residual_obs(cc, cc + 5, cam, M, m.x, m.y, e0, e1);
+    lens_residual<LM>(cc, cam, M, kc, wl, m.x, m.y, e0, e1);
     if (ex_out) {
       ex_out[2 * a] = e0;
       ex_out[2 * a + 1] = e1;
@@ -580,6 +598,63 @@ __global__ __launch_bounds__(256) void k_max_diag(const double *U, const double 
   }
 }
 
+template <int LM>
+static int set_lin_attrs(psba_ctx *h) {
+  const auto attr = hipFuncAttributeMaxDynamicSharedMemorySize;
+  PSBA_HIP(h, hipFuncSetAttribute((const void *)k_linearize<true, false, LM>, attr, 100 * 1024));
+  PSBA_HIP(h, hipFuncSetAttribute((const void *)k_linearize<false, false, LM>, attr, 100 * 1024));
+  PSBA_HIP(h, hipFuncSetAttribute((const void *)k_linearize2<true, false, LM>, attr, 100 * 1024));
+  PSBA_HIP(h, hipFuncSetAttribute((const void *)k_linearize2<false, false, LM>, attr, 100 * 1024));
+  return PSBA_OK;
+}
+
+// the kernels of one linearization for lens model LM (psba_ctx::lens)
+template <int LM>
+static void enqueue_linearize(psba_ctx *h, const LinArgs &a, bool dump, bool v1, size_t lds, double *Uo, double *gao) {
+  const Dims &d = h->d;
+  if (h->cam_global) {
+    const int grid = d.nTiles < 2048 ? d.nTiles : 2048;
+    if (v1 && dump)
+      hipLaunchKernelGGL((k_linearize<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+    else if (v1)
+      hipLaunchKernelGGL((k_linearize<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+    else if (dump)
+      hipLaunchKernelGGL((k_linearize2<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+    else
+      hipLaunchKernelGGL((k_linearize2<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+    if (h->nLong) {
+      if (dump)
+        hipLaunchKernelGGL((k_linearize_long<true, true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr);
+      else
+        hipLaunchKernelGGL((k_linearize_long<false, true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr);
+    }
+    hipLaunchKernelGGL(k_cam_sums<LM>, dim3((h->nCamUnits + 3) / 4), dim3(256), 0, h->stream, a, h->cam_obs,
+                       h->cam_units, h->nCamUnits);
+    hipLaunchKernelGGL(k_cam_finalize, dim3((42 * d.nC + 255) / 256), dim3(256), 0, h->stream, h->camacc, d.nC,
+                       h->coeff, h->coeff_g, Uo, gao);
+  } else {
+    if (v1 && dump)
+      hipLaunchKernelGGL((k_linearize<true, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
+    else if (v1)
+      hipLaunchKernelGGL((k_linearize<false, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
+    else if (dump)
+      hipLaunchKernelGGL((k_linearize2<true, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
+    else
+      hipLaunchKernelGGL((k_linearize2<false, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
+    int nslab = h->nPart;
+    if (h->nLong) {  // their camera sums: one more slab (zeroed by the caller)
+      double *slab = h->campart + (size_t)h->nPart * d.nC * CAM_ACC;
+      if (dump)
+        hipLaunchKernelGGL((k_linearize_long<true, false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab);
+      else
+        hipLaunchKernelGGL((k_linearize_long<false, false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab);
+      nslab++;
+    }
+    hipLaunchKernelGGL(k_cam_reduce, dim3(d.nC), dim3(1024), 0, h->stream, h->campart, nslab, d.nC, h->coeff,
+                       h->coeff_g, Uo, gao);
+  }
+}
+
 int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
   if (h->cnp != 6) return dump ? fail(h, PSBA_E_STATE, "the sba_func.h mirror is six-parameter only") : launch_linearize_fk(h, ahead, publish);
   const Dims &d = h->d;
@@ -609,6 +684,8 @@ int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
   a.pub_src = h->scal;
   a.pub_dst = publish ? h->h_scal_dev : nullptr;
   a.pub_stamp = h->pub_seq;
+  a.kc = h->lens_kc;
+  a.wl = h->lens_w;
   {
     const char *m = getenv("PSBA_LIN_MODE");
     a.mode = m ? atoi(m) : 0;
@@ -617,58 +694,26 @@ int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
   const size_t lds = h->cam_global ? 0 : sizeof(double) * CAM_ACC * (size_t)d.nC;
   // static LDS of the kernel is ~54 KiB: beyond 64 KiB in all, the dynamic part needs the attribute
   if (!h->lin_attr_set && lds > 8 * 1024) {
-    const auto attr = hipFuncAttributeMaxDynamicSharedMemorySize;
-    PSBA_HIP(h, hipFuncSetAttribute((const void *)k_linearize<true, false>, attr, 100 * 1024));
-    PSBA_HIP(h, hipFuncSetAttribute((const void *)k_linearize<false, false>, attr, 100 * 1024));
-    PSBA_HIP(h, hipFuncSetAttribute((const void *)k_linearize2<true, false>, attr, 100 * 1024));
-    PSBA_HIP(h, hipFuncSetAttribute((const void *)k_linearize2<false, false>, attr, 100 * 1024));
+    int rc = set_lin_attrs<LENS_PLAIN>(h);
+    if (rc == PSBA_OK) rc = set_lin_attrs<LENS_DIST>(h);
+    if (rc == PSBA_OK) rc = set_lin_attrs<LENS_COV>(h);
+    if (rc == PSBA_OK) rc = set_lin_attrs<LENS_BOTH>(h);
+    if (rc != PSBA_OK) return rc;
     h->lin_attr_set = true;
   }
   double *Uo = ahead ? h->U_alt : h->U, *gao = ahead ? h->ga_alt : h->ga;
   {
     ProfScope ps(h, PSBA_K_LINEARIZE);
-    if (h->cam_global) {
+    if (h->cam_global)
       PSBA_HIP(h, hipMemsetAsync(h->camacc, 0, sizeof(double) * CAM_ACC * (size_t)d.nC, h->stream));
-      const int grid = d.nTiles < 2048 ? d.nTiles : 2048;
-      if (v1 && dump)
-        hipLaunchKernelGGL((k_linearize<true, true>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
-      else if (v1)
-        hipLaunchKernelGGL((k_linearize<false, true>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
-      else if (dump)
-        hipLaunchKernelGGL((k_linearize2<true, true>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
-      else
-        hipLaunchKernelGGL((k_linearize2<false, true>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
-      if (h->nLong) {
-        if (dump)
-          hipLaunchKernelGGL((k_linearize_long<true, true>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr);
-        else
-          hipLaunchKernelGGL((k_linearize_long<false, true>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr);
-      }
-      hipLaunchKernelGGL(k_cam_sums, dim3((h->nCamUnits + 3) / 4), dim3(256), 0, h->stream, a, h->cam_obs,
-                         h->cam_units, h->nCamUnits);
-      hipLaunchKernelGGL(k_cam_finalize, dim3((42 * d.nC + 255) / 256), dim3(256), 0, h->stream, h->camacc, d.nC,
-                         h->coeff, h->coeff_g, Uo, gao);
-    } else {
-      if (v1 && dump)
-        hipLaunchKernelGGL((k_linearize<true, false>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
-      else if (v1)
-        hipLaunchKernelGGL((k_linearize<false, false>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
-      else if (dump)
-        hipLaunchKernelGGL((k_linearize2<true, false>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
-      else
-        hipLaunchKernelGGL((k_linearize2<false, false>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
-      int nslab = h->nPart;
-      if (h->nLong) {  // their camera sums: one more slab
-        double *slab = h->campart + (size_t)h->nPart * d.nC * CAM_ACC;
-        PSBA_HIP(h, hipMemsetAsync(slab, 0, sizeof(double) * CAM_ACC * (size_t)d.nC, h->stream));
-        if (dump)
-          hipLaunchKernelGGL((k_linearize_long<true, false>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab);
-        else
-          hipLaunchKernelGGL((k_linearize_long<false, false>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab);
-        nslab++;
-      }
-      hipLaunchKernelGGL(k_cam_reduce, dim3(d.nC), dim3(1024), 0, h->stream, h->campart, nslab, d.nC, h->coeff,
-                         h->coeff_g, Uo, gao);
+    else if (h->nLong)
+      PSBA_HIP(h, hipMemsetAsync(h->campart + (size_t)h->nPart * d.nC * CAM_ACC, 0, sizeof(double) * CAM_ACC * (size_t)d.nC,
+                                 h->stream));
+    switch (h->lens) {
+      case LENS_DIST: enqueue_linearize<LENS_DIST>(h, a, dump, v1, lds, Uo, gao); break;
+      case LENS_COV: enqueue_linearize<LENS_COV>(h, a, dump, v1, lds, Uo, gao); break;
+      case LENS_BOTH: enqueue_linearize<LENS_BOTH>(h, a, dump, v1, lds, Uo, gao); break;
+      default: enqueue_linearize<LENS_PLAIN>(h, a, dump, v1, lds, Uo, gao); break;
     }
   }
   PSBA_HIP(h, hipGetLastError());
@@ -684,9 +729,16 @@ int launch_residual(psba_ctx *h, int which, double *ex_out_dev) {
   if (grid > 256) grid = 256;  // one atomic request per workgroup; same-address atomics serialise
   {
     ProfScope ps(h, PSBA_K_RESIDUAL);
-    hipLaunchKernelGGL(k_residual, dim3(grid), dim3(256), 0, h->stream, h->camconst, h->cams[set],
-                       h->pts[set], h->impts, h->iidx, h->jidx, d.nO, ex_out_dev,
-                       h->scal + SC_COST);
+#define PSBA_RES_LAUNCH(LM)                                                                                          \
+  hipLaunchKernelGGL(k_residual<LM>, dim3(grid), dim3(256), 0, h->stream, h->camconst, h->cams[set], h->pts[set],    \
+                     h->impts, h->iidx, h->jidx, d.nO, ex_out_dev, h->scal + SC_COST, h->lens_kc, h->lens_w)
+    switch (h->lens) {
+      case LENS_DIST: PSBA_RES_LAUNCH(LENS_DIST); break;
+      case LENS_COV: PSBA_RES_LAUNCH(LENS_COV); break;
+      case LENS_BOTH: PSBA_RES_LAUNCH(LENS_BOTH); break;
+      default: PSBA_RES_LAUNCH(LENS_PLAIN); break;
+    }
+#undef PSBA_RES_LAUNCH
   }
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;

@@ -31,22 +31,27 @@ struct JmulArgs {
   double *out1;           // [2 nO] J x1 or nullptr
   double *dots;           // [3] accumulators (zeroed before the launch): x1.x1, x1.x2, x2.x2 in J-norm
   int nO, nA;
+  const double *kc, *wl;  // lens model (camera_model.h): read only by the LENS_DIST / LENS_COV instantiations
 };
 
+// J x with the whitened Jacobian blocks (covariances: L A, L B) of the handle's lens model
+template <int LM>
 __global__ __launch_bounds__(256) void k_jmul(JmulArgs p) {
   __shared__ double sRed[3][4];
   double d11 = 0.0, d12 = 0.0, d22 = 0.0;
   for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < p.nO; a += gridDim.x * blockDim.x) {
     const int i = p.iidx[a], j = p.jidx[a];
-    double cc[9], cam[6], M[3], e[2], A[12], B[6];
+    double cc[9], cam[6], M[3], e[2], A[12], B[6], kc[5], wl[3];
 #pragma unroll
     for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * j + k];
 #pragma unroll
     for (int k = 0; k < 6; k++) cam[k] = p.cams[6 * j + k];
 #pragma unroll
     for (int k = 0; k < 3; k++) M[k] = p.pts[3 * (size_t)i + k];
+    lens_load_kc<LM>(p.kc, j, kc);
+    lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
-    linearize_obs(cc, cc + 5, cam, M, m.x, m.y, e, A, B);
+    lens_linearize<LM>(cc, cam, M, kc, wl, m.x, m.y, e, A, B);
     double r1[2], r2[2];
 #pragma unroll
     for (int k = 0; k < 2; k++) {  // compute_Jmultiply.cl:32-46: row k of A_ij, then of B_ij
@@ -542,10 +547,17 @@ int launch_jmul(psba_ctx *h, const double *x1_dev, const double *x2_dev, double 
   a.dots = dots_dev;
   a.nO = h->d.nO;
   a.nA = h->d.nA;
+  a.kc = h->lens_kc;
+  a.wl = h->lens_w;
   PSBA_HIP(h, hipMemsetAsync(dots_dev, 0, 3 * sizeof(double), h->stream));
   int grid = (h->d.nO + 255) / 256;
   if (grid > 1024) grid = 1024;
-  hipLaunchKernelGGL(k_jmul, dim3(grid), dim3(256), 0, h->stream, a);
+  switch (h->lens) {
+    case LENS_DIST: hipLaunchKernelGGL(k_jmul<LENS_DIST>, dim3(grid), dim3(256), 0, h->stream, a); break;
+    case LENS_COV: hipLaunchKernelGGL(k_jmul<LENS_COV>, dim3(grid), dim3(256), 0, h->stream, a); break;
+    case LENS_BOTH: hipLaunchKernelGGL(k_jmul<LENS_BOTH>, dim3(grid), dim3(256), 0, h->stream, a); break;
+    default: hipLaunchKernelGGL(k_jmul<LENS_PLAIN>, dim3(grid), dim3(256), 0, h->stream, a); break;
+  }
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }

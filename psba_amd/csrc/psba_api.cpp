@@ -12,6 +12,7 @@
 #include <new>
 #include <vector>
 
+#include "camera_model.h"
 #include "psba_internal.h"
 
 using namespace psba;
@@ -117,6 +118,9 @@ static void free_problem_buffers(psba_ctx *h) {
   dev_free(h->pts[0]);
   dev_free(h->pts[1]);
   dev_free(h->impts);
+  dev_free(h->lens_kc);
+  dev_free(h->lens_w);
+  h->lens = 0;
   dev_free(h->iidx);
   dev_free(h->jidx);
   dev_free(h->ptr);
@@ -278,6 +282,85 @@ int psba_set_camera_model(psba_handle h, int model) {
   if (model != PSBA_CAMERA_FIXED_K && model != PSBA_CAMERA_FREE_K) return fail(h, PSBA_E_INVALID, "unknown camera model %d", model);
   NEED(h, !h->uploaded, "psba_set_camera_model before psba_upload_problem (every buffer depends on the camera block)");
   h->cnp = model == PSBA_CAMERA_FREE_K ? 11 : 6;
+  return PSBA_OK;
+}
+
+// ---- lens model (camera_model.h) -------------------------------------------------------------
+static int lens_settable(psba_ctx *h, const char *what) {
+  if (!h->uploaded) return fail(h, PSBA_E_STATE, "%s: no problem uploaded", what);
+  if (h->cnp != 6) return fail(h, PSBA_E_STATE, "%s: the fixed-intrinsics camera block only (not PSBA_CAMERA_FREE_K)", what);
+  if (h->backsub_pending) return fail(h, PSBA_E_STATE, "%s: a damping try is in flight (psba_backsub_wait first)", what);
+  return PSBA_OK;
+}
+
+// the model changed: a linearization queued ahead (or kept for the next psba_linearize) was made with the old one
+static void lens_changed(psba_ctx *h) {
+  h->ahead = false;
+  h->lin_is_ahead = false;
+  h->linearized = h->assembled = h->solved = false;
+}
+
+int psba_set_distortion(psba_handle h, const double *kc) {
+  CHECK_H(h);
+  TRY(lens_settable(h, __func__));
+  if (!kc) {
+    dev_free(h->lens_kc);
+    h->lens &= ~LENS_DIST;
+  } else {
+    for (int t = 0; t < 5 * h->d.nC; t++)
+      if (!std::isfinite(kc[t])) return fail(h, PSBA_E_INVALID, "%s: kc[%d] of camera %d is not finite", __func__, t % 5, t / 5);
+    if (!h->lens_kc) TRY(dev_alloc(h, &h->lens_kc, (size_t)5 * h->d.nC));
+    PSBA_HIP(h, hipMemcpyAsync(h->lens_kc, kc, sizeof(double) * 5 * (size_t)h->d.nC, hipMemcpyHostToDevice, h->stream));
+    PSBA_HIP(h, hipStreamSynchronize(h->stream));
+    h->lens |= LENS_DIST;
+  }
+  lens_changed(h);
+  return PSBA_OK;
+}
+
+int psba_set_obs_covariance(psba_handle h, const double *cov) {
+  CHECK_H(h);
+  TRY(lens_settable(h, __func__));
+  if (!cov) {
+    dev_free(h->lens_w);
+    h->lens &= ~LENS_COV;
+    lens_changed(h);
+    return PSBA_OK;
+  }
+  // Sigma = [p q; q r] -> Sigma^-1 = [r -q; -q p] / det = L^T L, L = [l00 l01; 0 l11]
+  std::vector<double> w((size_t)LENS_WSTRIDE * h->d.nO, 0.0);
+  for (int a = 0; a < h->d.nO; a++) {
+    const double *c = cov + 4 * (size_t)a;
+    const double p = c[0], r = c[3];
+    const double big = std::fmax(std::fmax(std::fabs(c[0]), std::fabs(c[1])), std::fmax(std::fabs(c[2]), std::fabs(c[3])));
+    if (!(std::isfinite(p) && std::isfinite(c[1]) && std::isfinite(c[2]) && std::isfinite(r)))
+      return fail(h, PSBA_E_INVALID, "%s: covariance of observation %d is not finite", __func__, a);
+    if (std::fabs(c[1] - c[2]) > 1e-12 * big)
+      return fail(h, PSBA_E_INVALID, "%s: covariance of observation %d is not symmetric (%.17g vs %.17g)", __func__, a, c[1], c[2]);
+    const double q = 0.5 * (c[1] + c[2]);
+    const double det = p * r - q * q;
+    if (!(p > 0.0) || !(det > 0.0))
+      return fail(h, PSBA_E_INVALID, "%s: covariance of observation %d is not positive definite", __func__, a);
+    const double i00 = r / det, i01 = -q / det, i11 = p / det;
+    const double l00 = std::sqrt(i00), l01 = i01 / l00;
+    const double t = i11 - l01 * l01;
+    if (!(t > 0.0)) return fail(h, PSBA_E_INVALID, "%s: covariance of observation %d is not positive definite", __func__, a);
+    w[(size_t)LENS_WSTRIDE * a] = l00;
+    w[(size_t)LENS_WSTRIDE * a + 1] = l01;
+    w[(size_t)LENS_WSTRIDE * a + 2] = std::sqrt(t);
+  }
+  if (!h->lens_w) TRY(dev_alloc(h, &h->lens_w, w.size()));
+  PSBA_HIP(h, hipMemcpyAsync(h->lens_w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, h->stream));
+  PSBA_HIP(h, hipStreamSynchronize(h->stream));
+  h->lens |= LENS_COV;
+  lens_changed(h);
+  return PSBA_OK;
+}
+
+int psba_lens_model(psba_handle h, int *has_distortion, int *has_covariance) {
+  CHECK_H(h);
+  if (has_distortion) *has_distortion = (h->lens & LENS_DIST) ? 1 : 0;
+  if (has_covariance) *has_covariance = (h->lens & LENS_COV) ? 1 : 0;
   return PSBA_OK;
 }
 

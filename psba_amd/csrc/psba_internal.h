@@ -161,6 +161,11 @@ struct psba_ctx {
   double *pts[2] = {nullptr, nullptr};   // [nP][3] cur / proposed   (pts3D_buffer, newPts3D_buffer)
   double *params0 = nullptr;    // [nT] the parameters as uploaded (psba_reset_params)
   double *impts = nullptr;      // [nO][2]                           (impts_buffer)
+  // lens model (psba_set_distortion / psba_set_obs_covariance; camera_model.h): the launch sites pick the kernel
+  // instantiation from `lens` (bit 0 distortion, bit 1 covariances); an upload resets it to none
+  int lens = 0;
+  double *lens_kc = nullptr;    // [nC][5] k1..k5, allocated while distortion is set
+  double *lens_w = nullptr;     // [nO][4] (l00, l01, l11, 0): L^T L = Sigma^-1, allocated while covariances are set
   int *iidx = nullptr;          // [nO] point of each observation    (iidx_buffer)
   int *jidx = nullptr;          // [nO] camera of each observation   (jidx_buffer)
   int *ptr = nullptr;           // [nP+1] point CSR over observations (replaces blkIdx_buffer)

@@ -4,11 +4,13 @@
 // the parameter split the driver performs (PSBA/main.cpp:131-149; fixed-K variant
 // PSBA/main_bak.cpp:32,65-71).  Format: SURVEY.md Appendix C.
 //   cams file: one camera per line, '#' comments; 7 columns (q0..q3 tx ty tz), 12 columns
-//              (fu u0 v0 ar s + those 7) or 17 columns (+5 distortion terms, ignored: the
-//              reference never optimises or applies them, main.cpp:73,102-103).
-//   pts file : X Y Z nframes { frame x y [cov] } ...; covariance (4 or 3 values) is
-//              detected from the first line and skipped (reference reads, then ignores it,
-//              main.cpp:112).
+//              (fu u0 v0 ar s + those 7) or 17 columns (fu u0 v0 ar s, kc(1:5), q, t).  The
+//              reference never optimises or applies the distortion terms (main.cpp:73,102-103);
+//              psba_read_problem skips them, psba_read_problem_ex returns them (camera_model.h).
+//   pts file : X Y Z nframes { frame x y [cov] } ...; covariance (4 values row-major or 3:
+//              xx xy yy) is detected from the first line (readparams.cpp:272-283,380-412); the
+//              reference then ignores it (main.cpp:112), and so does psba_read_problem;
+//              psba_read_problem_ex returns it, expanded to 4 values, in observation order.
 // Difference kept on purpose: frames of a point are sorted by camera id.  The reference
 // stores projections in file order but indexes them in camera order (readparams.cpp:364-373
 // vs misc.cpp:189-216) and so silently needs ascending ids; every bundled file has them.
@@ -64,6 +66,10 @@ T *dup(const std::vector<T> &v) {
   return p;
 }
 
+// the reader behind psba_read_problem (kc, cov null) and psba_read_problem_ex
+int read_problem(const char *cams_file, const char *pts_file, const double *fixedK, psba_problem *out,
+                 std::vector<double> *kc_out, std::vector<double> *cov_out);
+
 }  // namespace
 
 extern "C" {
@@ -82,6 +88,38 @@ void psba_free_problem(psba_problem *p) {
 
 int psba_read_problem(const char *cams_file, const char *pts_file, const double *fixedK,
                       psba_problem *out) {
+  return read_problem(cams_file, pts_file, fixedK, out, nullptr, nullptr);
+}
+
+void psba_free_problem_ex(psba_problem_ex *p) {
+  if (!p) return;
+  psba_free_problem(&p->base);
+  free(p->kc);
+  free(p->cov);
+  p->kc = p->cov = nullptr;
+}
+
+int psba_read_problem_ex(const char *cams_file, const char *pts_file, const double *fixedK, psba_problem_ex *out) {
+  if (!out) return PSBA_E_INVALID;
+  out->kc = out->cov = nullptr;
+  std::vector<double> kc, cov;
+  const int rc = read_problem(cams_file, pts_file, fixedK, &out->base, &kc, &cov);
+  if (rc != PSBA_OK) return rc;
+  if (!kc.empty()) out->kc = dup(kc);
+  if (!cov.empty()) out->cov = dup(cov);
+  if ((!kc.empty() && !out->kc) || (!cov.empty() && !out->cov)) {
+    psba_free_problem_ex(out);
+    return PSBA_E_NOMEM;
+  }
+  return PSBA_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int read_problem(const char *cams_file, const char *pts_file, const double *fixedK, psba_problem *out,
+                 std::vector<double> *kc_out, std::vector<double> *cov_out) {
   if (!cams_file || !pts_file || !out) return PSBA_E_INVALID;
   memset(out, 0, sizeof *out);
   FILE *fc = fopen(cams_file, "r");
@@ -106,6 +144,7 @@ int psba_read_problem(const char *cams_file, const char *pts_file, const double 
     } else {
       K.insert(K.end(), vals.begin(), vals.begin() + 5);
     }
+    if (ncol == 17 && kc_out) kc_out->insert(kc_out->end(), vals.begin() + 5, vals.begin() + 10);
     // quat2vec (misc.cpp:38-43): normalise, force a non-negative scalar part
     const double mag = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     const double sg = (q[0] >= 0.0) ? 1.0 : -1.0;
@@ -121,7 +160,7 @@ int psba_read_problem(const char *cams_file, const char *pts_file, const double 
     nC++;
   }
   int nP = 0, per = -1;
-  struct Ob { int cam; double x, y; };
+  struct Ob { int cam; double x, y, c[4]; };
   std::vector<Ob> obs;
   while (rc == PSBA_OK && read_data_line(fp, line)) {
     if (!parse_doubles(line, vals) || vals.size() < 4) { rc = PSBA_E_IO; break; }
@@ -139,7 +178,12 @@ int psba_read_problem(const char *cams_file, const char *pts_file, const double 
       const double *o = vals.data() + 4 + (size_t)per * f;
       const int cam = (int)o[0];
       if ((double)cam != o[0] || cam < 0 || cam >= nC) { rc = PSBA_E_IO; break; }
-      obs.push_back({cam, o[1], o[2]});
+      Ob ob{cam, o[1], o[2], {0.0, 0.0, 0.0, 0.0}};
+      if (per == 7)
+        for (int k = 0; k < 4; k++) ob.c[k] = o[3 + k];
+      else if (per == 6)  // xx xy yy
+        ob.c[0] = o[3], ob.c[1] = ob.c[2] = o[4], ob.c[3] = o[5];
+      obs.push_back(ob);
     }
     if (rc != PSBA_OK) break;
     std::stable_sort(obs.begin(), obs.end(), [](const Ob &a, const Ob &b) { return a.cam < b.cam; });
@@ -151,6 +195,7 @@ int psba_read_problem(const char *cams_file, const char *pts_file, const double 
       jidx.push_back(o.cam);
       impts.push_back(o.x);
       impts.push_back(o.y);
+      if (per > 3 && cov_out) cov_out->insert(cov_out->end(), o.c, o.c + 4);
     }
     nP++;
   }
@@ -175,6 +220,13 @@ int psba_read_problem(const char *cams_file, const char *pts_file, const double 
   }
   return PSBA_OK;
 }
+
+// BAL -> sba (psba_convert_bal, psba_convert_bal_kd)
+int convert_bal(const char *bal_file, const char *cams_out, const char *pts_out, double *max_abs_k, bool with_kc);
+
+}  // namespace
+
+extern "C" {
 
 // ---- writer ------------------------------------------------------------------------------
 // The reference declares printSBAMotionData / printSBAStructureData / printSBAData and keeps them
@@ -231,7 +283,22 @@ int psba_write_problem(const char *cams_file, const char *pts_file, int nCams, i
 // distortion, PSBA/main.cpp:73,102-103); *max_abs_k (may be NULL) returns the largest |k1|, |k2|
 // dropped so that the caller can judge it.  Observations are written point-major, cameras
 // ascending, which is what every consumer of the format assumes.
+// psba_convert_bal_kd keeps k1, k2: 17-column cams "f 0 0 1 0 k1 k2 0 0 0 q t".  BAL's normalised point
+// p = -P / P.z becomes (x', y') = (p.x, -p.y) here, with the same |p|^2, so f (1 + k1 |p|^2 + k2 |p|^4) p is
+// exactly this library's distortion model (camera_model.h) with kc = (k1, k2, 0, 0, 0).
 int psba_convert_bal(const char *bal_file, const char *cams_out, const char *pts_out, double *max_abs_k) {
+  return convert_bal(bal_file, cams_out, pts_out, max_abs_k, false);
+}
+
+int psba_convert_bal_kd(const char *bal_file, const char *cams_out, const char *pts_out) {
+  return convert_bal(bal_file, cams_out, pts_out, nullptr, true);
+}
+
+}  // extern "C"
+
+namespace {
+
+int convert_bal(const char *bal_file, const char *cams_out, const char *pts_out, double *max_abs_k, bool with_kc) {
   if (!bal_file || !cams_out || !pts_out) return PSBA_E_INVALID;
   FILE *fb = fopen(bal_file, "r");
   if (!fb) return PSBA_E_IO;
@@ -268,8 +335,12 @@ int psba_convert_bal(const char *bal_file, const char *cams_out, const char *pts
     const double q[4] = {std::cos(0.5 * th), k * c[0], k * c[1], k * c[2]};
     // (0, 1, 0, 0) (x) q : the half turn about x applied after R
     const double qf[4] = {-q[1], q[0], -q[3], q[2]};
-    fprintf(fc, "%.17g 0 0 1 0 %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", c[6], qf[0], qf[1], qf[2], qf[3], c[3],
-            -c[4], -c[5]);
+    if (with_kc)
+      fprintf(fc, "%.17g 0 0 1 0 %.17g %.17g 0 0 0 %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", c[6], c[7], c[8], qf[0], qf[1],
+              qf[2], qf[3], c[3], -c[4], -c[5]);
+    else
+      fprintf(fc, "%.17g 0 0 1 0 %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", c[6], qf[0], qf[1], qf[2], qf[3], c[3],
+              -c[4], -c[5]);
     kmax = std::max(kmax, std::max(std::fabs(c[7]), std::fabs(c[8])));
   }
   if (fclose(fc) != 0) return PSBA_E_IO;
@@ -288,4 +359,4 @@ int psba_convert_bal(const char *bal_file, const char *cams_out, const char *pts
   return PSBA_OK;
 }
 
-}  // extern "C"
+}  // namespace
