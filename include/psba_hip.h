@@ -128,6 +128,37 @@ int psba_set_distortion(psba_handle h, const double *kc);
  * relative (the error text names the observation) */
 int psba_set_obs_covariance(psba_handle h, const double *cov);
 int psba_lens_model(psba_handle h, int *has_distortion, int *has_covariance);
+
+/* ---- robust losses --------------------------------------------------------------------
+ * Model (the same in psba_amd/csrc/camera_model.h and DESIGN.md): s_a = ||L_a e_a||^2 is the whitened squared
+ * residual (L_a = I without covariances) and the cost becomes F = sum_a rho(s_a).  The scale c > 0 is in whitened
+ * units (pixels when Sigma = I), c2 = c^2:
+ *   PSBA_LOSS_NONE     rho = s                                          rho' = 1
+ *   PSBA_LOSS_HUBER    rho = s if s <= c2, else 2 c sqrt(s) - c2          rho' = 1, else c / sqrt(s)
+ *   PSBA_LOSS_CAUCHY   rho = c2 log(1 + s / c2)                           rho' = 1 / (1 + s / c2)
+ *   PSBA_LOSS_SOFT_L1  rho = 2 c2 (sqrt(1 + s / c2) - 1)                  rho' = 1 / sqrt(1 + s / c2)
+ * rho(0) = 0 and rho'(0) = 1 for every loss (no 1/2, the reference's convention).  The normal equations are those
+ * of weighted Gauss-Newton (IRLS): w_a = sqrt(rho'(s_a)) after the whitening, e <- w e, A <- w A, B <- w B, so
+ * g = A~^T e~ is the gradient of F (halved, in the sign convention of g).  The rho'' term of the Hessian is left
+ * out (negative for these losses: it would break positive definiteness).  psba_residual, the try scalars and the
+ * loop logs report F; the LM gain ratio compares the drop of F with the drop the weighted model predicts.
+ * The mirror verbs return what the normal equations see: psba_compute_exQT w L e, psba_compute_jacobiQT w L A and
+ * w L B, psba_compute_Jmultiply J~ x.
+ * Rules as for the lens model above: PSBA_E_STATE before psba_upload_problem, under PSBA_CAMERA_FREE_K and while a
+ * try is in flight; PSBA_E_INVALID for an unknown kind or a scale that is not finite and > 0 (checked for every
+ * kind).  Setting a loss discards a linearization queued ahead; an upload resets it to PSBA_LOSS_NONE with scale 1.
+ * PSBA_LOSS_NONE runs exactly the kernels of a handle that never set a loss.  The reference has no robust loss:
+ * PARITY UNPINNED -- checked against a numpy twin, finite differences and a dense solve. */
+#define PSBA_LOSS_NONE 0
+#define PSBA_LOSS_HUBER 1
+#define PSBA_LOSS_CAUCHY 2
+#define PSBA_LOSS_SOFT_L1 3
+int psba_set_robust_loss(psba_handle h, int kind, double scale);
+int psba_robust_loss(psba_handle h, int *kind, double *scale);
+/* s[n2Dprojs]: s_a = ||L_a e_a||^2 of each of this rank's observations (uploaded order) at the current
+ * (PSBA_PARAMS_CUR) or proposed (PSBA_PARAMS_NEW) parameters, under any loss: observations with s_a well above c2
+ * are the ones the loss down-weights.  Fixed-intrinsics camera block only. */
+int psba_obs_sq_residuals(psba_handle h, int which, double *s);
 /* which S-assembly route the uploaded problem takes: 0 = LDS-resident partitions of the block
  * triangle with the static schedule (fewer than 2048 cameras, up to 8 GB of partial-sum slabs on
  * this rank), 1 = the owner route for larger problems (one thread per block segment,
@@ -142,7 +173,7 @@ int psba_schur_path(psba_handle h, int *path);
  * One damping try = psba_schur_assemble -> psba_schur_reduce -> psba_schur_solve ->
  * psba_backsub; nothing is copied to the host in between. */
 
-/* ||e||^2 at a parameter set: compute_exQT + compute_L2_sq
+/* ||e||^2 at a parameter set (the robust cost sum rho(s_a) under a loss): compute_exQT + compute_L2_sq
  * (PSBA/sba_func.h:10-19, PSBA/levmar.cpp:93-94,188-193, PSBA/misc.cpp:151-157).
  * With a communicator attached the value is summed over all ranks. */
 int psba_residual(psba_handle h, int which, double *cost);
@@ -200,6 +231,7 @@ int psba_accept(psba_handle h);
  * PSBA_structPtr collapse into the handle.  A NULL host pointer means "stay on device"
  * exactly as in the reference.  Each verb leaves the device state as the reference's
  * wrapper of the same name does. */
+/* ex: the residual the normal equations see (w L e under a robust loss and covariances) */
 int psba_compute_exQT(psba_handle h, int which, double *ex);             /* sba_func.h:10-19 */
 int psba_compute_jacobiQT(psba_handle h, double *jac_A, double *jac_B);  /* sba_func.h:26-32 */
 int psba_compute_U(psba_handle h, double coeff, double *out);            /* sba_func.h:38-44 */

@@ -6,7 +6,9 @@ fallback: importing :mod:`psba_amd.capi` raises if the library has not been buil
 a handle raises if no GPU is present.
 """
 from .capi import (Psba, PsbaError, Problem, lib, lib_path, read_problem, partition_points,  # noqa: F401
-                   write_problem, convert_bal, read_problem_ex, convert_bal_kd)
+                   write_problem, convert_bal, read_problem_ex, convert_bal_kd,
+                   LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY, LOSS_SOFT_L1)
 
 __all__ = ["Psba", "PsbaError", "Problem", "lib", "lib_path", "read_problem", "partition_points",
-           "write_problem", "convert_bal", "read_problem_ex", "convert_bal_kd"]
+           "write_problem", "convert_bal", "read_problem_ex", "convert_bal_kd",
+           "LOSS_NONE", "LOSS_HUBER", "LOSS_CAUCHY", "LOSS_SOFT_L1"]

@@ -16,6 +16,7 @@ lib = C.CDLL(lib_path)
 
 PSBA_OK, PSBA_NOT_SPD, PSBA_SINGULAR_V = 0, 1, 2
 PARAMS_CUR, PARAMS_NEW = 0, 1
+LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY, LOSS_SOFT_L1 = 0, 1, 2, 3
 ITER_TURN_TO_LM, ITER_TURN_TO_TR, ITER_CONTINUE, ITER_ERR = 1, 2, 3, 4
 ITER_DP_NO_CHANGE, ITER_ERR_SMALL_ENOUGH, ITER_PASS = 5, 6, 7
 K_LINEARIZE, K_SCHUR, K_CHOLESKY, K_BACKSUB, K_RESIDUAL, K_ALLREDUCE, K_SCHUR_REDUCE = range(7)
@@ -149,6 +150,9 @@ SIGNATURES = [
     ("psba_set_distortion", C.c_int, [_h, _dp]),
     ("psba_set_obs_covariance", C.c_int, [_h, _dp]),
     ("psba_lens_model", C.c_int, [_h, _ip, _ip]),
+    ("psba_set_robust_loss", C.c_int, [_h, C.c_int, C.c_double]),
+    ("psba_robust_loss", C.c_int, [_h, _ip, _dp]),
+    ("psba_obs_sq_residuals", C.c_int, [_h, C.c_int, _dp]),
     ("psba_read_problem_ex", C.c_int, [C.c_char_p, C.c_char_p, _dp, C.POINTER(CProblemEx)]),
     ("psba_free_problem_ex", None, [C.POINTER(CProblemEx)]),
     ("psba_convert_bal_kd", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
@@ -453,6 +457,21 @@ class Psba:
         d, c = C.c_int(), C.c_int()
         self._ck(lib.psba_lens_model(self._h, C.byref(d), C.byref(c)))
         return bool(d.value), bool(c.value)
+
+    def set_robust_loss(self, kind, scale=1.0):
+        """psba_set_robust_loss: kind LOSS_NONE / LOSS_HUBER / LOSS_CAUCHY / LOSS_SOFT_L1, scale c > 0 in whitened
+        units (pixels when Sigma = I)."""
+        self._ck(lib.psba_set_robust_loss(self._h, int(kind), float(scale)))
+
+    def robust_loss(self):
+        """psba_robust_loss -> (kind, scale)"""
+        k, c = C.c_int(), C.c_double()
+        self._ck(lib.psba_robust_loss(self._h, C.byref(k), C.byref(c)))
+        return k.value, c.value
+
+    def obs_sq_residuals(self, which=PARAMS_CUR):
+        """psba_obs_sq_residuals: s_a = ||L_a e_a||^2 per observation [nO] at PARAMS_CUR / PARAMS_NEW."""
+        return self._out(lib.psba_obs_sq_residuals, self.nO, which)[1]
 
     def camera_block(self):
         n = C.c_int()

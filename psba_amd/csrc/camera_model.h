@@ -10,6 +10,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace psba {
 
 #define PSBA_HD __host__ __device__ __forceinline__
@@ -165,8 +167,8 @@ PSBA_HD void linearize_obs_freek(const double *p, const double *q0, const double
 // Covariances: observation a has an SPD 2x2 Sigma_a; the host factors Sigma_a^-1 = L_a^T L_a with L_a upper
 // triangular, stored (l00, l01, l11, 0).  The kernels whiten right after the projection (e <- L e, A <- L A,
 // B <- L B), so the cost is sum e^T Sigma^-1 e and everything downstream is the same normal equations.
-// The lens model of a kernel instantiation: bit 0 distortion, bit 1 covariances.
-enum { LENS_PLAIN = 0, LENS_DIST = 1, LENS_COV = 2, LENS_BOTH = 3 };
+// The lens model of a kernel instantiation: bit 0 distortion, bit 1 covariances, bit 2 robust loss (below).
+enum { LENS_PLAIN = 0, LENS_DIST = 1, LENS_COV = 2, LENS_BOTH = 3, LENS_ROBUST = 4, LENS_MODELS = 8 };
 constexpr int LENS_WSTRIDE = 4;  // doubles per observation of the whitening factors (l00, l01, l11, pad)
 
 // (xd, yd) and, when J is given, d(xd, yd) / d(x, y) row-major
@@ -281,6 +283,74 @@ PSBA_HD void whiten_obs(const double *w, double *e, double *A, double *B) {
   for (int k = 0; k < 3; k++) whiten2(w, B[k], B[3 + k]);
 }
 
+// ---- robust losses (the same model in include/psba_hip.h and DESIGN 7b) ----
+// s_a = ||L_a e_a||^2 is the whitened squared residual (L_a = I without covariances); the cost is F = sum_a rho(s_a)
+// with a scale c > 0 in whitened units (pixels when Sigma = I), c2 = c^2:
+//   NONE     rho = s                            rho' = 1
+//   HUBER    rho = s (s <= c2), 2 c sqrt(s) - c2  rho' = 1, c / sqrt(s)
+//   CAUCHY   rho = c2 log(1 + s / c2)            rho' = 1 / (1 + s / c2)
+//   SOFT_L1  rho = 2 c2 (sqrt(1 + s / c2) - 1)   rho' = 1 / sqrt(1 + s / c2)
+// rho(0) = 0 and rho'(0) = 1 for all four (no 1/2: the reference's convention).  The normal equations are those of
+// weighted Gauss-Newton (IRLS): w = sqrt(rho'(s)) after the whitening, e <- w e, A <- w A, B <- w B, so that
+// A~^T e~ is the gradient of F (halved, in the sign convention of g).  The rho'' term of the Hessian is left out:
+// it is negative for these three losses and would break positive definiteness.
+// The kind is uniform over a launch (no divergence within a wave); w is recomputed wherever the Jacobian blocks
+// are (K1, K3, k_jmul) from the same inputs, so every kernel sees the same w bit for bit and none is stored.
+enum { LOSS_NONE = 0, LOSS_HUBER = 1, LOSS_CAUCHY = 2, LOSS_SOFT_L1 = 3 };
+struct RobustLoss {
+  double c, c2, ic2;  // scale, c^2, 1 / c^2
+  int kind;
+};
+inline RobustLoss make_robust_loss(int kind, double c) {
+  RobustLoss r;
+  r.c = c;
+  r.c2 = c * c;
+  r.ic2 = 1.0 / r.c2;
+  r.kind = kind;
+  return r;
+}
+// rho(s) and w = sqrt(rho'(s)).  Huber's two branches are a select (both sides are finite or unused: c / 0 = inf
+// only where s <= c2 picks 1); soft-L1's rho is written as 2 s / (sqrt(1 + s / c2) + 1), the same value without the
+// cancellation of sqrt(1 + s / c2) - 1 at s << c2.
+PSBA_HD void robust_eval(const RobustLoss &rl, double s, double &rho, double &w) {
+  switch (rl.kind) {
+    case LOSS_HUBER: {
+      const double r = sqrt(s);
+      const bool in = s <= rl.c2;
+      rho = in ? s : 2.0 * rl.c * r - rl.c2;
+      w = in ? 1.0 : sqrt(rl.c / r);
+      break;
+    }
+    case LOSS_CAUCHY: {
+      const double u = 1.0 + s * rl.ic2;
+      rho = rl.c2 * log1p(s * rl.ic2);
+      w = 1.0 / sqrt(u);
+      break;
+    }
+    case LOSS_SOFT_L1: {
+      const double r = sqrt(1.0 + s * rl.ic2);
+      rho = 2.0 * s / (r + 1.0);
+      w = 1.0 / sqrt(r);
+      break;
+    }
+    default:
+      rho = s;
+      w = 1.0;
+      break;
+  }
+}
+// e <- w e, A <- w A, B <- w B with w of s = |e|^2 (e already whitened)
+PSBA_HD void robust_scale(const RobustLoss &rl, double *e, double *A, double *B) {
+  double rho, w;
+  robust_eval(rl, e[0] * e[0] + e[1] * e[1], rho, w);
+  e[0] *= w;
+  e[1] *= w;
+#pragma unroll
+  for (int k = 0; k < 12; k++) A[k] *= w;
+#pragma unroll
+  for (int k = 0; k < 6; k++) B[k] *= w;
+}
+
 // loads of camera j's kc and observation a's whitening factors (nothing under a model without them)
 template <int LM>
 PSBA_HD void lens_load_kc(const double *src, size_t j, double *kc) {
@@ -300,15 +370,16 @@ PSBA_HD void lens_load_w(const double *src, size_t a, double *w) {
 }
 
 // the per-observation entry points of the fixed-intrinsics kernels: LM = LENS_PLAIN is exactly linearize_obs /
-// residual_obs (kc and w are not read)
+// residual_obs (kc, w and rl are not read)
 template <int LM>
 PSBA_HD void lens_linearize(const double *cc, const double *cam, const double *M, const double *kc, const double *w,
-                            double mx, double my, double *e, double *A, double *B) {
+                            const RobustLoss &rl, double mx, double my, double *e, double *A, double *B) {
   if constexpr ((LM & LENS_DIST) != 0)
     linearize_obs_dist(cc, cc + 5, cam, M, kc, mx, my, e, A, B);
   else
     linearize_obs(cc, cc + 5, cam, M, mx, my, e, A, B);
   if constexpr ((LM & LENS_COV) != 0) whiten_obs(w, e, A, B);
+  if constexpr ((LM & LENS_ROBUST) != 0) robust_scale(rl, e, A, B);
 }
 template <int LM>
 PSBA_HD void lens_residual(const double *cc, const double *cam, const double *M, const double *kc, const double *w,
@@ -318,6 +389,37 @@ PSBA_HD void lens_residual(const double *cc, const double *cam, const double *M,
   else
     residual_obs(cc, cc + 5, cam, M, mx, my, e0, e1);
   if constexpr ((LM & LENS_COV) != 0) whiten2(w, e0, e1);
+}
+// the cost term of one observation from its whitened residual (lens_residual): s = |e|^2, or rho(s) under the robust
+// bit, which also scales e <- w e (the residual the normal equations see) and stores s to *s_out when given
+template <int LM>
+PSBA_HD double lens_cost(const RobustLoss &rl, double &e0, double &e1, double *s_out = nullptr) {
+  const double s = e0 * e0 + e1 * e1;
+  if constexpr ((LM & LENS_ROBUST) != 0) {
+    double rho, w;
+    robust_eval(rl, s, rho, w);
+    e0 *= w;
+    e1 *= w;
+    if (s_out) *s_out = s;
+    return rho;
+  } else {
+    return s;
+  }
+}
+
+// calls f(std::integral_constant<int, LM>()) for the lens model lm of a handle (the launch sites' dispatch)
+template <class F>
+void lens_dispatch(int lm, F &&f) {
+  switch (lm) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 5: f(std::integral_constant<int, 5>()); break;
+    case 6: f(std::integral_constant<int, 6>()); break;
+    case 7: f(std::integral_constant<int, 7>()); break;
+    default: f(std::integral_constant<int, 0>()); break;
+  }
 }
 
 // symmetric 3x3 inverse by the closed form the reference uses (T = -det,

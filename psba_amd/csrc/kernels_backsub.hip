@@ -32,14 +32,14 @@ struct BackArgs {
   int cam_terms;       // 1 on the rank that owns the camera terms of the scalar sums
   int mode;            // development ablation (PSBA_BACK_MODE): 1 no residual pass, 2 no W^T dpa pass
   const double *kc, *wl;  // lens model (camera_model.h): read only by the LENS_DIST / LENS_COV instantiations
-};
+};  // (the robust loss is the kernels' last argument, read only by the LENS_ROBUST instantiations)
 
 // RECOMP: W_ij^T dpa_j = coeff B_ij^T (A_ij dpa_j) from the Jacobian blocks recomputed at the current
 // parameters (~300 flop per observation) instead of from the stored W (144 bytes per observation:
 // 50 of the kernel's 66 MB at venice size); the camera constants and parameters loaded for it are
 // the ones the residual pass needs anyway.  (PSBA_BACK_READ_W=1: the W-reading form.)
 template <bool DUMP, bool RECOMP, int LM>
-__global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p) {
+__global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p, RobustLoss rl) {
   __shared__ double sT[TILE_OBS][3];   // W_a^T dpa_j per observation
   __shared__ double sNP[TILE_OBS][3];  // proposed point per point of the tile
   __shared__ double sRed[4][4];
@@ -88,11 +88,16 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p) {
     }
     __syncthreads();
     double cc[9], cam[6], da[6], kc[5], wl[3];
+    // a robust loss scales A and B by w(s) of the residual at the current parameters, so the recomputed blocks need
+    // the real measurement (K1's inputs, hence K1's w bit for bit); without the bit the measurement is 0 (e unused)
+    constexpr bool MEAS = RECOMP && (LM & LENS_ROBUST) != 0;
+    double2 m = make_double2(0.0, 0.0);
     if (RECOMP && a < o1) {
 #pragma unroll
       for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * j + k];
       lens_load_kc<LM>(p.kc, j, kc);
       lens_load_w<LM>(p.wl, a, wl);
+      if (MEAS) m = reinterpret_cast<const double2 *>(p.impts)[a];
 #pragma unroll
       for (int k = 0; k < 6; k++) {
         cam[k] = p.cams[6 * j + k];
@@ -105,7 +110,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p) {
         double M[3], e[2], A[12], B[6];
 #pragma unroll
         for (int k = 0; k < 3; k++) M[k] = p.pts[3 * (size_t)i + k];
-        lens_linearize<LM>(cc, cam, M, kc, wl, 0.0, 0.0, e, A, B);
+        lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
         double s0 = 0.0, s1 = 0.0;
 #pragma unroll
         for (int k = 0; k < 6; k++) {
@@ -191,9 +196,9 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p) {
 #pragma unroll
         for (int k = 0; k < 6; k++) cam[k] += da[k];
       }
-      const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
+      if (!MEAS) m = reinterpret_cast<const double2 *>(p.impts)[a];
       lens_residual<LM>(cc, cam, sNP[i - p0], kc, wl, m.x, m.y, e0, e1);
-      s_cost += e0 * e0 + e1 * e1;
+      s_cost += lens_cost<LM>(rl, e0, e1);
     }
     dsc = dn;
     i = j = 0;
@@ -224,7 +229,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p) {
 // workgroup walks its observations twice, TILE_OBS at a time -- sum of W_ij^T dpa_j (from the
 // stored W), then dpb_i and the proposed point by one thread, then the residuals at the proposal.
 template <bool DUMP, int LM>
-__global__ __launch_bounds__(TILE_OBS) void k_backsub_long(BackArgs p, const int *long_pts) {
+__global__ __launch_bounds__(TILE_OBS) void k_backsub_long(BackArgs p, const int *long_pts, RobustLoss rl) {
   __shared__ double sRed[TILE_OBS / 64][4];
   __shared__ double sNP[3];
   const int tid = threadIdx.x, i = long_pts[blockIdx.x];
@@ -292,7 +297,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub_long(BackArgs p, const int
     lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
     lens_residual<LM>(cc, cam, sNP, kc, wl, m.x, m.y, e0, e1);
-    s_cost += e0 * e0 + e1 * e1;
+    s_cost += lens_cost<LM>(rl, e0, e1);
   }
   __syncthreads();
   {
@@ -327,20 +332,20 @@ int launch_publish_scal(psba_ctx *h, hipStream_t s) {
 
 // K3 for lens model LM (psba_ctx::lens)
 template <int LM>
-static void enqueue_backsub(psba_ctx *h, const BackArgs &a, int grid, bool dump, bool read_w) {
+static void enqueue_backsub(psba_ctx *h, const BackArgs &a, const RobustLoss &rl, int grid, bool dump, bool read_w) {
   if (dump && read_w)
-    hipLaunchKernelGGL((k_backsub<true, false, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+    hipLaunchKernelGGL((k_backsub<true, false, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
   else if (dump)
-    hipLaunchKernelGGL((k_backsub<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+    hipLaunchKernelGGL((k_backsub<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
   else if (read_w)
-    hipLaunchKernelGGL((k_backsub<false, false, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+    hipLaunchKernelGGL((k_backsub<false, false, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
   else
-    hipLaunchKernelGGL((k_backsub<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+    hipLaunchKernelGGL((k_backsub<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
   if (h->nLong) {  // points seen by more cameras than a tile holds
     if (dump)
-      hipLaunchKernelGGL((k_backsub_long<true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts);
+      hipLaunchKernelGGL((k_backsub_long<true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, rl);
     else
-      hipLaunchKernelGGL((k_backsub_long<false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts);
+      hipLaunchKernelGGL((k_backsub_long<false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, rl);
   }
 }
 
@@ -373,6 +378,7 @@ int launch_backsub(psba_ctx *h, double mu, bool dump) {
   a.cam_terms = h->rank == 0 ? 1 : 0;
   a.kc = h->lens_kc;
   a.wl = h->lens_w;
+  const RobustLoss rl = make_robust_loss(h->loss_kind, h->loss_c);
   {
     const char *m = getenv("PSBA_BACK_MODE");
     a.mode = m ? atoi(m) : 0;
@@ -387,12 +393,7 @@ int launch_backsub(psba_ctx *h, double mu, bool dump) {
   {
     ProfScope ps(h, PSBA_K_BACKSUB);
     const bool read_w = getenv("PSBA_BACK_READ_W") != nullptr;
-    switch (h->lens) {
-      case LENS_DIST: enqueue_backsub<LENS_DIST>(h, a, grid, dump, read_w); break;
-      case LENS_COV: enqueue_backsub<LENS_COV>(h, a, grid, dump, read_w); break;
-      case LENS_BOTH: enqueue_backsub<LENS_BOTH>(h, a, grid, dump, read_w); break;
-      default: enqueue_backsub<LENS_PLAIN>(h, a, grid, dump, read_w); break;
-    }
+    lens_dispatch(h->lens, [&](auto m) { enqueue_backsub<decltype(m)::value>(h, a, rl, grid, dump, read_w); });
   }
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;

@@ -34,14 +34,15 @@ struct LinArgs {
   double *pub_dst;  // nullptr: nothing to publish
   double pub_stamp;
   // lens model (camera_model.h): [nC][5] distortion, [nO][LENS_WSTRIDE] whitening factors; read only by the
-  // LENS_DIST / LENS_COV instantiations
+  // LENS_DIST / LENS_COV instantiations.  The robust loss is every kernel's last argument (read only by the
+  // LENS_ROBUST instantiations; behind the others, so that their offsets stay put).
   const double *kc, *wl;
 };
 
 // GACC: many cameras -- the 27 sums per camera do not fit the LDS.  They are then formed by a
 // camera-major pass of their own (k_cam_sums) and this kernel leaves them out.
 template <bool DUMP, bool GACC, int LM>
-__global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p) {
+__global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p, RobustLoss rl) {
   __shared__ double sBE[TILE_OBS][9];  // B(6) | e(2) per observation of the tile (+1: odd row stride)
   __shared__ double sW[(TILE_OBS / 2) * 19];  // W blocks of half a tile (staged in two halves: LDS for three workgroups per CU)
   extern __shared__ double sAcc[];     // [nC][27]
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p) {
       lens_load_kc<LM>(p.kc, j, kc);
       lens_load_w<LM>(p.wl, a, wl);
       const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
-      lens_linearize<LM>(cc, cam, M, kc, wl, m.x, m.y, e, A, B);
+      lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
       if (DUMP) {
         p.dbg_ex[2 * a] = e[0];
         p.dbg_ex[2 * a + 1] = e[1];
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p) {
 //  * the NEXT tile's indices and the eighteen parameter doubles they lead to are fetched as soon as this tile's
 //    Jacobian is done, so their latency runs under the camera atomics, the scan and the W flush.
 template <bool DUMP, bool GACC, int LM>
-__global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p) {
+__global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss rl) {
   __shared__ double sW[TILE_OBS * 19];          // W blocks of the tile (row stride 19 doubles: odd, conflict-free stores)
   __shared__ double sCarV[TILE_OBS / 64][9];    // a wave's last lane: its scan values (the tail of its last segment)
   __shared__ int sCarP[TILE_OBS / 64][3];       // point of the wave's first lane, of its last lane, whole wave one point?
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p) {
     const int jc = j;
     if (act) {
       double e[2], A[12], B[6];
-      lens_linearize<LM>(cc, cam, M, kc, wl, m.x, m.y, e, A, B);
+      lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
       if (DUMP) {
         p.dbg_ex[2 * (size_t)a] = e[0];
         p.dbg_ex[2 * (size_t)a + 1] = e[1];
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p) {
 // fp64 atomics into one extra slab of the per-workgroup camera sums (zeroed before the launch) that
 // k_cam_reduce adds like any other -- with GACC the camera-major pass covers these observations anyway.
 template <bool DUMP, bool GACC, int LM>
-__global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const int *long_pts, double *cam_slab) {
+__global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const int *long_pts, double *cam_slab, RobustLoss rl) {
   __shared__ double sRed[TILE_OBS / 64][9];
   const int tid = threadIdx.x, i = long_pts[blockIdx.x];
   const int o0 = p.ptr[i], o1 = p.ptr[i + 1];
@@ -384,7 +385,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const in
     lens_load_kc<LM>(p.kc, j, kc);
     lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
-    lens_linearize<LM>(cc, cam, M, kc, wl, m.x, m.y, e, A, B);
+    lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
     if (DUMP) {
       p.dbg_ex[2 * (size_t)a] = e[0];
       p.dbg_ex[2 * (size_t)a + 1] = e[1];
@@ -437,7 +438,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const in
 // fp64 atomic adds per segment.  (Through per-observation atomics from the point-major kernel the
 // same sums took 25 ms at 20 M observations; the reference scans all points per output scalar.)
 template <int LM>
-__global__ __launch_bounds__(256) void k_cam_sums(LinArgs p, const int *cam_obs, const int4 *units, int nUnits) {
+__global__ __launch_bounds__(256) void k_cam_sums(LinArgs p, const int *cam_obs, const int4 *units, int nUnits, RobustLoss rl) {
   // one wave per unit (a segment of at most 256 observations of one camera): the lanes stride
   // through the segment, the 27 sums are folded across the wave, lane 0 adds them to the camera's
   // totals.  (One thread per unit walked its 256 gathers one after the other: 380 us for 218 k
@@ -463,7 +464,7 @@ __global__ __launch_bounds__(256) void k_cam_sums(LinArgs p, const int *cam_obs,
     for (int k = 0; k < 3; k++) M[k] = p.pts[3 * (size_t)i + k];
     lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
-    lens_linearize<LM>(cc, cam, M, kc, wl, m.x, m.y, e, A, B);
+    lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
     int k = 0;
 #pragma unroll
     for (int r = 0; r < 6; r++)
@@ -545,7 +546,7 @@ __global__ __launch_bounds__(256) void k_residual(const double *camconst, const 
                                                   const double *pts, const double *impts,
                                                   const int *iidx, const int *jidx, int nO,
                                                   double *ex_out, double *cost, const double *kcs,
-                                                  const double *wls) {
+                                                  const double *wls, RobustLoss rl, double *s_out) {
   __shared__ double sRed[4];
   double sum = 0.0;
   for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < nO; a += gridDim.x * blockDim.x) {
@@ -561,11 +562,12 @@ __global__ __launch_bounds__(256) void k_residual(const double *camconst, const 
     lens_load_w<LM>(wls, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(impts)[a];
     lens_residual<LM>(cc, cam, M, kc, wl, m.x, m.y, e0, e1);
+    const double f = lens_cost<LM>(rl, e0, e1, s_out ? s_out + a : nullptr);  // s_out: robust instantiations only
     if (ex_out) {
       ex_out[2 * a] = e0;
       ex_out[2 * a + 1] = e1;
     }
-    sum += e0 * e0 + e1 * e1;
+    sum += f;
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
@@ -610,44 +612,44 @@ static int set_lin_attrs(psba_ctx *h) {
 
 // the kernels of one linearization for lens model LM (psba_ctx::lens)
 template <int LM>
-static void enqueue_linearize(psba_ctx *h, const LinArgs &a, bool dump, bool v1, size_t lds, double *Uo, double *gao) {
+static void enqueue_linearize(psba_ctx *h, const LinArgs &a, const RobustLoss &rl, bool dump, bool v1, size_t lds, double *Uo, double *gao) {
   const Dims &d = h->d;
   if (h->cam_global) {
     const int grid = d.nTiles < 2048 ? d.nTiles : 2048;
     if (v1 && dump)
-      hipLaunchKernelGGL((k_linearize<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+      hipLaunchKernelGGL((k_linearize<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
     else if (v1)
-      hipLaunchKernelGGL((k_linearize<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+      hipLaunchKernelGGL((k_linearize<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
     else if (dump)
-      hipLaunchKernelGGL((k_linearize2<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+      hipLaunchKernelGGL((k_linearize2<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
     else
-      hipLaunchKernelGGL((k_linearize2<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a);
+      hipLaunchKernelGGL((k_linearize2<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
     if (h->nLong) {
       if (dump)
-        hipLaunchKernelGGL((k_linearize_long<true, true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr);
+        hipLaunchKernelGGL((k_linearize_long<true, true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr, rl);
       else
-        hipLaunchKernelGGL((k_linearize_long<false, true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr);
+        hipLaunchKernelGGL((k_linearize_long<false, true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr, rl);
     }
     hipLaunchKernelGGL(k_cam_sums<LM>, dim3((h->nCamUnits + 3) / 4), dim3(256), 0, h->stream, a, h->cam_obs,
-                       h->cam_units, h->nCamUnits);
+                       h->cam_units, h->nCamUnits, rl);
     hipLaunchKernelGGL(k_cam_finalize, dim3((42 * d.nC + 255) / 256), dim3(256), 0, h->stream, h->camacc, d.nC,
                        h->coeff, h->coeff_g, Uo, gao);
   } else {
     if (v1 && dump)
-      hipLaunchKernelGGL((k_linearize<true, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
+      hipLaunchKernelGGL((k_linearize<true, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl);
     else if (v1)
-      hipLaunchKernelGGL((k_linearize<false, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
+      hipLaunchKernelGGL((k_linearize<false, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl);
     else if (dump)
-      hipLaunchKernelGGL((k_linearize2<true, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
+      hipLaunchKernelGGL((k_linearize2<true, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl);
     else
-      hipLaunchKernelGGL((k_linearize2<false, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a);
+      hipLaunchKernelGGL((k_linearize2<false, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl);
     int nslab = h->nPart;
     if (h->nLong) {  // their camera sums: one more slab (zeroed by the caller)
       double *slab = h->campart + (size_t)h->nPart * d.nC * CAM_ACC;
       if (dump)
-        hipLaunchKernelGGL((k_linearize_long<true, false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab);
+        hipLaunchKernelGGL((k_linearize_long<true, false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab, rl);
       else
-        hipLaunchKernelGGL((k_linearize_long<false, false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab);
+        hipLaunchKernelGGL((k_linearize_long<false, false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab, rl);
       nslab++;
     }
     hipLaunchKernelGGL(k_cam_reduce, dim3(d.nC), dim3(1024), 0, h->stream, h->campart, nslab, d.nC, h->coeff,
@@ -686,6 +688,7 @@ int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
   a.pub_stamp = h->pub_seq;
   a.kc = h->lens_kc;
   a.wl = h->lens_w;
+  const RobustLoss rl = make_robust_loss(h->loss_kind, h->loss_c);
   {
     const char *m = getenv("PSBA_LIN_MODE");
     a.mode = m ? atoi(m) : 0;
@@ -694,10 +697,9 @@ int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
   const size_t lds = h->cam_global ? 0 : sizeof(double) * CAM_ACC * (size_t)d.nC;
   // static LDS of the kernel is ~54 KiB: beyond 64 KiB in all, the dynamic part needs the attribute
   if (!h->lin_attr_set && lds > 8 * 1024) {
-    int rc = set_lin_attrs<LENS_PLAIN>(h);
-    if (rc == PSBA_OK) rc = set_lin_attrs<LENS_DIST>(h);
-    if (rc == PSBA_OK) rc = set_lin_attrs<LENS_COV>(h);
-    if (rc == PSBA_OK) rc = set_lin_attrs<LENS_BOTH>(h);
+    int rc = PSBA_OK;
+    for (int lm = 0; lm < LENS_MODELS && rc == PSBA_OK; lm++)
+      lens_dispatch(lm, [&](auto m) { rc = set_lin_attrs<decltype(m)::value>(h); });
     if (rc != PSBA_OK) return rc;
     h->lin_attr_set = true;
   }
@@ -709,19 +711,14 @@ int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
     else if (h->nLong)
       PSBA_HIP(h, hipMemsetAsync(h->campart + (size_t)h->nPart * d.nC * CAM_ACC, 0, sizeof(double) * CAM_ACC * (size_t)d.nC,
                                  h->stream));
-    switch (h->lens) {
-      case LENS_DIST: enqueue_linearize<LENS_DIST>(h, a, dump, v1, lds, Uo, gao); break;
-      case LENS_COV: enqueue_linearize<LENS_COV>(h, a, dump, v1, lds, Uo, gao); break;
-      case LENS_BOTH: enqueue_linearize<LENS_BOTH>(h, a, dump, v1, lds, Uo, gao); break;
-      default: enqueue_linearize<LENS_PLAIN>(h, a, dump, v1, lds, Uo, gao); break;
-    }
+    lens_dispatch(h->lens, [&](auto m) { enqueue_linearize<decltype(m)::value>(h, a, rl, dump, v1, lds, Uo, gao); });
   }
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }
 
-int launch_residual(psba_ctx *h, int which, double *ex_out_dev) {
-  if (h->cnp != 6) return ex_out_dev ? fail(h, PSBA_E_STATE, "the sba_func.h mirror is six-parameter only") : launch_residual_fk(h, which);
+int launch_residual(psba_ctx *h, int which, double *ex_out_dev, double *s_out_dev) {
+  if (h->cnp != 6) return ex_out_dev || s_out_dev ? fail(h, PSBA_E_STATE, "the sba_func.h mirror is six-parameter only") : launch_residual_fk(h, which);
   const Dims &d = h->d;
   const int set = which == PSBA_PARAMS_NEW ? 1 - h->cur : h->cur;
   PSBA_HIP(h, hipMemsetAsync(h->scal + SC_COST, 0, sizeof(double), h->stream));
@@ -729,16 +726,13 @@ int launch_residual(psba_ctx *h, int which, double *ex_out_dev) {
   if (grid > 256) grid = 256;  // one atomic request per workgroup; same-address atomics serialise
   {
     ProfScope ps(h, PSBA_K_RESIDUAL);
-#define PSBA_RES_LAUNCH(LM)                                                                                          \
-  hipLaunchKernelGGL(k_residual<LM>, dim3(grid), dim3(256), 0, h->stream, h->camconst, h->cams[set], h->pts[set],    \
-                     h->impts, h->iidx, h->jidx, d.nO, ex_out_dev, h->scal + SC_COST, h->lens_kc, h->lens_w)
-    switch (h->lens) {
-      case LENS_DIST: PSBA_RES_LAUNCH(LENS_DIST); break;
-      case LENS_COV: PSBA_RES_LAUNCH(LENS_COV); break;
-      case LENS_BOTH: PSBA_RES_LAUNCH(LENS_BOTH); break;
-      default: PSBA_RES_LAUNCH(LENS_PLAIN); break;
-    }
-#undef PSBA_RES_LAUNCH
+    // s_out (psba_obs_sq_residuals): the robust instantiation, with LOSS_NONE when no loss is set (rho = s, w = 1)
+    const RobustLoss rl = make_robust_loss(h->loss_kind, h->loss_c);
+    lens_dispatch(h->lens | (s_out_dev ? LENS_ROBUST : 0), [&](auto m) {
+      hipLaunchKernelGGL(k_residual<decltype(m)::value>, dim3(grid), dim3(256), 0, h->stream, h->camconst, h->cams[set],
+                         h->pts[set], h->impts, h->iidx, h->jidx, d.nO, ex_out_dev, h->scal + SC_COST, h->lens_kc,
+                         h->lens_w, rl, s_out_dev);
+    });
   }
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;

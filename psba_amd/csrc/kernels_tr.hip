@@ -34,9 +34,9 @@ struct JmulArgs {
   const double *kc, *wl;  // lens model (camera_model.h): read only by the LENS_DIST / LENS_COV instantiations
 };
 
-// J x with the whitened Jacobian blocks (covariances: L A, L B) of the handle's lens model
+// J x with the whitened Jacobian blocks (covariances: L A, L B; a robust loss: w L A, w L B) of the handle's lens model
 template <int LM>
-__global__ __launch_bounds__(256) void k_jmul(JmulArgs p) {
+__global__ __launch_bounds__(256) void k_jmul(JmulArgs p, RobustLoss rl) {  // rl: read only by the LENS_ROBUST instantiations
   __shared__ double sRed[3][4];
   double d11 = 0.0, d12 = 0.0, d22 = 0.0;
   for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < p.nO; a += gridDim.x * blockDim.x) {
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void k_jmul(JmulArgs p) {
     lens_load_kc<LM>(p.kc, j, kc);
     lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
-    lens_linearize<LM>(cc, cam, M, kc, wl, m.x, m.y, e, A, B);
+    lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
     double r1[2], r2[2];
 #pragma unroll
     for (int k = 0; k < 2; k++) {  // compute_Jmultiply.cl:32-46: row k of A_ij, then of B_ij
@@ -549,15 +549,13 @@ int launch_jmul(psba_ctx *h, const double *x1_dev, const double *x2_dev, double 
   a.nA = h->d.nA;
   a.kc = h->lens_kc;
   a.wl = h->lens_w;
+  const RobustLoss rl = make_robust_loss(h->loss_kind, h->loss_c);
   PSBA_HIP(h, hipMemsetAsync(dots_dev, 0, 3 * sizeof(double), h->stream));
   int grid = (h->d.nO + 255) / 256;
   if (grid > 1024) grid = 1024;
-  switch (h->lens) {
-    case LENS_DIST: hipLaunchKernelGGL(k_jmul<LENS_DIST>, dim3(grid), dim3(256), 0, h->stream, a); break;
-    case LENS_COV: hipLaunchKernelGGL(k_jmul<LENS_COV>, dim3(grid), dim3(256), 0, h->stream, a); break;
-    case LENS_BOTH: hipLaunchKernelGGL(k_jmul<LENS_BOTH>, dim3(grid), dim3(256), 0, h->stream, a); break;
-    default: hipLaunchKernelGGL(k_jmul<LENS_PLAIN>, dim3(grid), dim3(256), 0, h->stream, a); break;
-  }
+  lens_dispatch(h->lens, [&](auto m) {
+    hipLaunchKernelGGL(k_jmul<decltype(m)::value>, dim3(grid), dim3(256), 0, h->stream, a, rl);
+  });
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }

@@ -120,7 +120,10 @@ static void free_problem_buffers(psba_ctx *h) {
   dev_free(h->impts);
   dev_free(h->lens_kc);
   dev_free(h->lens_w);
+  dev_free(h->obs_s);
   h->lens = 0;
+  h->loss_kind = PSBA_LOSS_NONE;
+  h->loss_c = 1.0;
   dev_free(h->iidx);
   dev_free(h->jidx);
   dev_free(h->ptr);
@@ -362,6 +365,46 @@ int psba_lens_model(psba_handle h, int *has_distortion, int *has_covariance) {
   if (has_distortion) *has_distortion = (h->lens & LENS_DIST) ? 1 : 0;
   if (has_covariance) *has_covariance = (h->lens & LENS_COV) ? 1 : 0;
   return PSBA_OK;
+}
+
+// ---- robust loss (camera_model.h RobustLoss) ----
+static_assert(PSBA_LOSS_NONE == LOSS_NONE && PSBA_LOSS_HUBER == LOSS_HUBER && PSBA_LOSS_CAUCHY == LOSS_CAUCHY &&
+                  PSBA_LOSS_SOFT_L1 == LOSS_SOFT_L1,
+              "loss kinds of the C ABI and the kernels");
+
+int psba_set_robust_loss(psba_handle h, int kind, double scale) {
+  CHECK_H(h);
+  TRY(lens_settable(h, __func__));
+  if (kind < PSBA_LOSS_NONE || kind > PSBA_LOSS_SOFT_L1) return fail(h, PSBA_E_INVALID, "%s: unknown loss kind %d", __func__, kind);
+  if (!(std::isfinite(scale) && scale > 0.0))
+    return fail(h, PSBA_E_INVALID, "%s: the scale must be finite and > 0 (got %.17g)", __func__, scale);
+  h->loss_kind = kind;
+  h->loss_c = scale;
+  if (kind == PSBA_LOSS_NONE)
+    h->lens &= ~LENS_ROBUST;  // the plain instantiations: bit for bit what a handle that never set a loss computes
+  else
+    h->lens |= LENS_ROBUST;
+  lens_changed(h);
+  return PSBA_OK;
+}
+
+int psba_robust_loss(psba_handle h, int *kind, double *scale) {
+  CHECK_H(h);
+  if (kind) *kind = h->loss_kind;
+  if (scale) *scale = h->loss_c;
+  return PSBA_OK;
+}
+
+static int d2h(psba_ctx *h, void *dst, const void *src, size_t bytes);
+
+int psba_obs_sq_residuals(psba_handle h, int which, double *s) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (not PSBA_CAMERA_FREE_K)");
+  if (which != PSBA_PARAMS_CUR && which != PSBA_PARAMS_NEW) return fail(h, PSBA_E_INVALID, "%s: which = %d", __func__, which);
+  if (!h->obs_s) TRY(dev_alloc(h, &h->obs_s, (size_t)h->d.nO));
+  TRY(launch_residual(h, which, nullptr, h->obs_s));
+  return d2h(h, s, h->obs_s, sizeof(double) * (size_t)h->d.nO);
 }
 
 int psba_camera_block(psba_handle h, int *cnp) {

@@ -161,9 +161,13 @@ struct psba_ctx {
   double *pts[2] = {nullptr, nullptr};   // [nP][3] cur / proposed   (pts3D_buffer, newPts3D_buffer)
   double *params0 = nullptr;    // [nT] the parameters as uploaded (psba_reset_params)
   double *impts = nullptr;      // [nO][2]                           (impts_buffer)
-  // lens model (psba_set_distortion / psba_set_obs_covariance; camera_model.h): the launch sites pick the kernel
-  // instantiation from `lens` (bit 0 distortion, bit 1 covariances); an upload resets it to none
+  // lens model (psba_set_distortion / psba_set_obs_covariance / psba_set_robust_loss; camera_model.h): the launch
+  // sites pick the kernel instantiation from `lens` (bit 0 distortion, bit 1 covariances, bit 2 a robust loss other
+  // than none); an upload resets it to none
   int lens = 0;
+  int loss_kind = 0;            // PSBA_LOSS_* and its scale (whitened units)
+  double loss_c = 1.0;
+  double *obs_s = nullptr;      // [nO] psba_obs_sq_residuals' device output, allocated on first use
   double *lens_kc = nullptr;    // [nC][5] k1..k5, allocated while distortion is set
   double *lens_w = nullptr;     // [nO][4] (l00, l01, l11, 0): L^T L = Sigma^-1, allocated while covariances are set
   int *iidx = nullptr;          // [nO] point of each observation    (iidx_buffer)
@@ -344,7 +348,7 @@ struct ProfScope {
 // ---- kernel launchers (one per .hip file) ----
 // kernels_linearize.hip
 int launch_linearize(psba_ctx *h, bool dump, bool ahead = false, bool publish = false);
-int launch_residual(psba_ctx *h, int which, double *ex_out_dev);
+int launch_residual(psba_ctx *h, int which, double *ex_out_dev, double *s_out_dev = nullptr);
 int launch_max_diag(psba_ctx *h);
 // kernels_schur.hip
 int build_schur_plan(psba_ctx *h, int nCams, int nPts, int nObs, const int *iidx, const int *jidx,

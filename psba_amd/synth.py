@@ -263,3 +263,20 @@ def cfg5(n_pts=2_000_000, seed=0x5BA5, shard=0, n_cams=2000):
     n_pts scales the problem down for time-bound runs (the camera count, hence the 12 000 x 12 000
     dense S, stays)."""
     return make_problem(n_cams, n_pts, 10.0, seed, min_track=10, max_track=10, shard=shard)
+
+
+def add_outliers(prob, frac, lo_px, hi_px, seed):
+    """A copy of `prob` with round(frac * nO) observations (drawn without replacement) moved by a displacement of
+    random direction and a length uniform in [lo_px, hi_px] pixels: the mismatched tracks of real data.
+    Returns (problem, sorted indices of the corrupted observations)."""
+    rng = np.random.default_rng([seed, 0x0D7])
+    nO = int(prob["nO"])
+    n = int(round(frac * nO))
+    idx = np.sort(rng.choice(nO, size=n, replace=False))
+    ang = rng.uniform(0.0, 2.0 * np.pi, n)
+    r = rng.uniform(lo_px, hi_px, n)
+    impts = np.array(prob["impts"], dtype=np.float64).reshape(nO, 2).copy()
+    impts[idx] += np.stack([r * np.cos(ang), r * np.sin(ang)], 1)
+    out = Problem({k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in prob.items()})
+    out["impts"] = impts
+    return out, idx
