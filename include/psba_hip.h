@@ -468,6 +468,12 @@ int psba_set_sparse_pattern(psba_handle h, const unsigned char *flags, long long
  *   psba_chol_dist_block(B, set, buf, &n)  get (set = 0) / set the packed block B; n = its doubles
  *   psba_chol_dist_finish    the backward solve: dpa, as after psba_schur_solve */
 int psba_chol_dist_shape(psba_handle h, int *n32, int *NB, int *sharded);
+/* read-only: the route psba_schur_solve / psba_SPDinv_matVec take for this handle's matrix, from the same size
+ * limits and PSBA_CHOL_* switches the chain reads when it is enqueued (nothing is launched).  out8 =
+ * {n32, fused (k_cholg_panel with the identity rows + k_cholg_solve), fused2 (k_cholg_panel without them + the
+ * backward solve), blocked (the two-level chain; neither of the three: the flat trsm + update chain), NB,
+ * diagonal-only steps (first super-panel), look-ahead, single workgroup (PSBA_CHOL_SINGLE)} */
+int psba_chol_shape(psba_handle h, int *out8);
 /* host only: the column exchange in front of the super-panel at column JE, as the RCCL path performs it --
  * out4[k] = {block B, owner rank (B mod nranks), slot of the exchange buffer, doubles}; returns the number of
  * blocks (0: none, the last super-panel), < 0 if cap is too small.  The owner of block B packs rows 64 B .. n32

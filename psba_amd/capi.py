@@ -158,6 +158,7 @@ SIGNATURES = [
     ("psba_convert_bal_kd", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
     ("psba_chol_dist_exchange_plan", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int]),
     ("psba_chol_dist_shape", C.c_int, [_h, _ip, _ip, _ip]),
+    ("psba_chol_shape", C.c_int, [_h, _ip]),
     ("psba_chol_dist_begin", C.c_int, [_h]),
     ("psba_chol_dist_superpanel", C.c_int, [_h, C.c_int]),
     ("psba_chol_dist_block", C.c_int, [_h, C.c_int, C.c_int, _dp, C.POINTER(C.c_longlong)]),
@@ -662,6 +663,14 @@ class Psba:
         n32, nb, sh = C.c_int(), C.c_int(), C.c_int()
         self._ck(lib.psba_chol_dist_shape(self._h, C.byref(n32), C.byref(nb), C.byref(sh)))
         return n32.value, nb.value, bool(sh.value)
+
+    def chol_shape(self):
+        """psba_chol_shape: the dense chain's route as a dict (n32, fused, fused2, blocked, NB, diag_only, lookahead,
+        single)"""
+        out = (C.c_int * 8)()
+        self._ck(lib.psba_chol_shape(self._h, out))
+        keys = ("n32", "fused", "fused2", "blocked", "NB", "diag_only", "lookahead", "single")
+        return {k: (int(v) if k in ("n32", "NB") else bool(v)) for k, v in zip(keys, out)}
 
     def chol_dist_begin(self):
         self._ck(lib.psba_chol_dist_begin(self._h))

@@ -1337,6 +1337,21 @@ static ChainShape chain_shape(const psba_ctx *h) {
   return c;
 }
 
+// whether the 32-column steps of the super-panel [J, JE) factor only its own diagonal block (see enqueue_superpanel)
+static bool steps_diag_only(int n32, int J, int JE) {
+  const bool steps_all_rows = getenv("PSBA_CHOL_STEPS_ALL_ROWS") != nullptr;
+  const bool steps_diag_forced = getenv("PSBA_CHOL_STEPS_DIAG_ONLY") != nullptr;
+  const int nbk = (JE - J) / GB;
+  return !steps_all_rows && (n32 >= 4400 || steps_diag_forced) && JE < n32 && (nbk == 4 || nbk == 8 || nbk == 12 || nbk == 16);
+}
+
+// whether the two-level chain splits each K = NB update into near and far parts on two streams (see enqueue_chain)
+static bool chain_lookahead(const ChainShape &c) {
+  bool look = c.blocked && c.NB % 64 == 0 && !getenv("PSBA_CHOL_WIDE2");
+  if (const char *e = getenv("PSBA_CHOL_LOOKAHEAD")) look = c.blocked && atoi(e) != 0 && c.NB % 64 == 0 && !getenv("PSBA_CHOL_WIDE2");
+  return look;
+}
+
 // a pause on a stream: one wave sleeps until `ticks` of the 100 MHz wall clock have passed (look-ahead chain: the far
 // update starts a few microseconds after the near one, see enqueue_superpanel)
 __global__ void k_cholg_pause(long long ticks) {
@@ -1362,11 +1377,8 @@ static void enqueue_superpanel(psba_ctx *h, hipStream_t s, const ChainShape &c, 
   // all rows / diagonal only: n = 2040 835 / 1038 us, 2400 1027 / 1282, 3600 1794 / 2088, 6000 4276 / 4506); with
   // four waves per tile row (k_cholg_trsm_block4) from ~4400: n = 3600 1760 / 1774 us, 4800 2712 / 2628, 6000
   // 3781 / 3413, 7200 5326 / 4766, 8040 6636 / 6025.  PSBA_CHOL_STEPS_DIAG_ONLY=1 forces it (tests).
-  const bool steps_all_rows = getenv("PSBA_CHOL_STEPS_ALL_ROWS") != nullptr;
-  const bool steps_diag_forced = getenv("PSBA_CHOL_STEPS_DIAG_ONLY") != nullptr;
   const int nbk = (JE - J) / GB;
-  const bool diag_only = !steps_all_rows && (n32 >= 4400 || steps_diag_forced) && JE < n32 &&
-                         (nbk == 4 || nbk == 8 || nbk == 12 || nbk == 16);
+  const bool diag_only = steps_diag_only(n32, J, JE);
   const int nTs = diag_only ? JE / 16 : nT;  // tile rows the steps see
   for (int j = J; j < JE; j += GB) {
     const int T0 = (j + GB) / 16, TE = JE / 16;
@@ -1515,8 +1527,7 @@ static void enqueue_chain(psba_ctx *h, hipStream_t s, bool skip_diag) {
   // (with the pause, the fine near update and the fence-free events it pays wherever the blocked chain runs: per
   // factorization off / on, n = 1860 777 / 731 us, 2520 1070 / 1032, 3000 1333 / 1282, 4200 2204 / 2106, 5100 2938 /
   // 2596, 6000 3949 / 3410, 7200 5515 / 4808)
-  bool look = blocked && c.NB % 64 == 0 && !getenv("PSBA_CHOL_WIDE2");
-  if (const char *e = getenv("PSBA_CHOL_LOOKAHEAD")) look = blocked && atoi(e) != 0 && c.NB % 64 == 0 && !getenv("PSBA_CHOL_WIDE2");
+  bool look = chain_lookahead(c);
   if (look) {
     if (!h->chol_side) {
       // the side stream at the LOWEST priority: the next super-panel's small dependent launches on the main stream
@@ -1622,6 +1633,22 @@ int chol_dist_shape(psba_ctx *h, int *NB, int *blocked) {
   const ChainShape c = chain_shape(h);
   *NB = c.NB;
   *blocked = c.blocked && c.NB % 64 == 0;
+  return PSBA_OK;
+}
+
+// the route the chain takes for this handle's matrix, from the same decisions enqueue_chain makes (launches nothing):
+// out = {n32, fused, fused2, blocked, NB, diagonal-only steps in the first super-panel, look-ahead, single workgroup}
+int chol_shape(psba_ctx *h, int *out) {
+  const ChainShape c = chain_shape(h);
+  const int n32 = h->n32;
+  out[0] = n32;
+  out[1] = c.fused;
+  out[2] = c.fused2;
+  out[3] = c.blocked;
+  out[4] = c.NB;
+  out[5] = c.blocked && steps_diag_only(n32, 0, c.NB < n32 ? c.NB : n32);
+  out[6] = chain_lookahead(c);
+  out[7] = getenv("PSBA_CHOL_SINGLE") != nullptr;
   return PSBA_OK;
 }
 

@@ -1127,6 +1127,12 @@ int psba_chol_dist_shape(psba_handle h, int *n32, int *NB, int *sharded) {
   if (sharded) *sharded = bl;
   return PSBA_OK;
 }
+int psba_chol_shape(psba_handle h, int *out8) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  if (!out8) return fail(h, PSBA_E_INVALID, "psba_chol_shape: null pointer");
+  return chol_shape(h, out8);
+}
 int psba_chol_dist_exchange_plan(int n32, int NB, int nranks, int JE, long long *out4, int cap) {
   if (!out4 || cap <= 0) return PSBA_E_INVALID;
   return psba::chol_dist_exchange_plan(n32, NB, nranks, JE, reinterpret_cast<long long(*)[4]>(out4), cap);

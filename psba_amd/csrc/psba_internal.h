@@ -380,6 +380,7 @@ int launch_bsr_gershgorin(psba_ctx *h, double *lambda, double *info3);
 // kernels_chol_graph.hip
 int launch_chol_graph(psba_ctx *h);
 int chol_dist_shape(psba_ctx *h, int *NB, int *blocked);
+int chol_shape(psba_ctx *h, int *out8);
 int chol_dist_exchange_plan(int n32, int NB, int nranks, int JE, long long (*out)[4], int cap);
 int chol_dist_begin(psba_ctx *h);
 int chol_dist_superpanel(psba_ctx *h, int J);
