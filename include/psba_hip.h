@@ -159,6 +159,43 @@ int psba_robust_loss(psba_handle h, int *kind, double *scale);
  * (PSBA_PARAMS_CUR) or proposed (PSBA_PARAMS_NEW) parameters, under any loss: observations with s_a well above c2
  * are the ones the loss down-weights.  Fixed-intrinsics camera block only. */
 int psba_obs_sq_residuals(psba_handle h, int which, double *s);
+
+/* ---- fixed parameter blocks -------------------------------------------------------------
+ * Model (the same in psba_amd/csrc/camera_model.h and DESIGN.md): cameras and points marked fixed are held constant.
+ * The problem solved is the reduced one: the columns of J that belong to fixed blocks are deleted and the fixed
+ * values enter the residual as constants.  It is stored embedded in the full-size system, so no plan, index table or
+ * buffer size changes:
+ *   linearization  A_ij = 0 for a fixed camera j, B_ij = 0 for a fixed point i (after the whitening and the loss
+ *                  weight), hence W_ij = 0 if either is fixed, g_a,j = 0 and g_b,i = 0 exactly.  The stored diagonal
+ *                  block of a fixed camera (U_j) or point (V_i) is the placeholder coeff I (coeff of psba_linearize),
+ *                  so V_i + mu I and S stay positive definite at mu = 0.  Under a rank layout only rank 0 (the rank
+ *                  that owns the camera terms) writes the camera placeholder into its partial U, the others zero:
+ *                  the summed diagonal block of a fixed camera is coeff I as on a single handle.
+ *   psba_max_diag / psba_begin / psba_maxElmOfUV  the maximum over the free blocks only.
+ *   S and e_a      block row and column j of a fixed camera are zero off the diagonal, the diagonal block is the
+ *                  placeholder + mu I, e_a,j = 0.
+ *   step           dp is exactly 0 on every fixed entry; the proposed and the accepted parameters of fixed blocks
+ *                  are bit-identical to the current ones.  psba_set_step ignores (and zeroes) the fixed entries of dp.
+ *   J x            psba_compute_Jmultiply / psba_jmul_dots use the masked J: fixed entries of x are not read.
+ *   cost           psba_residual, the try scalars and psba_obs_sq_residuals count every observation as before.
+ *   mirror verbs   return what the normal equations see: masked A, B, W, g, the placeholder blocks in U, V, S.
+ *   psba_set_params may still move a fixed block: an explicit act of the caller.
+ * fixed_cams[nCams], fixed_pts[n3Dpts]: non-zero = the parameter block is held constant.  NULL = none of that kind;
+ * two NULLs clear the mask, and a mask without a non-zero entry is no mask: the handle runs exactly the kernels of
+ * one that never set any.  Under a rank layout fixed_pts covers this rank's points (like cov), fixed_cams is the
+ * same on every rank.
+ * Rules as for the lens model above: PSBA_E_STATE before psba_upload_problem, under PSBA_CAMERA_FREE_K and while a
+ * try is in flight; PSBA_E_INVALID if the mask would leave no free parameter at all on a single-rank handle.  A
+ * refused call changes nothing.  Setting the mask discards a linearization queued ahead; an upload resets it to none.
+ * Structure-only: when every camera is fixed there is no coupled system (dpa = 0, dpb_i = (V_i + mu I)^-1 g_b,i), and
+ * psba_schur_assemble / psba_schur_reduce / psba_schur_solve queue no S assembly, no S-reduce and no factorization;
+ * psba_get_reduce_buffer / psba_set_reduce_buffer / psba_get_sparse_S / psba_set_sparse_S then return PSBA_E_STATE
+ * (nothing was assembled).  PSBA_FIXED_NO_SHORTCUT=1 in the environment keeps the general route; the mirror verbs
+ * (psba_compute_S ...) always take it; psba_cholmod_lambda returns PSBA_E_STATE between the psba_schur_assemble and the
+ * psba_schur_solve of a structure-only try.  The reference has no fixed blocks: PARITY UNPINNED -- checked against a
+ * numpy twin, the oracle's own sums on masked blocks, finite differences and a dense solve of the reduced system. */
+int psba_set_fixed(psba_handle h, const unsigned char *fixed_cams, const unsigned char *fixed_pts);
+int psba_fixed_counts(psba_handle h, int *n_fixed_cams, int *n_fixed_pts);
 /* which S-assembly route the uploaded problem takes: 0 = LDS-resident partitions of the block
  * triangle with the static schedule (fewer than 2048 cameras, up to 8 GB of partial-sum slabs on
  * this rank), 1 = the owner route for larger problems (one thread per block segment,

@@ -153,6 +153,8 @@ SIGNATURES = [
     ("psba_set_robust_loss", C.c_int, [_h, C.c_int, C.c_double]),
     ("psba_robust_loss", C.c_int, [_h, _ip, _dp]),
     ("psba_obs_sq_residuals", C.c_int, [_h, C.c_int, _dp]),
+    ("psba_set_fixed", C.c_int, [_h, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    ("psba_fixed_counts", C.c_int, [_h, _ip, _ip]),
     ("psba_read_problem_ex", C.c_int, [C.c_char_p, C.c_char_p, _dp, C.POINTER(CProblemEx)]),
     ("psba_free_problem_ex", None, [C.POINTER(CProblemEx)]),
     ("psba_convert_bal_kd", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
@@ -205,7 +207,8 @@ def _c(a, dt=np.float64):
 
 
 class Problem(dict):
-    """K[nC,5] initrot[nC,4] cams[nC,6] pts[nP,3] impts[nO,2] iidx[nO] jidx[nO] nC nP nO."""
+    """K[nC,5] initrot[nC,4] cams[nC,6] pts[nP,3] impts[nO,2] iidx[nO] jidx[nO] nC nP nO.
+    Optional: kc[nC,5], cov[nO,2,2] (read_problem_ex); fixed_cams[nC], fixed_pts[nP] (masks for Psba.set_fixed)."""
 
 
 def sparse_pattern(prob):
@@ -391,7 +394,8 @@ def ring_plan(n_cams, n_pts, iidx, jidx):
 def shard_problem(prob, nranks, rank):
     """The sub-problem rank `rank` owns: a contiguous point range and its observations;
     cameras are replicated.  A problem with kc / cov keys (read_problem_ex) keeps kc and the cov rows of
-    the observations it keeps."""
+    the observations it keeps; one with fixed_cams / fixed_pts keys (Psba.set_fixed) keeps fixed_cams and the
+    fixed_pts entries of its points."""
     bounds = partition_points(prob["nP"], prob["iidx"], nranks)
     p0, p1 = int(bounds[rank]), int(bounds[rank + 1])
     iidx = np.asarray(prob["iidx"])
@@ -404,6 +408,10 @@ def shard_problem(prob, nranks, rank):
         out["kc"] = prob["kc"]
     if "cov" in prob:
         out["cov"] = None if prob["cov"] is None else np.asarray(prob["cov"])[sel]
+    if "fixed_cams" in prob:
+        out["fixed_cams"] = prob["fixed_cams"]
+    if "fixed_pts" in prob:
+        out["fixed_pts"] = None if prob["fixed_pts"] is None else np.asarray(prob["fixed_pts"])[p0:p1]
     return out
 
 
@@ -469,6 +477,27 @@ class Psba:
         k, c = C.c_int(), C.c_double()
         self._ck(lib.psba_robust_loss(self._h, C.byref(k), C.byref(c)))
         return k.value, c.value
+
+    def set_fixed(self, cams=None, pts=None):
+        """psba_set_fixed: cams [nC], pts [nP] boolean or integer arrays, non-zero = the block is held constant;
+        None = none of that kind, two Nones clear the mask."""
+        def mask(a, n, what):
+            if a is None:
+                return None
+            m = (np.asarray(a).reshape(-1) != 0).astype(np.uint8)
+            if m.size != n:
+                raise PsbaError(-1, f"set_fixed: {m.size} flags for {n} {what}")
+            return np.ascontiguousarray(m)
+        c, p = mask(cams, self.nC, "cameras"), mask(pts, self.nP, "points")
+        ub = C.POINTER(C.c_ubyte)
+        self._ck(lib.psba_set_fixed(self._h, None if c is None else c.ctypes.data_as(ub),
+                                    None if p is None else p.ctypes.data_as(ub)))
+
+    def fixed_counts(self):
+        """psba_fixed_counts -> (fixed cameras, fixed points)"""
+        c, p = C.c_int(), C.c_int()
+        self._ck(lib.psba_fixed_counts(self._h, C.byref(c), C.byref(p)))
+        return c.value, p.value
 
     def obs_sq_residuals(self, which=PARAMS_CUR):
         """psba_obs_sq_residuals: s_a = ||L_a e_a||^2 per observation [nO] at PARAMS_CUR / PARAMS_NEW."""

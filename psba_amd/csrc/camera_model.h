@@ -168,7 +168,9 @@ PSBA_HD void linearize_obs_freek(const double *p, const double *q0, const double
 // triangular, stored (l00, l01, l11, 0).  The kernels whiten right after the projection (e <- L e, A <- L A,
 // B <- L B), so the cost is sum e^T Sigma^-1 e and everything downstream is the same normal equations.
 // The lens model of a kernel instantiation: bit 0 distortion, bit 1 covariances, bit 2 robust loss (below).
-enum { LENS_PLAIN = 0, LENS_DIST = 1, LENS_COV = 2, LENS_BOTH = 3, LENS_ROBUST = 4, LENS_MODELS = 8 };
+// Bit 3 (LENS_FIXED, below): some parameter blocks are held constant; set only at the launch sites of the kernels
+// that form Jacobian blocks or finish a step (lens_dispatch_fixed), never in psba_ctx::lens.
+enum { LENS_PLAIN = 0, LENS_DIST = 1, LENS_COV = 2, LENS_BOTH = 3, LENS_ROBUST = 4, LENS_MODELS = 8, LENS_FIXED = 8 };
 constexpr int LENS_WSTRIDE = 4;  // doubles per observation of the whitening factors (l00, l01, l11, pad)
 
 // (xd, yd) and, when J is given, d(xd, yd) / d(x, y) row-major
@@ -351,6 +353,54 @@ PSBA_HD void robust_scale(const RobustLoss &rl, double *e, double *A, double *B)
   for (int k = 0; k < 6; k++) B[k] *= w;
 }
 
+// ---- fixed parameter blocks (the same model in include/psba_hip.h and DESIGN 7c) ----
+// psba_set_fixed marks cameras and points that are held constant.  The problem solved is the reduced one: the
+// columns of J that belong to fixed blocks are deleted and the fixed values enter the residual as constants.  It is
+// stored embedded in the full-size system: A_ij = 0 for a fixed camera j and B_ij = 0 for a fixed point i (applied
+// after the whitening and the loss weight: zeroing commutes with both), hence W_ij = 0 if either is fixed,
+// g_a,j = 0 and g_b,i = 0 exactly; the stored diagonal block of a fixed camera (U_j) or point (V_i) is the
+// placeholder coeff I, which keeps V_i + mu I and S positive definite at mu = 0; dp is exactly 0 on fixed entries.
+// The residual e and the cost are untouched: every observation counts.
+// The mask is two byte arrays on the device (non-zero = fixed), read only by the LENS_FIXED instantiations: the
+// kernels' last argument, behind the robust loss, so that every other argument keeps its offset.
+struct FixedMask {
+  const unsigned char *cams, *pts;  // [nC], [nP]; either may be null (none of that kind)
+};
+enum { FIX_CAM = 1, FIX_PT = 2 };
+// which of observation (i, j)'s two blocks are fixed (0 without the bit: no load)
+template <int LM>
+PSBA_HD int fix_load(const FixedMask &fm, size_t i, size_t j) {
+  if constexpr ((LM & LENS_FIXED) != 0)
+    return ((fm.cams && fm.cams[j]) ? FIX_CAM : 0) | ((fm.pts && fm.pts[i]) ? FIX_PT : 0);
+  else
+    return 0;
+}
+template <int LM>
+PSBA_HD bool fix_cam(const FixedMask &fm, size_t j) {
+  if constexpr ((LM & LENS_FIXED) != 0)
+    return fm.cams && fm.cams[j];
+  else
+    return false;
+}
+template <int LM>
+PSBA_HD bool fix_pt(const FixedMask &fm, size_t i) {
+  if constexpr ((LM & LENS_FIXED) != 0)
+    return fm.pts && fm.pts[i];
+  else
+    return false;
+}
+// A <- 0 under FIX_CAM, B <- 0 under FIX_PT (selects: no divergence)
+template <int LM>
+PSBA_HD void fix_mask(int fx, double *A, double *B) {
+  if constexpr ((LM & LENS_FIXED) != 0) {
+    const bool fc = (fx & FIX_CAM) != 0, fp = (fx & FIX_PT) != 0;
+#pragma unroll
+    for (int k = 0; k < 12; k++) A[k] = fc ? 0.0 : A[k];
+#pragma unroll
+    for (int k = 0; k < 6; k++) B[k] = fp ? 0.0 : B[k];
+  }
+}
+
 // loads of camera j's kc and observation a's whitening factors (nothing under a model without them)
 template <int LM>
 PSBA_HD void lens_load_kc(const double *src, size_t j, double *kc) {
@@ -419,6 +469,23 @@ void lens_dispatch(int lm, F &&f) {
     case 6: f(std::integral_constant<int, 6>()); break;
     case 7: f(std::integral_constant<int, 7>()); break;
     default: f(std::integral_constant<int, 0>()); break;
+  }
+}
+
+// the same with the LENS_FIXED bit on top (lm = psba_ctx::lens, fixed = a mask is set): the launch sites of K1, K3,
+// k_cam_sums and k_jmul.  A handle without a mask runs the instantiations lens_dispatch picks.
+template <class F>
+void lens_dispatch_fixed(int lm, bool fixed, F &&f) {
+  if (!fixed) return lens_dispatch(lm, f);
+  switch (lm) {
+    case 1: f(std::integral_constant<int, LENS_FIXED | 1>()); break;
+    case 2: f(std::integral_constant<int, LENS_FIXED | 2>()); break;
+    case 3: f(std::integral_constant<int, LENS_FIXED | 3>()); break;
+    case 4: f(std::integral_constant<int, LENS_FIXED | 4>()); break;
+    case 5: f(std::integral_constant<int, LENS_FIXED | 5>()); break;
+    case 6: f(std::integral_constant<int, LENS_FIXED | 6>()); break;
+    case 7: f(std::integral_constant<int, LENS_FIXED | 7>()); break;
+    default: f(std::integral_constant<int, LENS_FIXED | 0>()); break;
   }
 }
 

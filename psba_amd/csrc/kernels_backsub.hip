@@ -39,7 +39,7 @@ struct BackArgs {
 // 50 of the kernel's 66 MB at venice size); the camera constants and parameters loaded for it are
 // the ones the residual pass needs anyway.  (PSBA_BACK_READ_W=1: the W-reading form.)
 template <bool DUMP, bool RECOMP, int LM>
-__global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p, RobustLoss rl) {
+__global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p, RobustLoss rl, FixedMask fm) {
   __shared__ double sT[TILE_OBS][3];   // W_a^T dpa_j per observation
   __shared__ double sNP[TILE_OBS][3];  // proposed point per point of the tile
   __shared__ double sRed[4][4];
@@ -56,7 +56,11 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p, RobustLoss rl)
       p.scal[SC_STATUS_SPD] = (p.status[1] == p.status[3]) ? 1.0 : 0.0;
     }
     for (int t = tid; t < p.nA; t += TILE_OBS) {
-      const double d = p.dp[t], c = p.cams[t] + d;
+      // a fixed camera: dpa_j is zero whatever the solver returned, and the proposal is the current block bit for bit
+      // (every other reader of dpa in this kernel masks it the same way, so the store below races with nothing)
+      const bool fc = fix_cam<LM>(fm, t / 6);
+      const double d = fc ? 0.0 : p.dp[t], c = fc ? p.cams[t] : p.cams[t] + d;
+      if (fc) p.dp[t] = 0.0;
       p.newcams[t] = c;
       s_den += d * p.ga[t];
       if (p.cam_terms) {
@@ -92,6 +96,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p, RobustLoss rl)
     // the real measurement (K1's inputs, hence K1's w bit for bit); without the bit the measurement is 0 (e unused)
     constexpr bool MEAS = RECOMP && (LM & LENS_ROBUST) != 0;
     double2 m = make_double2(0.0, 0.0);
+    const int fx = a < o1 ? fix_load<LM>(fm, i, j) : 0;
     if (RECOMP && a < o1) {
 #pragma unroll
       for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * j + k];
@@ -101,7 +106,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p, RobustLoss rl)
 #pragma unroll
       for (int k = 0; k < 6; k++) {
         cam[k] = p.cams[6 * j + k];
-        da[k] = p.dp[6 * j + k];
+        da[k] = (fx & FIX_CAM) ? 0.0 : p.dp[6 * j + k];
       }
     }
     if (a < o1 && p.mode != 2) {
@@ -111,6 +116,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p, RobustLoss rl)
 #pragma unroll
         for (int k = 0; k < 3; k++) M[k] = p.pts[3 * (size_t)i + k];
         lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
+        fix_mask<LM>(fx, A, B);
         double s0 = 0.0, s1 = 0.0;
 #pragma unroll
         for (int k = 0; k < 6; k++) {
@@ -125,7 +131,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p, RobustLoss rl)
         const double *dw = p.dp + 6 * j;
 #pragma unroll
         for (int k = 0; k < 6; k++) {
-          const double dk = dw[k];
+          const double dk = (fx & FIX_CAM) ? 0.0 : dw[k];
           t0 += w[3 * k] * dk;
           t1 += w[3 * k + 1] * dk;
           t2 += w[3 * k + 2] * dk;
@@ -162,15 +168,18 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p, RobustLoss rl)
       v[3] += p.mu;
       v[5] += p.mu;
       sym3_inverse(v, vi);
-      const double d0 = vi[0] * e0 + vi[1] * e1 + vi[2] * e2;
-      const double d1 = vi[1] * e0 + vi[3] * e1 + vi[4] * e2;
-      const double d2 = vi[2] * e0 + vi[4] * e1 + vi[5] * e2;
+      // a fixed point: dpb_i = 0 and the proposal is the current point bit for bit (its W_ij^T dpa_j terms and g_b,i are
+      // zero under the mask already; the select does not rely on it)
+      const bool fp = fix_pt<LM>(fm, ip);
+      const double d0 = fp ? 0.0 : vi[0] * e0 + vi[1] * e1 + vi[2] * e2;
+      const double d1 = fp ? 0.0 : vi[1] * e0 + vi[3] * e1 + vi[4] * e2;
+      const double d2 = fp ? 0.0 : vi[2] * e0 + vi[4] * e1 + vi[5] * e2;
       double *dpb = p.dp + p.nA + 3 * (size_t)ip;
       dpb[0] = d0;
       dpb[1] = d1;
       dpb[2] = d2;
       const double *M = p.pts + 3 * (size_t)ip;
-      const double n0 = M[0] + d0, n1 = M[1] + d1, n2 = M[2] + d2;
+      const double n0 = fp ? M[0] : M[0] + d0, n1 = fp ? M[1] : M[1] + d1, n2 = fp ? M[2] : M[2] + d2;
       double *np = p.newpts + 3 * (size_t)ip;
       np[0] = n0;
       np[1] = n1;
@@ -189,12 +198,12 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p, RobustLoss rl)
 #pragma unroll
         for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * j + k];
 #pragma unroll
-        for (int k = 0; k < 6; k++) cam[k] = p.cams[6 * j + k] + p.dp[6 * j + k];
+        for (int k = 0; k < 6; k++) cam[k] = (fx & FIX_CAM) ? p.cams[6 * j + k] : p.cams[6 * j + k] + p.dp[6 * j + k];
         lens_load_kc<LM>(p.kc, j, kc);
         lens_load_w<LM>(p.wl, a, wl);
       } else {
 #pragma unroll
-        for (int k = 0; k < 6; k++) cam[k] += da[k];
+        for (int k = 0; k < 6; k++) cam[k] = (fx & FIX_CAM) ? cam[k] : cam[k] + da[k];
       }
       if (!MEAS) m = reinterpret_cast<const double2 *>(p.impts)[a];
       lens_residual<LM>(cc, cam, sNP[i - p0], kc, wl, m.x, m.y, e0, e1);
@@ -229,7 +238,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub(BackArgs p, RobustLoss rl)
 // workgroup walks its observations twice, TILE_OBS at a time -- sum of W_ij^T dpa_j (from the
 // stored W), then dpb_i and the proposed point by one thread, then the residuals at the proposal.
 template <bool DUMP, int LM>
-__global__ __launch_bounds__(TILE_OBS) void k_backsub_long(BackArgs p, const int *long_pts, RobustLoss rl) {
+__global__ __launch_bounds__(TILE_OBS) void k_backsub_long(BackArgs p, const int *long_pts, RobustLoss rl, FixedMask fm) {
   __shared__ double sRed[TILE_OBS / 64][4];
   __shared__ double sNP[3];
   const int tid = threadIdx.x, i = long_pts[blockIdx.x];
@@ -238,9 +247,10 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub_long(BackArgs p, const int
   for (int a = o0 + tid; a < o1; a += TILE_OBS) {
     const double *w = p.W + 18 * (size_t)a;
     const double *dw = p.dp + 6 * (size_t)p.jidx[a];
+    const bool fc = fix_cam<LM>(fm, p.jidx[a]);
 #pragma unroll
     for (int k = 0; k < 6; k++) {
-      const double dk = dw[k];
+      const double dk = fc ? 0.0 : dw[k];
       t3[0] += w[3 * k] * dk;
       t3[1] += w[3 * k + 1] * dk;
       t3[2] += w[3 * k + 2] * dk;
@@ -272,11 +282,12 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub_long(BackArgs p, const int
     v[3] += p.mu;
     v[5] += p.mu;
     sym3_inverse(v, vi);
-    const double d[3] = {vi[0] * e[0] + vi[1] * e[1] + vi[2] * e[2], vi[1] * e[0] + vi[3] * e[1] + vi[4] * e[2],
-                         vi[2] * e[0] + vi[4] * e[1] + vi[5] * e[2]};
+    const bool fp = fix_pt<LM>(fm, i);
+    const double d[3] = {fp ? 0.0 : vi[0] * e[0] + vi[1] * e[1] + vi[2] * e[2], fp ? 0.0 : vi[1] * e[0] + vi[3] * e[1] + vi[4] * e[2],
+                         fp ? 0.0 : vi[2] * e[0] + vi[4] * e[1] + vi[5] * e[2]};
 #pragma unroll
     for (int q = 0; q < 3; q++) {
-      const double n = p.pts[3 * (size_t)i + q] + d[q];
+      const double n = fp ? p.pts[3 * (size_t)i + q] : p.pts[3 * (size_t)i + q] + d[q];
       p.dp[p.nA + 3 * (size_t)i + q] = d[q];
       p.newpts[3 * (size_t)i + q] = n;
       sNP[q] = n;
@@ -292,7 +303,8 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub_long(BackArgs p, const int
 #pragma unroll
     for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * (size_t)j + k];
 #pragma unroll
-    for (int k = 0; k < 6; k++) cam[k] = p.cams[6 * (size_t)j + k] + p.dp[6 * (size_t)j + k];
+    for (int k = 0; k < 6; k++)
+      cam[k] = fix_cam<LM>(fm, j) ? p.cams[6 * (size_t)j + k] : p.cams[6 * (size_t)j + k] + p.dp[6 * (size_t)j + k];
     lens_load_kc<LM>(p.kc, j, kc);
     lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
@@ -330,22 +342,55 @@ int launch_publish_scal(psba_ctx *h, hipStream_t s) {
   return PSBA_OK;
 }
 
+// Structure-only try (every camera fixed, psba_set_fixed): there is no coupled system, dpa = 0 and K3's point part is
+// the whole solve, dpb_i = (V_i + mu I)^-1 g_b,i.  This kernel stands in for K2, the S-reduce and the factorization:
+// it zeroes dpa and the try's partial sums, stamps the try (status[3]) and flags a singular V_i + mu I (status[0]) as
+// K2 would have.
+__global__ __launch_bounds__(256) void k_struct_only_begin(const double *PV, double mu, int nA, int nP, double *dp, double *scal,
+                                                           int *status, int try_id) {
+  const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gsize = gridDim.x * blockDim.x;
+  if (blockIdx.x == 0 && threadIdx.x < 4 * SC_NPART) scal[SC_PART + threadIdx.x] = 0.0;
+  if (blockIdx.x == 0 && threadIdx.x == 64) status[3] = try_id;
+  for (int t = gtid; t < nA; t += gsize) dp[t] = 0.0;
+  for (int i = gtid; i < nP; i += gsize) {
+    double v[6], vi[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) v[k] = PV[9 * (size_t)i + k];
+    v[0] += mu;
+    v[3] += mu;
+    v[5] += mu;
+    if (sym3_inverse(v, vi)) status[0] = try_id;
+  }
+}
+
+int launch_struct_only_try(psba_ctx *h, double mu) {
+  h->try_id++;
+  h->diag_done = false;
+  h->packed_pending = false;
+  int grid = (h->d.nP + 255) / 256;
+  if (grid > 1024) grid = 1024;
+  hipLaunchKernelGGL(k_struct_only_begin, dim3(grid), dim3(256), 0, h->stream, h->PV, mu, h->d.nA, h->d.nP, h->dp, h->scal,
+                     h->status, h->try_id);
+  PSBA_HIP(h, hipGetLastError());
+  return PSBA_OK;
+}
+
 // K3 for lens model LM (psba_ctx::lens)
 template <int LM>
-static void enqueue_backsub(psba_ctx *h, const BackArgs &a, const RobustLoss &rl, int grid, bool dump, bool read_w) {
+static void enqueue_backsub(psba_ctx *h, const BackArgs &a, const RobustLoss &rl, const FixedMask &fm, int grid, bool dump, bool read_w) {
   if (dump && read_w)
-    hipLaunchKernelGGL((k_backsub<true, false, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
+    hipLaunchKernelGGL((k_backsub<true, false, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl, fm);
   else if (dump)
-    hipLaunchKernelGGL((k_backsub<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
+    hipLaunchKernelGGL((k_backsub<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl, fm);
   else if (read_w)
-    hipLaunchKernelGGL((k_backsub<false, false, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
+    hipLaunchKernelGGL((k_backsub<false, false, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl, fm);
   else
-    hipLaunchKernelGGL((k_backsub<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
+    hipLaunchKernelGGL((k_backsub<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl, fm);
   if (h->nLong) {  // points seen by more cameras than a tile holds
     if (dump)
-      hipLaunchKernelGGL((k_backsub_long<true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, rl);
+      hipLaunchKernelGGL((k_backsub_long<true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, rl, fm);
     else
-      hipLaunchKernelGGL((k_backsub_long<false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, rl);
+      hipLaunchKernelGGL((k_backsub_long<false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, rl, fm);
   }
 }
 
@@ -393,7 +438,8 @@ int launch_backsub(psba_ctx *h, double mu, bool dump) {
   {
     ProfScope ps(h, PSBA_K_BACKSUB);
     const bool read_w = getenv("PSBA_BACK_READ_W") != nullptr;
-    lens_dispatch(h->lens, [&](auto m) { enqueue_backsub<decltype(m)::value>(h, a, rl, grid, dump, read_w); });
+    const FixedMask fm = {h->fix_cams, h->fix_pts};
+    lens_dispatch_fixed(h->lens, h->has_fixed, [&](auto m) { enqueue_backsub<decltype(m)::value>(h, a, rl, fm, grid, dump, read_w); });
   }
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;

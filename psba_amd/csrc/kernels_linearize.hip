@@ -42,7 +42,7 @@ struct LinArgs {
 // GACC: many cameras -- the 27 sums per camera do not fit the LDS.  They are then formed by a
 // camera-major pass of their own (k_cam_sums) and this kernel leaves them out.
 template <bool DUMP, bool GACC, int LM>
-__global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p, RobustLoss rl) {
+__global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p, RobustLoss rl, FixedMask fm) {
   __shared__ double sBE[TILE_OBS][9];  // B(6) | e(2) per observation of the tile (+1: odd row stride)
   __shared__ double sW[(TILE_OBS / 2) * 19];  // W blocks of half a tile (staged in two halves: LDS for three workgroups per CU)
   extern __shared__ double sAcc[];     // [nC][27]
@@ -94,6 +94,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p, RobustLoss rl
       lens_load_w<LM>(p.wl, a, wl);
       const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
       lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
+      fix_mask<LM>(fix_load<LM>(fm, i, j), A, B);
       if (DUMP) {
         p.dbg_ex[2 * a] = e[0];
         p.dbg_ex[2 * a + 1] = e[1];
@@ -207,7 +208,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p, RobustLoss rl
 //  * the NEXT tile's indices and the eighteen parameter doubles they lead to are fetched as soon as this tile's
 //    Jacobian is done, so their latency runs under the camera atomics, the scan and the W flush.
 template <bool DUMP, bool GACC, int LM>
-__global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss rl) {
+__global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss rl, FixedMask fm) {
   __shared__ double sW[TILE_OBS * 19];          // W blocks of the tile (row stride 19 doubles: odd, conflict-free stores)
   __shared__ double sCarV[TILE_OBS / 64][9];    // a wave's last lane: its scan values (the tail of its last segment)
   __shared__ int sCarP[TILE_OBS / 64][3];       // point of the wave's first lane, of its last lane, whole wave one point?
@@ -228,10 +229,12 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss r
   int i = 0, j = 0;
   double cc[9], cam[6], M[3], kc[5], wl[3];
   double2 m = make_double2(0.0, 0.0);
+  int fx = 0;  // which of the observation's blocks are fixed (LENS_FIXED instantiations; fetched with the operands)
   // prologue: the first tile's operands
   if (dsc.z + tid < dsc.w) {
     i = p.iidx[dsc.z + tid];
     j = p.jidx[dsc.z + tid];
+    fx = fix_load<LM>(fm, i, j);
 #pragma unroll
     for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * j + k];
 #pragma unroll
@@ -256,6 +259,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss r
     if (act) {
       double e[2], A[12], B[6];
       lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
+      fix_mask<LM>(fx, A, B);
       if (DUMP) {
         p.dbg_ex[2 * (size_t)a] = e[0];
         p.dbg_ex[2 * (size_t)a + 1] = e[1];
@@ -295,6 +299,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss r
     if (dn.z + tid < dn.w) {
       i = p.iidx[dn.z + tid];
       j = p.jidx[dn.z + tid];
+      fx = fix_load<LM>(fm, i, j);
 #pragma unroll
       for (int k = 0; k < 9; k++) cc[k] = p.camconst[9 * j + k];
 #pragma unroll
@@ -366,7 +371,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss r
 // fp64 atomics into one extra slab of the per-workgroup camera sums (zeroed before the launch) that
 // k_cam_reduce adds like any other -- with GACC the camera-major pass covers these observations anyway.
 template <bool DUMP, bool GACC, int LM>
-__global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const int *long_pts, double *cam_slab, RobustLoss rl) {
+__global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const int *long_pts, double *cam_slab, RobustLoss rl, FixedMask fm) {
   __shared__ double sRed[TILE_OBS / 64][9];
   const int tid = threadIdx.x, i = long_pts[blockIdx.x];
   const int o0 = p.ptr[i], o1 = p.ptr[i + 1];
@@ -386,6 +391,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const in
     lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
     lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
+    fix_mask<LM>(fix_load<LM>(fm, i, j), A, B);
     if (DUMP) {
       p.dbg_ex[2 * (size_t)a] = e[0];
       p.dbg_ex[2 * (size_t)a + 1] = e[1];
@@ -438,7 +444,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const in
 // fp64 atomic adds per segment.  (Through per-observation atomics from the point-major kernel the
 // same sums took 25 ms at 20 M observations; the reference scans all points per output scalar.)
 template <int LM>
-__global__ __launch_bounds__(256) void k_cam_sums(LinArgs p, const int *cam_obs, const int4 *units, int nUnits, RobustLoss rl) {
+__global__ __launch_bounds__(256) void k_cam_sums(LinArgs p, const int *cam_obs, const int4 *units, int nUnits, RobustLoss rl, FixedMask fm) {
   // one wave per unit (a segment of at most 256 observations of one camera): the lanes stride
   // through the segment, the 27 sums are folded across the wave, lane 0 adds them to the camera's
   // totals.  (One thread per unit walked its 256 gathers one after the other: 380 us for 218 k
@@ -465,6 +471,7 @@ __global__ __launch_bounds__(256) void k_cam_sums(LinArgs p, const int *cam_obs,
     lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
     lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
+    fix_mask<LM>(fix_load<LM>(fm, i, j), A, B);
     int k = 0;
 #pragma unroll
     for (int r = 0; r < 6; r++)
@@ -540,6 +547,29 @@ __global__ __launch_bounds__(1024) void k_cam_reduce(const double *campart, int 
   }
 }
 
+// Fixed blocks (camera_model.h FixedMask): behind the camera and point sums of a masked linearization, which are
+// exact zeros for a fixed block (its A or B was zeroed per observation).  Writes the placeholder coeff I into U_j of
+// a fixed camera and V_i of a fixed point and zero into g_a,j / g_b,i, whatever the sums hold.  One thread per
+// camera, then one per point; runs only on handles with a mask.  cam_diag: coeff on the rank that owns the camera terms
+// (rank 0) and 0 on the others, whose partial U_j is added to it: the summed block is coeff I as on a single handle.
+__global__ __launch_bounds__(256) void k_fixed_diag(FixedMask fm, int nC, int nP, double coeff, double cam_diag, double *U,
+                                                    double *ga, double *PV) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < nC) {
+    if (fm.cams && fm.cams[t]) {
+      for (int e = 0; e < 36; e++) U[36 * (size_t)t + e] = (e % 7 == 0) ? cam_diag : 0.0;
+      for (int e = 0; e < 6; e++) ga[6 * (size_t)t + e] = 0.0;
+    }
+  } else if (t - nC < nP) {
+    const int i = t - nC;
+    if (fm.pts && fm.pts[i]) {
+      double *pv = PV + 9 * (size_t)i;
+      pv[0] = coeff; pv[1] = 0.0; pv[2] = 0.0; pv[3] = coeff; pv[4] = 0.0; pv[5] = coeff;
+      pv[6] = 0.0; pv[7] = 0.0; pv[8] = 0.0;
+    }
+  }
+}
+
 // ---- residual: kern_compute_exQT + the host compute_L2_sq (PSBA/misc.cpp:151-157) -------
 template <int LM>
 __global__ __launch_bounds__(256) void k_residual(const double *camconst, const double *cams,
@@ -600,6 +630,29 @@ __global__ __launch_bounds__(256) void k_max_diag(const double *U, const double 
   }
 }
 
+// the same maximum over the free blocks only: the placeholder of a fixed block must not reach mu_0
+__global__ __launch_bounds__(256) void k_max_diag_fixed(const double *U, const double *PV, int nC, int nP, double *out,
+                                                        FixedMask fm) {
+  __shared__ double sRed[4];
+  double m = 0.0;
+  const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gsize = gridDim.x * blockDim.x;
+  for (int t = gtid; t < 6 * nC; t += gsize)
+    if (!(fm.cams && fm.cams[t / 6])) m = fmax(m, U[36 * (t / 6) + 7 * (t % 6)]);
+  for (int i = gtid; i < nP; i += gsize) {
+    if (fm.pts && fm.pts[i]) continue;
+    const double *v = PV + 9 * (size_t)i;
+    m = fmax(m, fmax(v[0], fmax(v[3], v[5])));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off, 64));
+  if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = fmax(fmax(sRed[0], sRed[1]), fmax(sRed[2], sRed[3]));
+    atomicMax(reinterpret_cast<unsigned long long *>(out), (unsigned long long)__double_as_longlong(m));
+  }
+}
+
 template <int LM>
 static int set_lin_attrs(psba_ctx *h) {
   const auto attr = hipFuncAttributeMaxDynamicSharedMemorySize;
@@ -612,44 +665,44 @@ static int set_lin_attrs(psba_ctx *h) {
 
 // the kernels of one linearization for lens model LM (psba_ctx::lens)
 template <int LM>
-static void enqueue_linearize(psba_ctx *h, const LinArgs &a, const RobustLoss &rl, bool dump, bool v1, size_t lds, double *Uo, double *gao) {
+static void enqueue_linearize(psba_ctx *h, const LinArgs &a, const RobustLoss &rl, const FixedMask &fm, bool dump, bool v1, size_t lds, double *Uo, double *gao) {
   const Dims &d = h->d;
   if (h->cam_global) {
     const int grid = d.nTiles < 2048 ? d.nTiles : 2048;
     if (v1 && dump)
-      hipLaunchKernelGGL((k_linearize<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
+      hipLaunchKernelGGL((k_linearize<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl, fm);
     else if (v1)
-      hipLaunchKernelGGL((k_linearize<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
+      hipLaunchKernelGGL((k_linearize<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl, fm);
     else if (dump)
-      hipLaunchKernelGGL((k_linearize2<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
+      hipLaunchKernelGGL((k_linearize2<true, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl, fm);
     else
-      hipLaunchKernelGGL((k_linearize2<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl);
+      hipLaunchKernelGGL((k_linearize2<false, true, LM>), dim3(grid), dim3(TILE_OBS), 0, h->stream, a, rl, fm);
     if (h->nLong) {
       if (dump)
-        hipLaunchKernelGGL((k_linearize_long<true, true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr, rl);
+        hipLaunchKernelGGL((k_linearize_long<true, true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr, rl, fm);
       else
-        hipLaunchKernelGGL((k_linearize_long<false, true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr, rl);
+        hipLaunchKernelGGL((k_linearize_long<false, true, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, (double *)nullptr, rl, fm);
     }
     hipLaunchKernelGGL(k_cam_sums<LM>, dim3((h->nCamUnits + 3) / 4), dim3(256), 0, h->stream, a, h->cam_obs,
-                       h->cam_units, h->nCamUnits, rl);
+                       h->cam_units, h->nCamUnits, rl, fm);
     hipLaunchKernelGGL(k_cam_finalize, dim3((42 * d.nC + 255) / 256), dim3(256), 0, h->stream, h->camacc, d.nC,
                        h->coeff, h->coeff_g, Uo, gao);
   } else {
     if (v1 && dump)
-      hipLaunchKernelGGL((k_linearize<true, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl);
+      hipLaunchKernelGGL((k_linearize<true, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl, fm);
     else if (v1)
-      hipLaunchKernelGGL((k_linearize<false, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl);
+      hipLaunchKernelGGL((k_linearize<false, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl, fm);
     else if (dump)
-      hipLaunchKernelGGL((k_linearize2<true, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl);
+      hipLaunchKernelGGL((k_linearize2<true, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl, fm);
     else
-      hipLaunchKernelGGL((k_linearize2<false, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl);
+      hipLaunchKernelGGL((k_linearize2<false, false, LM>), dim3(h->nPart), dim3(TILE_OBS), lds, h->stream, a, rl, fm);
     int nslab = h->nPart;
     if (h->nLong) {  // their camera sums: one more slab (zeroed by the caller)
       double *slab = h->campart + (size_t)h->nPart * d.nC * CAM_ACC;
       if (dump)
-        hipLaunchKernelGGL((k_linearize_long<true, false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab, rl);
+        hipLaunchKernelGGL((k_linearize_long<true, false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab, rl, fm);
       else
-        hipLaunchKernelGGL((k_linearize_long<false, false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab, rl);
+        hipLaunchKernelGGL((k_linearize_long<false, false, LM>), dim3(h->nLong), dim3(TILE_OBS), 0, h->stream, a, h->long_pts, slab, rl, fm);
       nslab++;
     }
     hipLaunchKernelGGL(k_cam_reduce, dim3(d.nC), dim3(1024), 0, h->stream, h->campart, nslab, d.nC, h->coeff,
@@ -689,6 +742,7 @@ int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
   a.kc = h->lens_kc;
   a.wl = h->lens_w;
   const RobustLoss rl = make_robust_loss(h->loss_kind, h->loss_c);
+  const FixedMask fm = {h->fix_cams, h->fix_pts};
   {
     const char *m = getenv("PSBA_LIN_MODE");
     a.mode = m ? atoi(m) : 0;
@@ -698,8 +752,8 @@ int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
   // static LDS of the kernel is ~54 KiB: beyond 64 KiB in all, the dynamic part needs the attribute
   if (!h->lin_attr_set && lds > 8 * 1024) {
     int rc = PSBA_OK;
-    for (int lm = 0; lm < LENS_MODELS && rc == PSBA_OK; lm++)
-      lens_dispatch(lm, [&](auto m) { rc = set_lin_attrs<decltype(m)::value>(h); });
+    for (int lm = 0; lm < 2 * LENS_MODELS && rc == PSBA_OK; lm++)
+      lens_dispatch_fixed(lm % LENS_MODELS, lm >= LENS_MODELS, [&](auto m) { rc = set_lin_attrs<decltype(m)::value>(h); });
     if (rc != PSBA_OK) return rc;
     h->lin_attr_set = true;
   }
@@ -711,7 +765,10 @@ int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
     else if (h->nLong)
       PSBA_HIP(h, hipMemsetAsync(h->campart + (size_t)h->nPart * d.nC * CAM_ACC, 0, sizeof(double) * CAM_ACC * (size_t)d.nC,
                                  h->stream));
-    lens_dispatch(h->lens, [&](auto m) { enqueue_linearize<decltype(m)::value>(h, a, rl, dump, v1, lds, Uo, gao); });
+    lens_dispatch_fixed(h->lens, h->has_fixed, [&](auto m) { enqueue_linearize<decltype(m)::value>(h, a, rl, fm, dump, v1, lds, Uo, gao); });
+    if (h->has_fixed)  // the placeholder blocks, into whichever set of outputs this linearization wrote
+      hipLaunchKernelGGL(k_fixed_diag, dim3((d.nC + d.nP + 255) / 256), dim3(256), 0, h->stream, fm, d.nC, d.nP, h->coeff,
+                         h->rank == 0 ? h->coeff : 0.0, Uo, gao, a.PV);
   }
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
@@ -743,8 +800,12 @@ int launch_max_diag(psba_ctx *h) {
   PSBA_HIP(h, hipMemsetAsync(h->scal + SC_MAXDIAG, 0, sizeof(double), h->stream));
   int grid = (h->d.nP + 255) / 256;
   if (grid > 512) grid = 512;
-  hipLaunchKernelGGL(k_max_diag, dim3(grid), dim3(256), 0, h->stream, h->U, h->PV, h->d.nC, h->d.nP,
-                     h->scal + SC_MAXDIAG);
+  if (h->has_fixed)
+    hipLaunchKernelGGL(k_max_diag_fixed, dim3(grid), dim3(256), 0, h->stream, h->U, h->PV, h->d.nC, h->d.nP,
+                       h->scal + SC_MAXDIAG, FixedMask{h->fix_cams, h->fix_pts});
+  else
+    hipLaunchKernelGGL(k_max_diag, dim3(grid), dim3(256), 0, h->stream, h->U, h->PV, h->d.nC, h->d.nP,
+                       h->scal + SC_MAXDIAG);
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }

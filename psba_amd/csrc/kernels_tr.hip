@@ -36,7 +36,7 @@ struct JmulArgs {
 
 // J x with the whitened Jacobian blocks (covariances: L A, L B; a robust loss: w L A, w L B) of the handle's lens model
 template <int LM>
-__global__ __launch_bounds__(256) void k_jmul(JmulArgs p, RobustLoss rl) {  // rl: read only by the LENS_ROBUST instantiations
+__global__ __launch_bounds__(256) void k_jmul(JmulArgs p, RobustLoss rl, FixedMask fm) {  // rl, fm: read only by the LENS_ROBUST / LENS_FIXED instantiations
   __shared__ double sRed[3][4];
   double d11 = 0.0, d12 = 0.0, d22 = 0.0;
   for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < p.nO; a += gridDim.x * blockDim.x) {
@@ -52,19 +52,22 @@ __global__ __launch_bounds__(256) void k_jmul(JmulArgs p, RobustLoss rl) {  // r
     lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
     lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
+    // the masked J: a fixed block's entries of x are not read at all (they may hold anything, NaN included)
+    const int fx = fix_load<LM>(fm, i, j);
+    const bool fc = (fx & FIX_CAM) != 0, fp = (fx & FIX_PT) != 0;
     double r1[2], r2[2];
 #pragma unroll
     for (int k = 0; k < 2; k++) {  // compute_Jmultiply.cl:32-46: row k of A_ij, then of B_ij
       double s1 = 0.0, s2 = 0.0;
 #pragma unroll
       for (int c = 0; c < 6; c++) {
-        s1 += A[6 * k + c] * p.x1[6 * j + c];
-        s2 += A[6 * k + c] * p.x2[6 * j + c];
+        s1 += fc ? 0.0 : A[6 * k + c] * p.x1[6 * j + c];
+        s2 += fc ? 0.0 : A[6 * k + c] * p.x2[6 * j + c];
       }
 #pragma unroll
       for (int c = 0; c < 3; c++) {
-        s1 += B[3 * k + c] * p.x1[p.nA + 3 * (size_t)i + c];
-        s2 += B[3 * k + c] * p.x2[p.nA + 3 * (size_t)i + c];
+        s1 += fp ? 0.0 : B[3 * k + c] * p.x1[p.nA + 3 * (size_t)i + c];
+        s2 += fp ? 0.0 : B[3 * k + c] * p.x2[p.nA + 3 * (size_t)i + c];
       }
       r1[k] = s1;
       r2[k] = s2;
@@ -107,6 +110,22 @@ __global__ __launch_bounds__(256) void k_newp(const double *cams, const double *
     newcams[t] = cams[t] + dp[t];
   else if (t < (size_t)nA + nB)
     newpts[t - nA] = pts[t - nA] + dp[t];
+}
+
+// the same under a mask (psba_set_fixed): a fixed block's entries of dp are ignored and zeroed, its proposal is the
+// current block bit for bit
+__global__ __launch_bounds__(256) void k_newp_fixed(const double *cams, const double *pts, double *dp, int nA, int nB,
+                                                    double *newcams, double *newpts, FixedMask fm) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < (size_t)nA) {
+    const bool f = fm.cams && fm.cams[t / 6];
+    if (f) dp[t] = 0.0;
+    newcams[t] = f ? cams[t] : cams[t] + dp[t];
+  } else if (t < (size_t)nA + nB) {
+    const bool f = fm.pts && fm.pts[(t - nA) / 3];
+    if (f) dp[t] = 0.0;
+    newpts[t - nA] = f ? pts[t - nA] : pts[t - nA] + dp[t];
+  }
 }
 
 // ---- modified Cholesky -------------------------------------------------------------------
@@ -553,8 +572,9 @@ int launch_jmul(psba_ctx *h, const double *x1_dev, const double *x2_dev, double 
   PSBA_HIP(h, hipMemsetAsync(dots_dev, 0, 3 * sizeof(double), h->stream));
   int grid = (h->d.nO + 255) / 256;
   if (grid > 1024) grid = 1024;
-  lens_dispatch(h->lens, [&](auto m) {
-    hipLaunchKernelGGL(k_jmul<decltype(m)::value>, dim3(grid), dim3(256), 0, h->stream, a, rl);
+  const FixedMask fm = {h->fix_cams, h->fix_pts};
+  lens_dispatch_fixed(h->lens, h->has_fixed, [&](auto m) {
+    hipLaunchKernelGGL(k_jmul<decltype(m)::value>, dim3(grid), dim3(256), 0, h->stream, a, rl, fm);
   });
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
@@ -568,9 +588,13 @@ int launch_pack_g(psba_ctx *h, double *g_dev) {
   return PSBA_OK;
 }
 
-int launch_newp(psba_ctx *h, const double *dp_dev) {
+int launch_newp(psba_ctx *h, double *dp_dev) {
   const size_t n = (size_t)h->d.nT;
-  hipLaunchKernelGGL(k_newp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->cams[h->cur], h->pts[h->cur],
+  if (h->has_fixed)
+    hipLaunchKernelGGL(k_newp_fixed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->cams[h->cur], h->pts[h->cur],
+                       dp_dev, h->d.nA, h->d.nB, h->cams[1 - h->cur], h->pts[1 - h->cur], FixedMask{h->fix_cams, h->fix_pts});
+  else
+    hipLaunchKernelGGL(k_newp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->cams[h->cur], h->pts[h->cur],
                      dp_dev, h->d.nA, h->d.nB, h->cams[1 - h->cur], h->pts[1 - h->cur]);
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;

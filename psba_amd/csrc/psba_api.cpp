@@ -121,6 +121,10 @@ static void free_problem_buffers(psba_ctx *h) {
   dev_free(h->lens_kc);
   dev_free(h->lens_w);
   dev_free(h->obs_s);
+  dev_free(h->fix_cams);
+  dev_free(h->fix_pts);
+  h->n_fix_cams = h->n_fix_pts = 0;
+  h->has_fixed = h->struct_only = h->try_shortcut = false;
   h->lens = 0;
   h->loss_kind = PSBA_LOSS_NONE;
   h->loss_c = 1.0;
@@ -392,6 +396,64 @@ int psba_robust_loss(psba_handle h, int *kind, double *scale) {
   CHECK_H(h);
   if (kind) *kind = h->loss_kind;
   if (scale) *scale = h->loss_c;
+  return PSBA_OK;
+}
+
+// ---- fixed parameter blocks (camera_model.h FixedMask) ----
+int psba_set_fixed(psba_handle h, const unsigned char *fixed_cams, const unsigned char *fixed_pts) {
+  CHECK_H(h);
+  TRY(lens_settable(h, __func__));
+  const int nC = h->d.nC, nP = h->d.nP;
+  int nfc = 0, nfp = 0;
+  for (int j = 0; fixed_cams && j < nC; j++) nfc += fixed_cams[j] ? 1 : 0;
+  for (int i = 0; fixed_pts && i < nP; i++) nfp += fixed_pts[i] ? 1 : 0;
+  // (under a rank layout this rank sees only its own points: the other ranks' may be free)
+  if (h->nranks == 1 && nfc == nC && nfp == nP)
+    return fail(h, PSBA_E_INVALID, "%s: every camera and every point is fixed: no free parameter is left", __func__);
+  // a mask without a non-zero entry is no mask.  The new masks are staged in buffers of their own and swapped in
+  // only when both are on the device: an allocation or a copy that fails leaves the handle as it was
+  std::vector<unsigned char> fc, fp;
+  unsigned char *new_c = nullptr, *new_p = nullptr;
+  auto stage = [&]() -> int {
+    if (nfc) {
+      fc.resize((size_t)nC);
+      for (int j = 0; j < nC; j++) fc[j] = fixed_cams[j] ? 1 : 0;
+      TRY(dev_alloc(h, &new_c, (size_t)nC));
+      PSBA_HIP(h, hipMemcpyAsync(new_c, fc.data(), fc.size(), hipMemcpyHostToDevice, h->stream));
+    }
+    if (nfp) {
+      fp.resize((size_t)nP);
+      for (int i = 0; i < nP; i++) fp[i] = fixed_pts[i] ? 1 : 0;
+      TRY(dev_alloc(h, &new_p, (size_t)nP));
+      PSBA_HIP(h, hipMemcpyAsync(new_p, fp.data(), fp.size(), hipMemcpyHostToDevice, h->stream));
+    }
+    PSBA_HIP(h, hipStreamSynchronize(h->stream));  // (also: nothing queued still reads the old masks)
+    return PSBA_OK;
+  };
+  const int rc = stage();
+  if (rc != PSBA_OK) {
+    (void)hipStreamSynchronize(h->stream);
+    dev_free(new_c);
+    dev_free(new_p);
+    return rc;
+  }
+  dev_free(h->fix_cams);
+  dev_free(h->fix_pts);
+  h->fix_cams = new_c;
+  h->fix_pts = new_p;
+  h->n_fix_cams = nfc;
+  h->n_fix_pts = nfp;
+  h->has_fixed = nfc > 0 || nfp > 0;  // none: the plain kernel instantiations, as on a handle that never set a mask
+  h->struct_only = nfc == nC;
+  h->try_shortcut = false;
+  lens_changed(h);
+  return PSBA_OK;
+}
+
+int psba_fixed_counts(psba_handle h, int *n_fixed_cams, int *n_fixed_pts) {
+  CHECK_H(h);
+  if (n_fixed_cams) *n_fixed_cams = h->n_fix_cams;
+  if (n_fixed_pts) *n_fixed_pts = h->n_fix_pts;
   return PSBA_OK;
 }
 
@@ -919,7 +981,13 @@ int psba_schur_assemble(psba_handle h, double mu) {
   CHECK_H(h);
   NEED(h, h->linearized, "psba_linearize first");
   h->mu = mu;
-  TRY(launch_schur(h, mu, false));
+  // every camera fixed: no coupled system.  dpa = 0 and K3's point part is the whole solve, so K2, the S-reduce and the
+  // factorization are not queued at all (PSBA_FIXED_NO_SHORTCUT=1: the general route, for the test that compares them)
+  h->try_shortcut = h->struct_only && h->cnp == 6 && !getenv("PSBA_FIXED_NO_SHORTCUT");
+  if (h->try_shortcut)
+    TRY(launch_struct_only_try(h, mu));
+  else
+    TRY(launch_schur(h, mu, false));
   h->assembled = true;
   h->solved = h->backsubbed = false;
   return PSBA_OK;
@@ -949,7 +1017,7 @@ static int allreduce_schur(psba_ctx *h) {
 int psba_schur_reduce(psba_handle h) {
   CHECK_H(h);
   NEED(h, h->assembled, "psba_schur_assemble first");
-  if (!h->comm) return PSBA_OK;
+  if (!h->comm || h->try_shortcut) return PSBA_OK;
   ProfScope ps(h, PSBA_K_ALLREDUCE);
   TRY(allreduce_schur(h));
   return PSBA_OK;
@@ -958,6 +1026,11 @@ int psba_schur_reduce(psba_handle h) {
 int psba_schur_solve(psba_handle h) {
   CHECK_H(h);
   NEED(h, h->assembled, "psba_schur_assemble first");
+  if (h->try_shortcut) {  // structure-only: dpa is zero already, the try is stamped, psba_backsub does the rest
+    h->assembled = false;
+    h->solved = true;
+    return PSBA_OK;
+  }
   if (h->packed_pending) TRY(allreduce_schur(h));  // psba_schur_reduce was skipped
   if (h->solver == PSBA_SOLVER_PCG) {
     TRY(launch_pcg_solve(h));
@@ -1226,6 +1299,7 @@ int psba_pcg_info(psba_handle h, int *iters, double *relres, long long *blocks, 
 int psba_get_sparse_S(psba_handle h, int *jk, double *val, double *ea) {
   CHECK_H(h);
   NEED(h, h->assembled && h->solver == PSBA_SOLVER_PCG, "psba_schur_assemble with PSBA_SOLVER_PCG first");
+  NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");
   if (jk) TRY(d2h(h, jk, h->bs_jk, sizeof(int2) * (size_t)h->bs_nblk));
   if (val) TRY(d2h(h, val, h->bs_val, sizeof(double) * 36 * (size_t)h->bs_nblk));
   if (ea) TRY(d2h(h, ea, h->bs_ea, sizeof(double) * (size_t)h->d.nA));
@@ -1236,6 +1310,7 @@ int psba_get_sparse_S(psba_handle h, int *jk, double *val, double *ea) {
 int psba_set_sparse_S(psba_handle h, const double *val, const double *ea) {
   CHECK_H(h);
   NEED(h, h->assembled && h->solver == PSBA_SOLVER_PCG, "psba_schur_assemble with PSBA_SOLVER_PCG first");
+  NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");
   if (val) PSBA_HIP(h, hipMemcpyAsync(h->bs_val, val, sizeof(double) * 36 * (size_t)h->bs_nblk, hipMemcpyHostToDevice, h->stream));
   if (ea) PSBA_HIP(h, hipMemcpyAsync(h->bs_ea, ea, sizeof(double) * (size_t)h->d.nA, hipMemcpyHostToDevice, h->stream));
   PSBA_HIP(h, hipStreamSynchronize(h->stream));
@@ -1324,6 +1399,14 @@ int psba_cholmod_lambda(psba_handle h, int reassemble, double *lambda, double *i
   NEED(h, h->uploaded, "no problem uploaded");
   if (h->nranks > 1 && !h->comm)
     return fail(h, PSBA_E_INVALID, "psba_cholmod_lambda on a rank layout needs the communicator (S must be complete)");
+  // a structure-only try (every camera fixed) has assembled nothing, and forming S here at lambda = 0 would put the
+  // try's solve on the general route with the wrong damping: finish the try first (the loops never get here: such a
+  // try cannot fail its factorization)
+  NEED(h, !(h->try_shortcut && h->assembled), "a structure-only try is open (psba_schur_solve / psba_backsub first)");
+  if (h->try_shortcut) {  // the last try assembled nothing: whatever the caller says, S has to be formed here
+    reassemble = 1;
+    h->try_shortcut = false;
+  }
   if (h->solver == PSBA_SOLVER_PCG) {
     // block-sparse mode: no dense S to factor -- the damping estimate is the Gershgorin shift of the stored blocks
     // (kernels_pcg.hip; no reference counterpart: the reference has no sparse mode)
@@ -1388,6 +1471,7 @@ static int relinearize_dump(psba_ctx *h) {
 static int reassemble_dump(psba_ctx *h) {
   NEED(h, h->linearized, "linearise first (compute_jacobiQT / compute_U / ...)");
   TRY(ensure_dbg(h));
+  h->try_shortcut = false;  // the mirror always takes the general route
   TRY(launch_schur(h, h->mu_applied ? h->mu : 0.0, true));
   h->assembled = true;
   h->solved = h->backsubbed = false;
@@ -1521,6 +1605,7 @@ int psba_compute_ea(psba_handle h, double *ea) {
 int psba_SPDinv_matVec(psba_handle h, double *dpa) {
   CHECK_H(h);
   NEED(h, h->assembled, "compute_S / compute_ea first");
+  NEED(h, !h->try_shortcut, "every camera is fixed: psba_schur_assemble assembled no S (compute_S / compute_ea first)");
   TRY(launch_chol_solve(h));
   h->assembled = false;
   h->solved = true;
@@ -1650,6 +1735,7 @@ int psba_get_reduce_buffer(psba_handle h, double *out) {
   NEED(h, h->assembled, "psba_schur_assemble first");
   NEED(h, !h->comm, "the reduce-buffer verbs are for handles without a communicator");
   NEED(h, h->solver != PSBA_SOLVER_PCG, "no dense reduce buffer with PSBA_SOLVER_PCG (psba_get_sparse_S)");
+  NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");
   if (packed_hook(h)) return d2h(h, out, h->redp, sizeof(double) * h->packed_doubles);
   return d2h(h, out, h->red, sizeof(double) * (size_t)(h->n32 + 1) * h->n32);
 }
@@ -1659,6 +1745,7 @@ int psba_set_reduce_buffer(psba_handle h, const double *in) {
   NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
   NEED(h, h->assembled, "psba_schur_assemble first");
   NEED(h, !h->comm, "the reduce-buffer verbs are for handles without a communicator");
+  NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");
   if (!in) return fail(h, PSBA_E_INVALID, "null buffer");
   if (packed_hook(h)) {  // the summed packed sums: psba_schur_solve scatters them (k_schur_expand)
     PSBA_HIP(h, hipMemcpyAsync(h->redp, in, sizeof(double) * h->packed_doubles, hipMemcpyHostToDevice, h->stream));

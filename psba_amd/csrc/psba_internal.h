@@ -170,6 +170,13 @@ struct psba_ctx {
   double *obs_s = nullptr;      // [nO] psba_obs_sq_residuals' device output, allocated on first use
   double *lens_kc = nullptr;    // [nC][5] k1..k5, allocated while distortion is set
   double *lens_w = nullptr;     // [nO][4] (l00, l01, l11, 0): L^T L = Sigma^-1, allocated while covariances are set
+  // fixed parameter blocks (psba_set_fixed; camera_model.h FixedMask): byte masks on the device, allocated while a
+  // mask of that kind with a non-zero entry is set; an upload resets them to none.  has_fixed selects the LENS_FIXED
+  // kernel instantiations at the launch sites (lens_dispatch_fixed); struct_only = every camera is fixed
+  unsigned char *fix_cams = nullptr, *fix_pts = nullptr;  // [nC], [nP]
+  int n_fix_cams = 0, n_fix_pts = 0;
+  bool has_fixed = false, struct_only = false;
+  bool try_shortcut = false;    // this try took the structure-only shortcut: nothing was assembled or factored
   int *iidx = nullptr;          // [nO] point of each observation    (iidx_buffer)
   int *jidx = nullptr;          // [nO] camera of each observation   (jidx_buffer)
   int *ptr = nullptr;           // [nP+1] point CSR over observations (replaces blkIdx_buffer)
@@ -389,10 +396,11 @@ int chol_dist_finish(psba_ctx *h);
 // kernels_backsub.hip
 int launch_backsub(psba_ctx *h, double mu, bool dump);
 int launch_publish_scal(psba_ctx *h, hipStream_t s);
+int launch_struct_only_try(psba_ctx *h, double mu);
 // kernels_tr.hip
 int launch_jmul(psba_ctx *h, const double *x1_dev, const double *x2_dev, double *out1_dev, double *dots_dev);
 int launch_pack_g(psba_ctx *h, double *g_dev);
-int launch_newp(psba_ctx *h, const double *dp_dev);
+int launch_newp(psba_ctx *h, double *dp_dev);
 int launch_cholmod(psba_ctx *h, double *out4_dev);
 
 }  // namespace psba
