@@ -1712,8 +1712,8 @@ static int chol_dist_comm(psba_ctx *h) {
   const int n32 = h->n32;
   const size_t per = (size_t)(n32 + 1) * 64;  // a slot of the exchange buffer
   if (!h->dist_buf) {
-    if (hipMalloc((void **)&h->dist_buf, sizeof(double) * per * (size_t)(c.NB / 64 + 1)) != hipSuccess)
-      return fail(h, PSBA_E_HIP, "no memory for the column exchange buffers");
+    const int rc = h->dist_buf.alloc(h, per * (size_t)(c.NB / 64 + 1));
+    if (rc != PSBA_OK) return rc;
   }
   int rc = chol_dist_begin(h);
   for (int J = 0; J < n32 && rc == PSBA_OK; J += c.NB) {
@@ -1767,20 +1767,16 @@ int launch_chol_graph(psba_ctx *h) {
     return PSBA_OK;
   }
   if (!h->chol_graph[v] || h->chol_graph_n32[v] != h->n32 || h->chol_graph_red[v] != h->red) {
-    if (h->chol_graph[v]) {
-      (void)hipGraphExecDestroy(h->chol_graph[v]);
-      h->chol_graph[v] = nullptr;
-    }
+    h->chol_graph[v].reset();
     hipGraph_t g = nullptr;
     PSBA_HIP(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     enqueue_chain(h, h->stream, v == 1);
     PSBA_HIP(h, hipStreamEndCapture(h->stream, &g));
-    hipError_t e = hipGraphInstantiate(&h->chol_graph[v], g, nullptr, nullptr, 0);
+    hipGraphExec_t ge = nullptr;
+    hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
-    if (e != hipSuccess) {
-      h->chol_graph[v] = nullptr;
-      return fail(h, PSBA_E_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(h, PSBA_E_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
+    h->chol_graph[v].reset(ge);
     h->chol_graph_n32[v] = h->n32;
     h->chol_graph_red[v] = h->red;
   }

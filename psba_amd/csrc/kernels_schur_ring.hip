@@ -419,7 +419,8 @@ int launch_schur_ring(psba_ctx *h, double mu, bool dump) {
     h->ring_attr_set = true;
   }
   if (getenv("PSBA_RING_TIMING") && !h->chol_tim_ring) {
-    PSBA_HIP(h, hipMalloc(&h->chol_tim_ring, sizeof(long long) * 8192));
+    const int rc = h->chol_tim_ring.alloc(h, 8192);
+    if (rc != PSBA_OK) return rc;
     PSBA_HIP(h, hipMemset(h->chol_tim_ring, 0, sizeof(long long) * 8192));
   }
   RingArgs a;

@@ -88,116 +88,34 @@ ProfScope::~ProfScope() {
     if (rc__ < 0) return rc__;    \
   } while (0)
 
-template <typename T>
-static int dev_alloc(psba_ctx *h, T **p, size_t n) {
-  PSBA_HIP(h, hipMalloc((void **)p, sizeof(T) * (n ? n : 1)));
-  // PSBA_DEBUG_POISON=1 (tests): fresh allocations filled with 0xFF bytes (NaN as doubles, -1 as ints), so that
-  // anything read before it is written shows in the results instead of depending on what the allocator recycled
+namespace psba {
+int alloc_bytes(psba_ctx *h, void **p, size_t bytes, bool pinned) {
+  *p = nullptr;
+  if (pinned) {
+    if (hipHostMalloc(p, bytes) != hipSuccess) return fail(h, PSBA_E_NOMEM, "no pinned memory (%zu bytes)", bytes);
+    return PSBA_OK;
+  }
+  PSBA_HIP(h, hipMalloc(p, bytes));
   static const bool poison = getenv("PSBA_DEBUG_POISON") != nullptr;
   if (poison) {
-    PSBA_HIP(h, hipMemsetAsync(*p, 0xFF, sizeof(T) * (n ? n : 1), h->stream));
+    PSBA_HIP(h, hipMemsetAsync(*p, 0xFF, bytes, h->stream));
     PSBA_HIP(h, hipStreamSynchronize(h->stream));
   }
   return PSBA_OK;
 }
+}  // namespace psba
+
+// v on the device, in a buffer of its own (the blocking copy goes through the null stream: psba_upload_problem ends
+// with a device-wide synchronisation)
 template <typename T>
-static void dev_free(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
+static int upload(psba_ctx *h, DevBuf<T> &dst, const std::vector<T> &v) {
+  TRY(dst.alloc(h, v.size()));
+  if (!v.empty()) PSBA_HIP(h, hipMemcpy(dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
+  return PSBA_OK;
 }
 
-static void free_problem_buffers(psba_ctx *h) {
-  for (int v = 0; v < 2; v++)
-    if (h->chol_graph[v]) {
-      (void)hipGraphExecDestroy(h->chol_graph[v]);
-      h->chol_graph[v] = nullptr;
-    }
-  dev_free(h->camconst);
-  dev_free(h->cams[0]);
-  dev_free(h->cams[1]);
-  dev_free(h->pts[0]);
-  dev_free(h->pts[1]);
-  dev_free(h->impts);
-  dev_free(h->lens_kc);
-  dev_free(h->lens_w);
-  dev_free(h->obs_s);
-  dev_free(h->fix_cams);
-  dev_free(h->fix_pts);
-  h->n_fix_cams = h->n_fix_pts = 0;
-  h->has_fixed = h->struct_only = h->try_shortcut = false;
-  h->lens = 0;
-  h->loss_kind = PSBA_LOSS_NONE;
-  h->loss_c = 1.0;
-  dev_free(h->iidx);
-  dev_free(h->jidx);
-  dev_free(h->ptr);
-  dev_free(h->params0);
-  dev_free(h->tile_pt);
-  dev_free(h->tile_desc);
-  dev_free(h->long_pts);
-  h->nLong = 0;
-  dev_free(h->W);
-  dev_free(h->W_alt);
-  dev_free(h->PV_alt);
-  dev_free(h->U_alt);
-  dev_free(h->ga_alt);
-  dev_free(h->PV);
-  dev_free(h->U);
-  dev_free(h->ga);
-  dev_free(h->campart);
-  dev_free(h->camacc);
-  dev_free(h->cam_obs);
-  dev_free(h->cam_units);
-  h->nCamUnits = 0;
-  dev_free(h->red);
-  dev_free(h->items);
-  dev_free(h->wg);
-  dev_free(h->posblock);
-  dev_free(h->gtab);
-  dev_free(h->diag0);
-  dev_free(h->redp);
-  dev_free(h->slab);
-#ifdef PSBA_BUILD_EXPERIMENTS
-  dev_free(h->ring_wg);
-  dev_free(h->ring_steps);
-  dev_free(h->ring_entries);
-  dev_free(h->ring_ops);
-  dev_free(h->ring_jobs);
-  dev_free(h->ring_bl0);
-  dev_free(h->ring_canon);
-  dev_free(h->ring_slab);
-  dev_free(h->ring_pvi);
-#endif
-  h->ring_nWg = h->ring_nS = 0;
-  dev_free(h->bs_val);
-  h->bs_ea = nullptr;
-  dev_free(h->bs_jk);
-  dev_free(h->bs_diag);
-  dev_free(h->bs_rowptr);
-  dev_free(h->bs_rowent);
-  dev_free(h->pcg_vec);
-  dev_free(h->pcg_minv);
-  dev_free(h->pcg_scal);
-  h->bs_nblk = 0;
-  dev_free(h->own_prod);
-  dev_free(h->own_waves);
-  dev_free(h->own_units);
-  h->own_nwaves = 0;
-  dev_free(h->dp);
-  dev_free(h->trv[0]);
-  dev_free(h->trv[1]);
-  dev_free(h->jmul_out);
-  dev_free(h->chol_ws);
-  dev_free(h->dist_buf);
-  dev_free(h->chol_L);
-  dev_free(h->dbg_ex);
-  dev_free(h->dbg_JA);
-  dev_free(h->dbg_JB);
-  dev_free(h->dbg_Y);
-  dev_free(h->dbg_Vinv);
-  dev_free(h->dbg_eb);
-  h->uploaded = h->linearized = h->assembled = h->solved = h->backsubbed = false;
-}
+// the uploaded problem and everything that was set or computed on it goes: buffers, schedules, settings, try state
+static void drop_problem(psba_ctx *h) { static_cast<ProblemState &>(*h) = ProblemState{}; }
 
 extern "C" {
 
@@ -229,11 +147,14 @@ int psba_create(int device, psba_handle *out) {
   h->device = device;
   if ((e = hipSetDevice(device)) != hipSuccess ||
       (e = create_main_stream(&h->stream)) != hipSuccess ||
-      (e = hipMalloc((void **)&h->scal, sizeof(double) * NSCAL)) != hipSuccess ||
-      (e = hipHostMalloc((void **)&h->h_scal, sizeof(double) * (NSCAL + 8))) != hipSuccess ||  // (+ the publish stamp)
       (e = hipEventCreateWithFlags(&h->scal_event, hipEventDisableTiming)) != hipSuccess) {
     int rc = fail(nullptr, PSBA_E_HIP, "psba_create: %s", hipGetErrorString(e));
-    delete h;
+    psba_destroy(h);
+    return rc;
+  }
+  if (h->scal.alloc(h, NSCAL) != PSBA_OK || h->h_scal.alloc(h, NSCAL + 8) != PSBA_OK) {  // (+ the publish stamp)
+    int rc = fail(nullptr, PSBA_E_HIP, "psba_create: %s", h->err.c_str());
+    psba_destroy(h);
     return rc;
   }
   if (hipHostGetDevicePointer((void **)&h->h_scal_dev, h->h_scal, 0) != hipSuccess) h->h_scal_dev = nullptr;
@@ -263,17 +184,13 @@ int psba_destroy(psba_handle h) {
     (void)hipStreamDestroy(h->chol_side);
   }
   if (h->stream2) (void)hipStreamDestroy(h->stream2);
-  free_problem_buffers(h);
-  dev_free(h->scal);
-  if (h->h_scal) (void)hipHostFree(h->h_scal);
-  if (h->pcg_host) (void)hipHostFree(h->pcg_host);
   if (h->scal_event) (void)hipEventDestroy(h->scal_event);
   for (auto &s : h->spans) {
     (void)hipEventDestroy(s.a);
     (void)hipEventDestroy(s.b);
   }
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;  // (the problem's buffers, the scalar blocks and the captured graphs go with their owners)
   return PSBA_OK;
 }
 
@@ -311,12 +228,12 @@ int psba_set_distortion(psba_handle h, const double *kc) {
   CHECK_H(h);
   TRY(lens_settable(h, __func__));
   if (!kc) {
-    dev_free(h->lens_kc);
+    h->lens_kc.reset();
     h->lens &= ~LENS_DIST;
   } else {
     for (int t = 0; t < 5 * h->d.nC; t++)
       if (!std::isfinite(kc[t])) return fail(h, PSBA_E_INVALID, "%s: kc[%d] of camera %d is not finite", __func__, t % 5, t / 5);
-    if (!h->lens_kc) TRY(dev_alloc(h, &h->lens_kc, (size_t)5 * h->d.nC));
+    if (!h->lens_kc) TRY(h->lens_kc.alloc(h, (size_t)5 * h->d.nC));
     PSBA_HIP(h, hipMemcpyAsync(h->lens_kc, kc, sizeof(double) * 5 * (size_t)h->d.nC, hipMemcpyHostToDevice, h->stream));
     PSBA_HIP(h, hipStreamSynchronize(h->stream));
     h->lens |= LENS_DIST;
@@ -329,7 +246,7 @@ int psba_set_obs_covariance(psba_handle h, const double *cov) {
   CHECK_H(h);
   TRY(lens_settable(h, __func__));
   if (!cov) {
-    dev_free(h->lens_w);
+    h->lens_w.reset();
     h->lens &= ~LENS_COV;
     lens_changed(h);
     return PSBA_OK;
@@ -356,7 +273,7 @@ int psba_set_obs_covariance(psba_handle h, const double *cov) {
     w[(size_t)LENS_WSTRIDE * a + 1] = l01;
     w[(size_t)LENS_WSTRIDE * a + 2] = std::sqrt(t);
   }
-  if (!h->lens_w) TRY(dev_alloc(h, &h->lens_w, w.size()));
+  if (!h->lens_w) TRY(h->lens_w.alloc(h, w.size()));
   PSBA_HIP(h, hipMemcpyAsync(h->lens_w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, h->stream));
   PSBA_HIP(h, hipStreamSynchronize(h->stream));
   h->lens |= LENS_COV;
@@ -413,18 +330,18 @@ int psba_set_fixed(psba_handle h, const unsigned char *fixed_cams, const unsigne
   // a mask without a non-zero entry is no mask.  The new masks are staged in buffers of their own and swapped in
   // only when both are on the device: an allocation or a copy that fails leaves the handle as it was
   std::vector<unsigned char> fc, fp;
-  unsigned char *new_c = nullptr, *new_p = nullptr;
+  DevBuf<unsigned char> new_c, new_p;
   auto stage = [&]() -> int {
     if (nfc) {
       fc.resize((size_t)nC);
       for (int j = 0; j < nC; j++) fc[j] = fixed_cams[j] ? 1 : 0;
-      TRY(dev_alloc(h, &new_c, (size_t)nC));
+      TRY(new_c.alloc(h, (size_t)nC));
       PSBA_HIP(h, hipMemcpyAsync(new_c, fc.data(), fc.size(), hipMemcpyHostToDevice, h->stream));
     }
     if (nfp) {
       fp.resize((size_t)nP);
       for (int i = 0; i < nP; i++) fp[i] = fixed_pts[i] ? 1 : 0;
-      TRY(dev_alloc(h, &new_p, (size_t)nP));
+      TRY(new_p.alloc(h, (size_t)nP));
       PSBA_HIP(h, hipMemcpyAsync(new_p, fp.data(), fp.size(), hipMemcpyHostToDevice, h->stream));
     }
     PSBA_HIP(h, hipStreamSynchronize(h->stream));  // (also: nothing queued still reads the old masks)
@@ -432,15 +349,11 @@ int psba_set_fixed(psba_handle h, const unsigned char *fixed_cams, const unsigne
   };
   const int rc = stage();
   if (rc != PSBA_OK) {
-    (void)hipStreamSynchronize(h->stream);
-    dev_free(new_c);
-    dev_free(new_p);
+    (void)hipStreamSynchronize(h->stream);  // (before the staged buffers go)
     return rc;
   }
-  dev_free(h->fix_cams);
-  dev_free(h->fix_pts);
-  h->fix_cams = new_c;
-  h->fix_pts = new_p;
+  h->fix_cams = std::move(new_c);
+  h->fix_pts = std::move(new_p);
   h->n_fix_cams = nfc;
   h->n_fix_pts = nfp;
   h->has_fixed = nfc > 0 || nfp > 0;  // none: the plain kernel instantiations, as on a handle that never set a mask
@@ -464,7 +377,7 @@ int psba_obs_sq_residuals(psba_handle h, int which, double *s) {
   NEED(h, h->uploaded, "no problem uploaded");
   NEED(h, h->cnp == 6, "six-parameter camera blocks only (not PSBA_CAMERA_FREE_K)");
   if (which != PSBA_PARAMS_CUR && which != PSBA_PARAMS_NEW) return fail(h, PSBA_E_INVALID, "%s: which = %d", __func__, which);
-  if (!h->obs_s) TRY(dev_alloc(h, &h->obs_s, (size_t)h->d.nO));
+  if (!h->obs_s) TRY(h->obs_s.alloc(h, (size_t)h->d.nO));
   TRY(launch_residual(h, which, nullptr, h->obs_s));
   return d2h(h, s, h->obs_s, sizeof(double) * (size_t)h->d.nO);
 }
@@ -484,366 +397,398 @@ int psba_get_dims(psba_handle h, int *nCams, int *n3Dpts, int *n2Dprojs) {
   return PSBA_OK;
 }
 
-int psba_upload_problem(psba_handle h, int nCams, int n3Dpts, int n2Dprojs, const double *Kparas,
-                        const double *impts, const double *initrot, const double *camsEx,
-                        const double *pts3D, const int *iidx, const int *jidx) {
-  CHECK_H(h);
-  if (nCams <= 0 || n3Dpts <= 0 || n2Dprojs <= 0 || !Kparas || !impts || !initrot || !camsEx ||
-      !pts3D || !iidx || !jidx)
+// ---- psba_upload_problem, step by step ----------------------------------------------------
+namespace {
+struct Upload {  // the caller's arrays and what the steps derive from them on the host
+  int nC, nP, nO;
+  const double *Kparas, *impts, *initrot, *camsEx, *pts3D;
+  const int *iidx, *jidx;
+  std::vector<int> ptr;       // point CSR over the observations
+  std::vector<int> tile_pt;   // first point of each tile of the contiguous partition
+  std::vector<int> long_pts;  // points seen by more than TILE_OBS cameras
+  int maxTrack = 0;
+};
+}  // namespace
+
+// arguments and ordering, and the point CSR (replaces generate_idxs).  Nothing of the handle is touched here: a
+// rejected upload leaves the old problem usable
+static int build_point_csr(psba_ctx *h, Upload &u) {
+  if (u.nC <= 0 || u.nP <= 0 || u.nO <= 0 || !u.Kparas || !u.impts || !u.initrot || !u.camsEx || !u.pts3D || !u.iidx ||
+      !u.jidx)
     return fail(h, PSBA_E_INVALID, "psba_upload_problem: null pointer or non-positive size");
-  PSBA_HIP(h, hipSetDevice(h->device));
-  // ---- index build: point CSR + point-aligned tiles (replaces generate_idxs) ----
-  std::vector<int> ptr((size_t)n3Dpts + 1, 0);
-  for (int a = 0; a < n2Dprojs; a++) {
-    const int i = iidx[a], j = jidx[a];
-    if (i < 0 || i >= n3Dpts || j < 0 || j >= nCams)
+  if (h->cnp != 6 && (h->solver == PSBA_SOLVER_PCG || h->nranks > 1 || h->comm))
+    return fail(h, PSBA_E_INVALID, "free intrinsics: dense solver, single rank only");
+  u.ptr.assign((size_t)u.nP + 1, 0);
+  for (int a = 0; a < u.nO; a++) {
+    const int i = u.iidx[a], j = u.jidx[a];
+    if (i < 0 || i >= u.nP || j < 0 || j >= u.nC)
       return fail(h, PSBA_E_INVALID, "observation %d: point %d / camera %d out of range", a, i, j);
-    if (a > 0 && (i < iidx[a - 1] || (i == iidx[a - 1] && j <= jidx[a - 1])))
+    if (a > 0 && (i < u.iidx[a - 1] || (i == u.iidx[a - 1] && j <= u.jidx[a - 1])))
       return fail(h, PSBA_E_INVALID,
                   "observations must be sorted point-major with ascending, distinct cameras "
                   "inside a point (violated at observation %d)", a);
-    ptr[(size_t)i + 1]++;
+    u.ptr[(size_t)i + 1]++;
   }
-  int maxTrack = 0;
-  for (int i = 0; i < n3Dpts; i++) {
-    if (ptr[(size_t)i + 1] > maxTrack) maxTrack = ptr[(size_t)i + 1];
-    ptr[(size_t)i + 1] += ptr[i];
+  for (int i = 0; i < u.nP; i++) {
+    if (u.ptr[(size_t)i + 1] > u.maxTrack) u.maxTrack = u.ptr[(size_t)i + 1];
+    u.ptr[(size_t)i + 1] += u.ptr[i];
   }
-  // point-aligned tiles of at most TILE_OBS observations / TILE_PTS points.  A point seen by more
-  // cameras than a tile holds (the reference has no such limit: CL_files/compute_V.cl:6-38 loops
-  // over all cameras) is a tile of its own that the tile kernels skip; one workgroup per such point
-  // walks its observations in the *_long kernels instead.
-  std::vector<int> tile_pt, long_pts;
-  tile_pt.push_back(0);
-  {
-    int p0 = 0;
-    while (p0 < n3Dpts) {
-      int p1 = p0;
-      if (ptr[(size_t)p0 + 1] - ptr[p0] > TILE_OBS) {
-        long_pts.push_back(p0);
-        p1 = p0 + 1;
-      } else {
-        while (p1 < n3Dpts && (ptr[(size_t)p1 + 1] - ptr[p0]) <= TILE_OBS && (p1 - p0) < TILE_PTS) p1++;
-      }
-      tile_pt.push_back(p1);
-      p0 = p1;
+  return PSBA_OK;
+}
+
+// point-aligned tiles of at most TILE_OBS observations / TILE_PTS points.  A point seen by more
+// cameras than a tile holds (the reference has no such limit: CL_files/compute_V.cl:6-38 loops
+// over all cameras) is a tile of its own that the tile kernels skip; one workgroup per such point
+// walks its observations in the *_long kernels instead.
+static void cut_tiles(Upload &u) {
+  const std::vector<int> &ptr = u.ptr;
+  u.tile_pt.push_back(0);
+  for (int p0 = 0; p0 < u.nP;) {
+    int p1 = p0;
+    if (ptr[(size_t)p0 + 1] - ptr[p0] > TILE_OBS) {
+      u.long_pts.push_back(p0);
+      p1 = p0 + 1;
+    } else {
+      while (p1 < u.nP && (ptr[(size_t)p1 + 1] - ptr[p0]) <= TILE_OBS && (p1 - p0) < TILE_PTS) p1++;
     }
+    u.tile_pt.push_back(p1);
+    p0 = p1;
   }
-  free_problem_buffers(h);
-  Dims d;
-  d.nC = nCams;
-  d.nP = n3Dpts;
-  d.nO = n2Dprojs;
+}
+
+// the sizes everything else is cut to, and which form K1's camera sums take
+static void set_dims(psba_ctx *h, const Upload &u) {
   const int cnp = h->cnp;  // 6, or 11 with free intrinsics (kernels_freek.hip)
-  if (cnp != 6 && (h->solver == PSBA_SOLVER_PCG || h->nranks > 1 || h->comm))
-    return fail(h, PSBA_E_INVALID, "free intrinsics: dense solver, single rank only");
-  d.nA = cnp * nCams;
-  d.nB = 3 * n3Dpts;
+  Dims d;
+  d.nC = u.nC;
+  d.nP = u.nP;
+  d.nO = u.nO;
+  d.nA = cnp * u.nC;
+  d.nB = 3 * u.nP;
   d.nT = d.nA + d.nB;
-  d.nTilesAll = (int)tile_pt.size() - 1;
-  d.nTiles = d.nTilesAll - (int)long_pts.size();  // the tile kernels never see a long point's tile
-  if (d.nTiles < 1) d.nTiles = 1;                 // (only long points: one empty tile keeps the grids non-empty)
-  d.maxTrack = maxTrack;
-  // K1 keeps 27 accumulators per camera in LDS while they fit beside its tile buffers (nC <= 455);
-  // beyond that its camera sums go to global memory with fp64 atomics
+  d.nTilesAll = (int)u.tile_pt.size() - 1;
+  d.nTiles = d.nTilesAll - (int)u.long_pts.size();  // the tile kernels never see a long point's tile
+  if (d.nTiles < 1) d.nTiles = 1;                   // (only long points: one empty tile keeps the grids non-empty)
+  d.maxTrack = u.maxTrack;
+  h->d = d;
+  h->nLong = (int)u.long_pts.size();
   // K1's 27 sums per camera: LDS accumulators per workgroup while they leave room for three
   // workgroups per CU (up to ~220 cameras: 31 ... 36 us for K1 at 218 k observations), the
   // camera-major pass beyond (~40 us flat; the LDS form takes 55 us at 257 cameras and 64 at 455,
   // where it ends: PSBA_LIN_LDS_ACC=1 keeps it up to there)
   const size_t cam_lds_max = getenv("PSBA_LIN_LDS_ACC") ? 96 * 1024 : 48 * 1024;
-  h->cam_global = cnp == 6 && ((size_t)CAM_ACC * nCams * sizeof(double) > cam_lds_max || getenv("PSBA_LIN_GLOBAL_ACC"));
-  h->d = d;
+  h->cam_global = cnp == 6 && ((size_t)CAM_ACC * u.nC * sizeof(double) > cam_lds_max || getenv("PSBA_LIN_GLOBAL_ACC"));
   h->nPart = d.nTiles < 768 ? d.nTiles : 768;  // persistent workgroups: three per CU fit since W is staged in halves
   if (const char *e = getenv("PSBA_LIN_GRID")) h->nPart = atoi(e) > 0 && atoi(e) < d.nTiles ? atoi(e) : d.nTiles;
-  h->cur = 0;
+  h->n32 = (d.nA + 31) / 32 * 32;
+}
 
-  std::vector<double> cc((size_t)nCams * 9);
-  for (int j = 0; j < nCams; j++) {
-    for (int k = 0; k < 5; k++) cc[(size_t)9 * j + k] = Kparas[5 * j + k];
-    for (int k = 0; k < 4; k++) cc[(size_t)9 * j + 5 + k] = initrot[4 * j + k];
-  }
-  TRY(dev_alloc(h, &h->camconst, cc.size()));
-  TRY(dev_alloc(h, &h->cams[0], (size_t)d.nA));
-  TRY(dev_alloc(h, &h->cams[1], (size_t)d.nA));
-  TRY(dev_alloc(h, &h->pts[0], (size_t)d.nB));
-  TRY(dev_alloc(h, &h->pts[1], (size_t)d.nB));
-  TRY(dev_alloc(h, &h->params0, (size_t)d.nT));
-  TRY(dev_alloc(h, &h->impts, (size_t)2 * d.nO));
-  TRY(dev_alloc(h, &h->iidx, (size_t)d.nO));
-  TRY(dev_alloc(h, &h->jidx, (size_t)d.nO));
-  TRY(dev_alloc(h, &h->ptr, (size_t)d.nP + 1));
-  TRY(dev_alloc(h, &h->tile_pt, tile_pt.size()));
-  TRY(dev_alloc(h, &h->tile_desc, (size_t)d.nTiles));
-  h->nLong = (int)long_pts.size();
-  if (h->nLong) {
-    TRY(dev_alloc(h, &h->long_pts, long_pts.size()));
-    PSBA_HIP(h, hipMemcpy(h->long_pts, long_pts.data(), sizeof(int) * long_pts.size(), hipMemcpyHostToDevice));
-  }
-  TRY(dev_alloc(h, &h->W, (size_t)3 * cnp * d.nO));
-  TRY(dev_alloc(h, &h->W_alt, (size_t)3 * cnp * d.nO));
-  TRY(dev_alloc(h, &h->PV, (size_t)9 * d.nP));
-  TRY(dev_alloc(h, &h->PV_alt, (size_t)9 * d.nP));
+// everything the kernels write: parameters, both sets of linearization outputs, camera sums, S and its factor
+static int alloc_work_buffers(psba_ctx *h) {
+  const Dims &d = h->d;
+  const int cnp = h->cnp;
+  TRY(h->cams[0].alloc(h, (size_t)d.nA));
+  TRY(h->cams[1].alloc(h, (size_t)d.nA));
+  TRY(h->pts[0].alloc(h, (size_t)d.nB));
+  TRY(h->pts[1].alloc(h, (size_t)d.nB));
+  TRY(h->params0.alloc(h, (size_t)d.nT));
+  TRY(h->impts.alloc(h, (size_t)2 * d.nO));
+  TRY(h->iidx.alloc(h, (size_t)d.nO));
+  TRY(h->jidx.alloc(h, (size_t)d.nO));
+  TRY(h->W.alloc(h, (size_t)3 * cnp * d.nO));
+  TRY(h->W_alt.alloc(h, (size_t)3 * cnp * d.nO));
+  TRY(h->PV.alloc(h, (size_t)9 * d.nP));
+  TRY(h->PV_alt.alloc(h, (size_t)9 * d.nP));
   // (a point without observations is never written by K1, whose stores come from the last lane of a point's run
   // of observations: its V_i and g_b,i are the zeros put here)
   PSBA_HIP(h, hipMemsetAsync(h->PV, 0, sizeof(double) * 9 * (size_t)d.nP, h->stream));
   PSBA_HIP(h, hipMemsetAsync(h->PV_alt, 0, sizeof(double) * 9 * (size_t)d.nP, h->stream));
-  TRY(dev_alloc(h, &h->U, (size_t)cnp * cnp * d.nC));
-  TRY(dev_alloc(h, &h->U_alt, (size_t)cnp * cnp * d.nC));
-  TRY(dev_alloc(h, &h->ga, (size_t)d.nA));
-  TRY(dev_alloc(h, &h->ga_alt, (size_t)d.nA));
-  h->ahead = h->lin_is_ahead = false;
-  TRY(dev_alloc(h, &h->campart, (h->cam_global || cnp != 6) ? 1 : (size_t)(h->nPart + 1) * d.nC * CAM_ACC));  // (+1: the long points' slab)
-  if (cnp != 6) TRY(dev_alloc(h, &h->camacc, (size_t)d.nC * (cnp * (cnp + 1) / 2 + cnp)));  // kernels_freek.hip: 66 + 11 sums per camera
-  if (h->cam_global) {
-    TRY(dev_alloc(h, &h->camacc, (size_t)d.nC * CAM_ACC));
-    // camera-major index of the observations, cut into segments of at most 256
-    std::vector<int> cptr((size_t)nCams + 1, 0), cobs((size_t)n2Dprojs);
-    for (int a = 0; a < n2Dprojs; a++) cptr[(size_t)jidx[a] + 1]++;
-    for (int j = 0; j < nCams; j++) cptr[(size_t)j + 1] += cptr[j];
-    {
-      std::vector<int> at(cptr.begin(), cptr.end() - 1);
-      for (int a = 0; a < n2Dprojs; a++) cobs[(size_t)at[jidx[a]]++] = a;
-    }
-    std::vector<int4> units;
-    const int LSEG = 256;
-    for (int j = 0; j < nCams; j++)
-      for (int f = cptr[j]; f < cptr[(size_t)j + 1]; f += LSEG)
-        units.push_back(make_int4(j, f, std::min(f + LSEG, cptr[(size_t)j + 1]), 0));
-    h->nCamUnits = (int)units.size();
-    TRY(dev_alloc(h, &h->cam_obs, cobs.size()));
-    TRY(dev_alloc(h, &h->cam_units, units.size()));
-    PSBA_HIP(h, hipMemcpy(h->cam_obs, cobs.data(), sizeof(int) * cobs.size(), hipMemcpyHostToDevice));
-    PSBA_HIP(h, hipMemcpy(h->cam_units, units.data(), sizeof(int4) * units.size(), hipMemcpyHostToDevice));
-  }
-  h->n32 = (d.nA + 31) / 32 * 32;
+  TRY(h->U.alloc(h, (size_t)cnp * cnp * d.nC));
+  TRY(h->U_alt.alloc(h, (size_t)cnp * cnp * d.nC));
+  TRY(h->ga.alloc(h, (size_t)d.nA));
+  TRY(h->ga_alt.alloc(h, (size_t)d.nA));
+  TRY(h->campart.alloc(h, (h->cam_global || cnp != 6) ? 1 : (size_t)(h->nPart + 1) * d.nC * CAM_ACC));  // (+1: the long points' slab)
+  if (cnp != 6) TRY(h->camacc.alloc(h, (size_t)d.nC * (cnp * (cnp + 1) / 2 + cnp)));  // kernels_freek.hip: 66 + 11 sums per camera
+  if (h->cam_global) TRY(h->camacc.alloc(h, (size_t)d.nC * CAM_ACC));
   // rows [0, n32 + 16) are the reduce buffer proper; n32 more rows below it are the working
   // space of the identity rows the panel chain carries along (kernels_chol_graph.hip)
-  const bool sparse = h->solver == PSBA_SOLVER_PCG;  // no dense S, no factor: only the blocks that exist (below)
-  const size_t dense = sparse ? 1 : (size_t)(2 * h->n32 + 16) * h->n32;
-  TRY(dev_alloc(h, &h->red, dense));
+  // (PSBA_SOLVER_PCG: no dense S, no factor -- only the blocks that exist, plan_schur_sparse)
+  const size_t dense = h->solver == PSBA_SOLVER_PCG ? 1 : (size_t)(2 * h->n32 + 16) * h->n32;
+  TRY(h->red.alloc(h, dense));
   PSBA_HIP(h, hipMemsetAsync(h->red, 0, sizeof(double) * dense, h->stream));
-  TRY(dev_alloc(h, &h->dp, (size_t)(d.nT > 36 * d.nC ? d.nT : 36 * d.nC)));
-  TRY(dev_alloc(h, &h->chol_ws, (size_t)((d.nA + 31) / 32) * 1024));
-  TRY(dev_alloc(h, &h->chol_L, dense));
+  TRY(h->dp.alloc(h, (size_t)(d.nT > 36 * d.nC ? d.nT : 36 * d.nC)));
+  PSBA_HIP(h, hipMemsetAsync(h->dp, 0, sizeof(double) * d.nT, h->stream));
+  TRY(h->chol_ws.alloc(h, (size_t)((d.nA + 31) / 32) * 1024));
+  TRY(h->chol_L.alloc(h, dense));
   PSBA_HIP(h, hipMemsetAsync(h->chol_L, 0, sizeof(double) * dense, h->stream));
-  if (getenv("PSBA_CHOL_TIMING") && !h->chol_tim) TRY(dev_alloc(h, &h->chol_tim, 32));  // [0..15] diag kernel + pivot wave, [16..31] inverse wave
-  // ---- K2's static schedule (groups of blocks, workgroups, conflict-free item rows) ----
-  if (sparse) {
-    // block-sparse S: the owner route's product lists give the blocks that exist
-    OwnerPlanHost op;
-    // sharded points: every rank must hold the same block list, the union of what the ranks' points
-    // produce -- one byte per block of the lower triangle, combined with a max all-reduce over the
-    // communicator, or handed in by a host that has its own transport (psba_set_sparse_pattern)
-    std::vector<unsigned char> pat;
-    // (PSBA_SPARSE_PATTERN_FORCE=1: test hook -- a one-rank communicator exchanges its pattern too)
-    if (h->nranks > 1 || (h->comm && getenv("PSBA_SPARSE_PATTERN_FORCE"))) {
-      const size_t nBlk = (size_t)nCams * (nCams + 1) / 2;
-      if (h->comm) {
-        pat.resize(nBlk);
-        TRY(sparse_pattern(nCams, n2Dprojs, iidx, jidx, ptr.data(), pat.data()));
-        unsigned char *dev = nullptr;
-        PSBA_HIP(h, hipMalloc((void **)&dev, nBlk));
-        hipError_t e1 = hipMemcpyAsync(dev, pat.data(), nBlk, hipMemcpyHostToDevice, h->stream);
-        ncclResult_t e2 = e1 == hipSuccess ? ncclAllReduce(dev, dev, nBlk, ncclUint8, ncclMax, h->comm, h->stream) : ncclSuccess;
-        if (e1 == hipSuccess && e2 == ncclSuccess) e1 = hipMemcpyAsync(pat.data(), dev, nBlk, hipMemcpyDeviceToHost, h->stream);
-        if (e1 == hipSuccess && e2 == ncclSuccess) e1 = hipStreamSynchronize(h->stream);
-        (void)hipFree(dev);
-        if (e2 != ncclSuccess) return fail(h, PSBA_E_RCCL, "all-reduce of the block pattern: %s", ncclGetErrorString(e2));
-        PSBA_HIP(h, e1);
-      } else {
-        if (h->bs_pattern.size() != nBlk)
-          return fail(h, PSBA_E_STATE, "PSBA_SOLVER_PCG with a rank layout and no communicator: psba_set_sparse_pattern "
-                                       "(the union of psba_sparse_pattern over the ranks) before psba_upload_problem");
-        pat = h->bs_pattern;
-      }
-    }
-    TRY(build_owner_plan(nCams, n2Dprojs, iidx, jidx, ptr.data(), op, pat.empty() ? nullptr : pat.data()));
-    h->nGroups = 0;
-    h->packedN = 36 * (size_t)nCams * (nCams + 1) / 2;
-    TRY(dev_alloc(h, &h->own_prod, op.prod.size()));
-    TRY(dev_alloc(h, &h->own_waves, op.waves.size()));
-    TRY(dev_alloc(h, &h->own_units, op.units.size()));
-    PSBA_HIP(h, hipMemcpy(h->own_prod, op.prod.data(), sizeof(int2) * op.prod.size(), hipMemcpyHostToDevice));
-    PSBA_HIP(h, hipMemcpy(h->own_waves, op.waves.data(), sizeof(OwnerWave) * op.waves.size(), hipMemcpyHostToDevice));
-    PSBA_HIP(h, hipMemcpy(h->own_units, op.units.data(), sizeof(OwnerUnit) * op.units.size(), hipMemcpyHostToDevice));
-    h->own_nwaves = (int)op.waves.size();
-    h->own_products = op.products;
-    h->bs_nblk = (long long)op.blocks.size();
-    TRY(dev_alloc(h, &h->bs_val, (size_t)36 * op.blocks.size() + (size_t)d.nA));
-    h->bs_ea = h->bs_val + (size_t)36 * op.blocks.size();
-    TRY(dev_alloc(h, &h->bs_jk, op.blocks.size()));
-    TRY(dev_alloc(h, &h->bs_diag, op.diag_slot.size()));
-    PSBA_HIP(h, hipMemcpy(h->bs_jk, op.blocks.data(), sizeof(int2) * op.blocks.size(), hipMemcpyHostToDevice));
-    PSBA_HIP(h, hipMemcpy(h->bs_diag, op.diag_slot.data(), sizeof(int) * op.diag_slot.size(), hipMemcpyHostToDevice));
-    {  // the symmetric pattern by block row (kernels_pcg.hip, k_pcg_spmv)
-      std::vector<int> rp((size_t)nCams + 1, 0);
-      for (const int2 &b : op.blocks) {
-        rp[(size_t)b.x + 1]++;
-        if (b.x != b.y) rp[(size_t)b.y + 1]++;
-      }
-      for (int j = 0; j < nCams; j++) rp[(size_t)j + 1] += rp[(size_t)j];
-      std::vector<int2> ent((size_t)rp[(size_t)nCams]);
-      std::vector<int> at(rp.begin(), rp.end() - 1);
-      for (size_t sl = 0; sl < op.blocks.size(); sl++) {
-        const int2 b = op.blocks[sl];
-        if (b.x == b.y) {
-          ent[(size_t)at[(size_t)b.x]++] = make_int2((int)sl, b.x | (2 << 28));
-        } else {
-          ent[(size_t)at[(size_t)b.x]++] = make_int2((int)sl, b.y);
-          ent[(size_t)at[(size_t)b.y]++] = make_int2((int)sl, b.x | (1 << 28));
-        }
-      }
-      TRY(dev_alloc(h, &h->bs_rowptr, rp.size()));
-      TRY(dev_alloc(h, &h->bs_rowent, ent.size()));
-      PSBA_HIP(h, hipMemcpy(h->bs_rowptr, rp.data(), sizeof(int) * rp.size(), hipMemcpyHostToDevice));
-      PSBA_HIP(h, hipMemcpy(h->bs_rowent, ent.data(), sizeof(int2) * ent.size(), hipMemcpyHostToDevice));
-    }
-    TRY(dev_alloc(h, &h->pcg_vec, (size_t)5 * d.nA));  // r, z, p, q, and r's second buffer
-    TRY(dev_alloc(h, &h->pcg_minv, (size_t)36 * d.nC));
-    TRY(dev_alloc(h, &h->pcg_scal, (size_t)(16 + 4 * 64)));  // scalars + the partial sums of p.Sp (kernels_pcg.hip)
-    if (!h->pcg_host && hipHostMalloc((void **)&h->pcg_host, sizeof(double) * 16) != hipSuccess)
-      return fail(h, PSBA_E_NOMEM, "no pinned memory for the PCG scalars");
-    if (getenv("PSBA_SCHUR_PLAN_INFO"))
-      fprintf(stderr, "[psba] block-sparse S: %lld of %lld blocks of the lower block triangle (%.1f %%), %lld products\n",
-              h->bs_nblk, (long long)nCams * (nCams + 1) / 2, 100.0 * (double)h->bs_nblk / ((double)nCams * (nCams + 1) / 2),
-              op.products);
+  if (getenv("PSBA_CHOL_TIMING")) TRY(h->chol_tim.alloc(h, 32));  // [0..15] diag kernel + pivot wave, [16..31] inverse wave
+  return PSBA_OK;
+}
+
+// camera-major index of the observations, cut into segments of at most 256 (K1's camera sums with many cameras)
+static int upload_camera_index(psba_ctx *h, const Upload &u) {
+  std::vector<int> cptr((size_t)u.nC + 1, 0), cobs((size_t)u.nO);
+  for (int a = 0; a < u.nO; a++) cptr[(size_t)u.jidx[a] + 1]++;
+  for (int j = 0; j < u.nC; j++) cptr[(size_t)j + 1] += cptr[j];
+  {
+    std::vector<int> at(cptr.begin(), cptr.end() - 1);
+    for (int a = 0; a < u.nO; a++) cobs[(size_t)at[u.jidx[a]]++] = a;
   }
-#ifdef PSBA_BUILD_EXPERIMENTS
-  if (!sparse) {
-    RingPlanHost rp;
-    TRY(build_ring_plan(nCams, n3Dpts, n2Dprojs, iidx, jidx, ptr.data(), rp));
-    if (rp.nWg > 0) {
-      h->packedN = 36 * (size_t)nCams * (nCams + 1) / 2;
-      h->nGroups = 0;
-      h->ring_nWg = rp.nWg;
-      h->ring_nS = rp.nS;
-      h->ring_products = rp.products;
-      h->ring_slots = rp.slots;
-      h->ring_loaded_recs = (size_t)rp.loaded_recs;
-      std::vector<int> canon;
-      for (int j = 0; j < nCams; j++)
-        for (int k = 0; k <= j; k++) canon.push_back((j << 16) | k);
-      auto up = [&](auto **dst, const auto &v) -> int {
-        TRY(dev_alloc(h, dst, v.size() ? v.size() : 1));
-        if (v.size()) PSBA_HIP(h, hipMemcpy(*dst, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice));
-        return PSBA_OK;
-      };
-      TRY(up(&h->ring_wg, rp.wgs));
-      TRY(up(&h->ring_steps, rp.steps));
-      TRY(up(&h->ring_entries, rp.entries));
-      TRY(up(&h->ring_ops, rp.ops));
-      TRY(up(&h->ring_jobs, rp.jobs));
-      TRY(up(&h->ring_bl0, rp.blk_lane0));
-      TRY(up(&h->ring_canon, canon));
-      TRY(dev_alloc(h, &h->ring_slab, (size_t)rp.nS * h->packedN));
-      TRY(dev_alloc(h, &h->ring_pvi, (size_t)9 * n3Dpts + 2));
-      h->packed_doubles = h->packedN;
-      TRY(dev_alloc(h, &h->redp, h->packed_doubles));
-      if (getenv("PSBA_SCHUR_PLAN_INFO")) {
-        long long steps_max = 0;
-        for (const auto &w : rp.wgs) steps_max = w.nsteps > steps_max ? w.nsteps : steps_max;
-        fprintf(stderr, "[psba] K2 ring route: %d block ranges x %d stretches, %lld products in %lld lane-steps (fill %.3f), "
-                        "%lld record loads (%.2f per observation), %zu jobs, steps <= %lld, lists %.1f MB, copies %.1f MB\n",
-                rp.nR, rp.nS, rp.products, rp.slots, rp.slots ? (double)rp.products / (double)rp.slots : 1.0,
-                rp.loaded_recs, (double)rp.loaded_recs / n2Dprojs, rp.jobs.size(), steps_max,
-                1e-6 * (4.0 * rp.entries.size() + 4.0 * rp.ops.size() + 16.0 * rp.jobs.size() + 16.0 * rp.steps.size()),
-                8e-6 * (double)rp.nS * (double)h->packedN);
-      }
-    }
+  std::vector<int4> units;
+  const int LSEG = 256;
+  for (int j = 0; j < u.nC; j++)
+    for (int f = cptr[j]; f < cptr[(size_t)j + 1]; f += LSEG)
+      units.push_back(make_int4(j, f, std::min(f + LSEG, cptr[(size_t)j + 1]), 0));
+  h->nCamUnits = (int)units.size();
+  TRY(upload(h, h->cam_obs, cobs));
+  return upload(h, h->cam_units, units);
+}
+
+// ---- K2's static schedule: one of the routes below per problem (psba_schur_path) ----
+
+// the owner route's product lists (many cameras; with PSBA_SOLVER_PCG they also give the blocks that exist)
+static int upload_owner_plan(psba_ctx *h, const OwnerPlanHost &op) {
+  TRY(upload(h, h->own_prod, op.prod));
+  TRY(upload(h, h->own_waves, op.waves));
+  TRY(upload(h, h->own_units, op.units));
+  h->own_nwaves = (int)op.waves.size();
+  h->own_products = op.products;
+  return PSBA_OK;
+}
+
+// sharded points: every rank must hold the same block list, the union of what the ranks' points
+// produce -- one byte per block of the lower triangle, combined with a max all-reduce over the
+// communicator, or handed in by a host that has its own transport (psba_set_sparse_pattern).
+// pat stays empty where this rank's own blocks are the list
+static int shared_block_pattern(psba_ctx *h, const Upload &u, std::vector<unsigned char> &pat) {
+  // (PSBA_SPARSE_PATTERN_FORCE=1: test hook -- a one-rank communicator exchanges its pattern too)
+  if (!(h->nranks > 1 || (h->comm && getenv("PSBA_SPARSE_PATTERN_FORCE")))) return PSBA_OK;
+  const size_t nBlk = (size_t)u.nC * (u.nC + 1) / 2;
+  if (!h->comm) {
+    if (h->bs_pattern.size() != nBlk)
+      return fail(h, PSBA_E_STATE, "PSBA_SOLVER_PCG with a rank layout and no communicator: psba_set_sparse_pattern "
+                                   "(the union of psba_sparse_pattern over the ranks) before psba_upload_problem");
+    pat = h->bs_pattern;
+    return PSBA_OK;
   }
-#endif
-  if (cnp != 6) {
-    h->nGroups = 0;  // the free-intrinsics route needs no schedule (global atomics straight into S)
-  } else if (!sparse && !h->ring_nWg) {
-    SchurPlanHost plan;
-    TRY(build_schur_plan(h, nCams, n3Dpts, n2Dprojs, iidx, jidx, ptr.data(), plan));
-    h->schur_runs = h->nGroups > 0 && plan.runs;
-    h->schur_pairs = h->nGroups > 0 && plan.pair_items > 0;
-    if (h->nGroups) {
-      TRY(dev_alloc(h, &h->items, plan.items.size() ? plan.items.size() : 1));
-      TRY(dev_alloc(h, &h->wg, plan.wgs.size()));
-      TRY(dev_alloc(h, &h->posblock, plan.posblock.size()));
-      TRY(dev_alloc(h, &h->slab, plan.slab_doubles));
-      PSBA_HIP(h, hipMemcpy(h->items, plan.items.data(), sizeof(unsigned long long) * plan.items.size(), hipMemcpyHostToDevice));
-      PSBA_HIP(h, hipMemcpy(h->wg, plan.wgs.data(), sizeof(SchurWg) * plan.wgs.size(), hipMemcpyHostToDevice));
-      PSBA_HIP(h, hipMemcpy(h->posblock, plan.posblock.data(), sizeof(int) * plan.posblock.size(), hipMemcpyHostToDevice));
-      for (int j = 0, b = 0; j < 6; j++)
-        for (int k = 0; k <= j; k++, b++) {
-          h->h_diagpos[b] = j < nCams ? plan.blockpos[(size_t)b] : 0;
-          int g = -1;
-          if (j < nCams)
-            for (g = 0; b >= h->gblk0[g + 1];) g++;
-          h->h_diaggrp[b] = g;
-        }
-      {
-        std::vector<ReduceGroup> tab;
-        long long pos0 = 0;
-        for (int g = 0; g < h->nGroups; g++) {
-          tab.insert(tab.end(), (size_t)h->gnblk[g] / 16, ReduceGroup{h->gnwg[g], h->gnblk[g], pos0, h->gslab[g], 0});
-          pos0 += h->gnblk[g];
-        }
-        TRY(dev_alloc(h, &h->gtab, tab.size()));
-        PSBA_HIP(h, hipMemcpy(h->gtab, tab.data(), sizeof(ReduceGroup) * tab.size(), hipMemcpyHostToDevice));
-      }
-      h->packed_doubles = h->packedN;  // 36 doubles per block of the lower block triangle, canonical order
-      TRY(dev_alloc(h, &h->redp, h->packed_doubles));
-      TRY(dev_alloc(h, &h->diag0, (size_t)21 * 36));
-      PSBA_HIP(h, hipMemsetAsync(h->diag0, 0, sizeof(double) * 21 * 36, h->stream));
-      if (getenv("PSBA_SCHUR_PLAN_INFO"))
-        fprintf(stderr, "[psba] K2 plan%s: %d groups, %d workgroups, %lld products in %zu item slots (fill %.3f), slabs %.1f MB\n",
-                plan.runs ? " (runs layout)" : "", h->nGroups, h->nWg, plan.real_items, plan.items.size(),
-                plan.items.size() ? (double)plan.real_items / (double)plan.items.size() : 1.0,
-                8e-6 * (double)plan.slab_doubles);
+  pat.resize(nBlk);
+  TRY(sparse_pattern(u.nC, u.nO, u.iidx, u.jidx, u.ptr.data(), pat.data()));
+  DevBuf<unsigned char> dev;
+  TRY(dev.alloc(h, nBlk));
+  PSBA_HIP(h, hipMemcpyAsync(dev, pat.data(), nBlk, hipMemcpyHostToDevice, h->stream));
+  RCCL(h, ncclAllReduce(dev, dev, nBlk, ncclUint8, ncclMax, h->comm, h->stream));
+  PSBA_HIP(h, hipMemcpyAsync(pat.data(), dev, nBlk, hipMemcpyDeviceToHost, h->stream));
+  PSBA_HIP(h, hipStreamSynchronize(h->stream));
+  return PSBA_OK;
+}
+
+// the symmetric pattern by block row (kernels_pcg.hip, k_pcg_spmv)
+static int upload_bsr_rows(psba_ctx *h, const OwnerPlanHost &op) {
+  const int nC = h->d.nC;
+  std::vector<int> rp((size_t)nC + 1, 0);
+  for (const int2 &b : op.blocks) {
+    rp[(size_t)b.x + 1]++;
+    if (b.x != b.y) rp[(size_t)b.y + 1]++;
+  }
+  for (int j = 0; j < nC; j++) rp[(size_t)j + 1] += rp[(size_t)j];
+  std::vector<int2> ent((size_t)rp[(size_t)nC]);
+  std::vector<int> at(rp.begin(), rp.end() - 1);
+  for (size_t sl = 0; sl < op.blocks.size(); sl++) {
+    const int2 b = op.blocks[sl];
+    if (b.x == b.y) {
+      ent[(size_t)at[(size_t)b.x]++] = make_int2((int)sl, b.x | (2 << 28));
     } else {
-      // many cameras: the owner route (one thread per block segment, sums in registers)
-      OwnerPlanHost op;
-      TRY(build_owner_plan(nCams, n2Dprojs, iidx, jidx, ptr.data(), op));
-      TRY(dev_alloc(h, &h->own_prod, op.prod.size()));
-      TRY(dev_alloc(h, &h->own_waves, op.waves.size()));
-      TRY(dev_alloc(h, &h->own_units, op.units.size()));
-      PSBA_HIP(h, hipMemcpy(h->own_prod, op.prod.data(), sizeof(int2) * op.prod.size(), hipMemcpyHostToDevice));
-      PSBA_HIP(h, hipMemcpy(h->own_waves, op.waves.data(), sizeof(OwnerWave) * op.waves.size(), hipMemcpyHostToDevice));
-      PSBA_HIP(h, hipMemcpy(h->own_units, op.units.data(), sizeof(OwnerUnit) * op.units.size(), hipMemcpyHostToDevice));
-      h->own_nwaves = (int)op.waves.size();
-      h->own_products = op.products;
-      if (getenv("PSBA_SCHUR_PLAN_INFO"))
-        // no silent cliff: say which route K2 takes (psba_schur_path returns the same)
-        fprintf(stderr, "[psba] K2 owner route (%d cameras): %lld products in %zu ELL slots (fill %.3f), %d waves\n",
-                nCams, op.products, op.prod.size(), (double)op.products / (double)op.prod.size(), h->own_nwaves);
+      ent[(size_t)at[(size_t)b.x]++] = make_int2((int)sl, b.y);
+      ent[(size_t)at[(size_t)b.y]++] = make_int2((int)sl, b.x | (1 << 28));
     }
+  }
+  TRY(upload(h, h->bs_rowptr, rp));
+  return upload(h, h->bs_rowent, ent);
+}
+
+// block-sparse S (PSBA_SOLVER_PCG): the owner route's product lists give the blocks that exist
+static int plan_schur_sparse(psba_ctx *h, const Upload &u) {
+  const Dims &d = h->d;
+  std::vector<unsigned char> pat;
+  TRY(shared_block_pattern(h, u, pat));
+  OwnerPlanHost op;
+  TRY(build_owner_plan(u.nC, u.nO, u.iidx, u.jidx, u.ptr.data(), op, pat.empty() ? nullptr : pat.data()));
+  h->packedN = 36 * (size_t)u.nC * (u.nC + 1) / 2;
+  TRY(upload_owner_plan(h, op));
+  h->bs_nblk = (long long)op.blocks.size();
+  TRY(h->bs_val.alloc(h, (size_t)36 * op.blocks.size() + (size_t)d.nA));
+  h->bs_ea = h->bs_val + (size_t)36 * op.blocks.size();
+  TRY(upload(h, h->bs_jk, op.blocks));
+  TRY(upload(h, h->bs_diag, op.diag_slot));
+  TRY(upload_bsr_rows(h, op));
+  TRY(h->pcg_vec.alloc(h, (size_t)5 * d.nA));  // r, z, p, q, and r's second buffer
+  TRY(h->pcg_minv.alloc(h, (size_t)36 * d.nC));
+  TRY(h->pcg_scal.alloc(h, (size_t)(16 + 4 * 64)));  // scalars + the partial sums of p.Sp (kernels_pcg.hip)
+  if (!h->pcg_host) TRY(h->pcg_host.alloc(h, 16));
+  if (getenv("PSBA_SCHUR_PLAN_INFO"))
+    fprintf(stderr, "[psba] block-sparse S: %lld of %lld blocks of the lower block triangle (%.1f %%), %lld products\n",
+            h->bs_nblk, (long long)u.nC * (u.nC + 1) / 2, 100.0 * (double)h->bs_nblk / ((double)u.nC * (u.nC + 1) / 2),
+            op.products);
+  return PSBA_OK;
+}
+
+#ifdef PSBA_BUILD_EXPERIMENTS
+// the ring route (few cameras): taken where build_ring_plan finds it worth it (ring_nWg > 0 afterwards)
+static int plan_schur_ring(psba_ctx *h, const Upload &u) {
+  RingPlanHost rp;
+  TRY(build_ring_plan(u.nC, u.nP, u.nO, u.iidx, u.jidx, u.ptr.data(), rp));
+  if (rp.nWg <= 0) return PSBA_OK;
+  h->packedN = 36 * (size_t)u.nC * (u.nC + 1) / 2;
+  h->ring_nWg = rp.nWg;
+  h->ring_nS = rp.nS;
+  h->ring_products = rp.products;
+  h->ring_slots = rp.slots;
+  h->ring_loaded_recs = (size_t)rp.loaded_recs;
+  std::vector<int> canon;
+  for (int j = 0; j < u.nC; j++)
+    for (int k = 0; k <= j; k++) canon.push_back((j << 16) | k);
+  TRY(upload(h, h->ring_wg, rp.wgs));
+  TRY(upload(h, h->ring_steps, rp.steps));
+  TRY(upload(h, h->ring_entries, rp.entries));
+  TRY(upload(h, h->ring_ops, rp.ops));
+  TRY(upload(h, h->ring_jobs, rp.jobs));
+  TRY(upload(h, h->ring_bl0, rp.blk_lane0));
+  TRY(upload(h, h->ring_canon, canon));
+  TRY(h->ring_slab.alloc(h, (size_t)rp.nS * h->packedN));
+  TRY(h->ring_pvi.alloc(h, (size_t)9 * u.nP + 2));
+  h->packed_doubles = h->packedN;
+  TRY(h->redp.alloc(h, h->packed_doubles));
+  if (getenv("PSBA_SCHUR_PLAN_INFO")) {
+    long long steps_max = 0;
+    for (const auto &w : rp.wgs) steps_max = w.nsteps > steps_max ? w.nsteps : steps_max;
+    fprintf(stderr, "[psba] K2 ring route: %d block ranges x %d stretches, %lld products in %lld lane-steps (fill %.3f), "
+                    "%lld record loads (%.2f per observation), %zu jobs, steps <= %lld, lists %.1f MB, copies %.1f MB\n",
+            rp.nR, rp.nS, rp.products, rp.slots, rp.slots ? (double)rp.products / (double)rp.slots : 1.0,
+            rp.loaded_recs, (double)rp.loaded_recs / u.nO, rp.jobs.size(), steps_max,
+            1e-6 * (4.0 * rp.entries.size() + 4.0 * rp.ops.size() + 16.0 * rp.jobs.size() + 16.0 * rp.steps.size()),
+            8e-6 * (double)rp.nS * (double)h->packedN);
+  }
+  return PSBA_OK;
+}
+#endif
+
+// the LDS route (groups of blocks, workgroups, conflict-free item rows), or, where build_schur_plan finds no
+// partition of S that fits (nGroups = 0: many cameras), the owner route
+static int plan_schur_lds(psba_ctx *h, const Upload &u) {
+  SchurPlanHost plan;
+  TRY(build_schur_plan(h, u.nC, u.nP, u.nO, u.iidx, u.jidx, u.ptr.data(), plan));
+  if (!h->nGroups) {
+    // many cameras: the owner route (one thread per block segment, sums in registers)
+    OwnerPlanHost op;
+    TRY(build_owner_plan(u.nC, u.nO, u.iidx, u.jidx, u.ptr.data(), op));
+    TRY(upload_owner_plan(h, op));
+    if (getenv("PSBA_SCHUR_PLAN_INFO"))
+      // no silent cliff: say which route K2 takes (psba_schur_path returns the same)
+      fprintf(stderr, "[psba] K2 owner route (%d cameras): %lld products in %zu ELL slots (fill %.3f), %d waves\n",
+              u.nC, op.products, op.prod.size(), (double)op.products / (double)op.prod.size(), h->own_nwaves);
+    return PSBA_OK;
+  }
+  h->schur_runs = plan.runs;
+  h->schur_pairs = plan.pair_items > 0;
+  TRY(upload(h, h->items, plan.items));
+  TRY(upload(h, h->wg, plan.wgs));
+  TRY(upload(h, h->posblock, plan.posblock));
+  TRY(h->slab.alloc(h, plan.slab_doubles));
+  for (int j = 0, b = 0; j < 6; j++)
+    for (int k = 0; k <= j; k++, b++) {
+      h->h_diagpos[b] = j < u.nC ? plan.blockpos[(size_t)b] : 0;
+      int g = -1;
+      if (j < u.nC)
+        for (g = 0; b >= h->gblk0[g + 1];) g++;
+      h->h_diaggrp[b] = g;
+    }
+  std::vector<ReduceGroup> tab;
+  long long pos0 = 0;
+  for (int g = 0; g < h->nGroups; g++) {
+    tab.insert(tab.end(), (size_t)h->gnblk[g] / 16, ReduceGroup{h->gnwg[g], h->gnblk[g], pos0, h->gslab[g], 0});
+    pos0 += h->gnblk[g];
+  }
+  TRY(upload(h, h->gtab, tab));
+  h->packed_doubles = h->packedN;  // 36 doubles per block of the lower block triangle, canonical order
+  TRY(h->redp.alloc(h, h->packed_doubles));
+  TRY(h->diag0.alloc(h, (size_t)21 * 36));
+  PSBA_HIP(h, hipMemsetAsync(h->diag0, 0, sizeof(double) * 21 * 36, h->stream));
+  if (getenv("PSBA_SCHUR_PLAN_INFO"))
+    fprintf(stderr, "[psba] K2 plan%s: %d groups, %d workgroups, %lld products in %zu item slots (fill %.3f), slabs %.1f MB\n",
+            plan.runs ? " (runs layout)" : "", h->nGroups, h->nWg, plan.real_items, plan.items.size(),
+            plan.items.size() ? (double)plan.real_items / (double)plan.items.size() : 1.0,
+            8e-6 * (double)plan.slab_doubles);
+  return PSBA_OK;
+}
+
+static int plan_schur(psba_ctx *h, const Upload &u) {
+  if (h->solver == PSBA_SOLVER_PCG) return plan_schur_sparse(h, u);
+#ifdef PSBA_BUILD_EXPERIMENTS
+  TRY(plan_schur_ring(h, u));
+  if (h->ring_nWg) return PSBA_OK;
+#endif
+  if (h->cnp != 6) return PSBA_OK;  // the free-intrinsics route needs no schedule (global atomics straight into S)
+  return plan_schur_lds(h, u);
+}
+
+// the caller's arrays and the index tables derived from them, to the device
+static int copy_inputs(psba_ctx *h, const Upload &u) {
+  const Dims &d = h->d;
+  std::vector<double> cc((size_t)u.nC * 9);
+  for (int j = 0; j < u.nC; j++) {
+    for (int k = 0; k < 5; k++) cc[(size_t)9 * j + k] = u.Kparas[5 * j + k];
+    for (int k = 0; k < 4; k++) cc[(size_t)9 * j + 5 + k] = u.initrot[4 * j + k];
+  }
+  TRY(upload(h, h->camconst, cc));
+  TRY(upload(h, h->ptr, u.ptr));
+  TRY(upload(h, h->tile_pt, u.tile_pt));
+  if (h->nLong) TRY(upload(h, h->long_pts, u.long_pts));
+  std::vector<int4> tile_desc;
+  for (int t = 0; t < d.nTilesAll; t++)
+    if (u.ptr[u.tile_pt[t + 1]] - u.ptr[u.tile_pt[t]] <= TILE_OBS)
+      tile_desc.push_back(make_int4(u.tile_pt[t], u.tile_pt[t + 1], u.ptr[u.tile_pt[t]], u.ptr[u.tile_pt[t + 1]]));
+  if (tile_desc.empty()) tile_desc.push_back(make_int4(0, 0, 0, 0));  // (only long points: an empty tile keeps the grids non-empty)
+  TRY(upload(h, h->tile_desc, tile_desc));
+  const double *cams = u.camsEx;
+  std::vector<double> cam11;  // free intrinsics: the camera block is (K | local rotation | translation)
+  if (h->cnp != 6) {
+    cam11.resize((size_t)d.nA);
+    for (int j = 0; j < u.nC; j++) {
+      for (int k = 0; k < 5; k++) cam11[(size_t)h->cnp * j + k] = u.Kparas[5 * j + k];
+      for (int k = 0; k < 6; k++) cam11[(size_t)h->cnp * j + 5 + k] = u.camsEx[6 * j + k];
+    }
+    cams = cam11.data();
   }
   auto H2D = [&](void *dst, const void *src, size_t bytes) {
     return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
   };
-  PSBA_HIP(h, H2D(h->camconst, cc.data(), sizeof(double) * cc.size()));
-  std::vector<double> cam11;  // free intrinsics: the camera block is (K | local rotation | translation)
-  if (cnp != 6) {
-    cam11.resize((size_t)d.nA);
-    for (int j = 0; j < nCams; j++) {
-      for (int k = 0; k < 5; k++) cam11[(size_t)cnp * j + k] = Kparas[5 * j + k];
-      for (int k = 0; k < 6; k++) cam11[(size_t)cnp * j + 5 + k] = camsEx[6 * j + k];
-    }
-    camsEx = cam11.data();
-  }
-  PSBA_HIP(h, H2D(h->cams[0], camsEx, sizeof(double) * d.nA));
-  PSBA_HIP(h, H2D(h->pts[0], pts3D, sizeof(double) * d.nB));
-  PSBA_HIP(h, H2D(h->params0, camsEx, sizeof(double) * d.nA));
-  PSBA_HIP(h, H2D(h->params0 + d.nA, pts3D, sizeof(double) * d.nB));
-  PSBA_HIP(h, H2D(h->impts, impts, sizeof(double) * 2 * (size_t)d.nO));
-  PSBA_HIP(h, H2D(h->iidx, iidx, sizeof(int) * (size_t)d.nO));
-  PSBA_HIP(h, H2D(h->jidx, jidx, sizeof(int) * (size_t)d.nO));
-  PSBA_HIP(h, H2D(h->ptr, ptr.data(), sizeof(int) * ptr.size()));
-  PSBA_HIP(h, H2D(h->tile_pt, tile_pt.data(), sizeof(int) * tile_pt.size()));
-  std::vector<int4> tile_desc;
-  for (int t = 0; t < d.nTilesAll; t++)
-    if (ptr[tile_pt[t + 1]] - ptr[tile_pt[t]] <= TILE_OBS)
-      tile_desc.push_back(make_int4(tile_pt[t], tile_pt[t + 1], ptr[tile_pt[t]], ptr[tile_pt[t + 1]]));
-  if (tile_desc.empty()) tile_desc.push_back(make_int4(0, 0, 0, 0));  // (only long points: an empty tile keeps the grids non-empty)
-  PSBA_HIP(h, hipMemcpy(h->tile_desc, tile_desc.data(), sizeof(int4) * tile_desc.size(), hipMemcpyHostToDevice));
-  PSBA_HIP(h, hipMemsetAsync(h->dp, 0, sizeof(double) * d.nT, h->stream));
+  PSBA_HIP(h, H2D(h->cams[0], cams, sizeof(double) * d.nA));
+  PSBA_HIP(h, H2D(h->pts[0], u.pts3D, sizeof(double) * d.nB));
+  PSBA_HIP(h, H2D(h->params0, cams, sizeof(double) * d.nA));
+  PSBA_HIP(h, H2D(h->params0 + d.nA, u.pts3D, sizeof(double) * d.nB));
+  PSBA_HIP(h, H2D(h->impts, u.impts, sizeof(double) * 2 * (size_t)d.nO));
+  PSBA_HIP(h, H2D(h->iidx, u.iidx, sizeof(int) * (size_t)d.nO));
+  PSBA_HIP(h, H2D(h->jidx, u.jidx, sizeof(int) * (size_t)d.nO));
   PSBA_HIP(h, hipStreamSynchronize(h->stream));  // host vectors go out of scope
-  // ... and the blocking copies above went through the null stream, which this handle's non-blocking stream does
-  // not wait for: everything on the device is done before the first kernel can be queued
+  return PSBA_OK;
+}
+
+int psba_upload_problem(psba_handle h, int nCams, int n3Dpts, int n2Dprojs, const double *Kparas,
+                        const double *impts, const double *initrot, const double *camsEx,
+                        const double *pts3D, const int *iidx, const int *jidx) {
+  CHECK_H(h);
+  Upload u{nCams, n3Dpts, n2Dprojs, Kparas, impts, initrot, camsEx, pts3D, iidx, jidx};
+  TRY(build_point_csr(h, u));
+  cut_tiles(u);
+  PSBA_HIP(h, hipSetDevice(h->device));
+  drop_problem(h);  // from here on the handle holds no problem until this upload has succeeded
+  set_dims(h, u);
+  TRY(alloc_work_buffers(h));
+  if (h->cam_global) TRY(upload_camera_index(h, u));
+  TRY(plan_schur(h, u));
+  TRY(copy_inputs(h, u));
+  // the blocking copies went through the null stream, which this handle's non-blocking stream does not wait for:
+  // everything on the device is done before the first kernel can be queued
   PSBA_HIP(h, hipDeviceSynchronize());
   h->uploaded = true;
   return PSBA_OK;
@@ -937,10 +882,9 @@ static int enqueue_max_diag(psba_ctx *h) {
     PSBA_HIP(h, hipMemcpyAsync(tmp, h->U, sizeof(double) * 36 * h->d.nC, hipMemcpyDeviceToDevice,
                                h->stream));
     RCCL(h, ncclAllReduce(tmp, tmp, (size_t)36 * h->d.nC, ncclDouble, ncclSum, h->comm, h->stream));
-    double *keep = h->U;
-    h->U = tmp;
+    std::swap(h->U, h->dp);  // (the launcher reads h->U)
     int rc = launch_max_diag(h);
-    h->U = keep;
+    std::swap(h->U, h->dp);
     TRY(rc);
     RCCL(h, ncclAllReduce(h->scal + SC_MAXDIAG, h->scal + SC_MAXDIAG, 1, ncclDouble, ncclMax,
                           h->comm, h->stream));
@@ -1233,7 +1177,7 @@ int psba_chol_dist_block(psba_handle h, int B, int set, double *buf, long long *
   const long long n = (long long)(h->n32 + 1 - 64 * B) * ncols;
   if (n_doubles) *n_doubles = n;
   if (!buf) return PSBA_OK;
-  if (!h->dist_buf) TRY(dev_alloc(h, &h->dist_buf, (size_t)(h->n32 + 1) * 64 * 8));
+  if (!h->dist_buf) TRY(h->dist_buf.alloc(h, (size_t)(h->n32 + 1) * 64 * 8));
   if (set) {
     PSBA_HIP(h, hipMemcpyAsync(h->dist_buf, buf, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream));
     return chol_dist_block(h, B, h->dist_buf, 1);
@@ -1252,7 +1196,7 @@ int psba_chol_dist_finish(psba_handle h) {
 
 static int ensure_trv(psba_ctx *h) {
   for (int k = 0; k < 2; k++)
-    if (!h->trv[k]) TRY(dev_alloc(h, &h->trv[k], (size_t)h->d.nT));
+    if (!h->trv[k]) TRY(h->trv[k].alloc(h, (size_t)h->d.nT));
   return PSBA_OK;
 }
 
@@ -1357,7 +1301,7 @@ int psba_compute_Jmultiply(psba_handle h, const double *x, double *Jmul) {
   NEED(h, h->uploaded, "no problem uploaded");
   if (!x) return fail(h, PSBA_E_INVALID, "psba_compute_Jmultiply: null pointer");
   TRY(ensure_trv(h));
-  if (!h->jmul_out) TRY(dev_alloc(h, &h->jmul_out, (size_t)2 * h->d.nO));
+  if (!h->jmul_out) TRY(h->jmul_out.alloc(h, (size_t)2 * h->d.nO));
   PSBA_HIP(h, hipMemcpyAsync(h->trv[0], x, sizeof(double) * (size_t)h->d.nT, hipMemcpyHostToDevice, h->stream));
   TRY(launch_jmul(h, h->trv[0], h->trv[0], h->jmul_out, h->scal + SC_TR_DOTS));
   return d2h(h, Jmul, h->jmul_out, sizeof(double) * 2 * (size_t)h->d.nO);
@@ -1444,12 +1388,12 @@ int psba_cholmod_lambda(psba_handle h, int reassemble, double *lambda, double *i
 
 static int ensure_dbg(psba_ctx *h) {
   const Dims &d = h->d;
-  if (!h->dbg_ex) TRY(dev_alloc(h, &h->dbg_ex, (size_t)2 * d.nO));
-  if (!h->dbg_JA) TRY(dev_alloc(h, &h->dbg_JA, (size_t)12 * d.nO));
-  if (!h->dbg_JB) TRY(dev_alloc(h, &h->dbg_JB, (size_t)6 * d.nO));
-  if (!h->dbg_Y) TRY(dev_alloc(h, &h->dbg_Y, (size_t)18 * d.nO));
-  if (!h->dbg_Vinv) TRY(dev_alloc(h, &h->dbg_Vinv, (size_t)9 * d.nP));
-  if (!h->dbg_eb) TRY(dev_alloc(h, &h->dbg_eb, (size_t)3 * d.nP));
+  if (!h->dbg_ex) TRY(h->dbg_ex.alloc(h, (size_t)2 * d.nO));
+  if (!h->dbg_JA) TRY(h->dbg_JA.alloc(h, (size_t)12 * d.nO));
+  if (!h->dbg_JB) TRY(h->dbg_JB.alloc(h, (size_t)6 * d.nO));
+  if (!h->dbg_Y) TRY(h->dbg_Y.alloc(h, (size_t)18 * d.nO));
+  if (!h->dbg_Vinv) TRY(h->dbg_Vinv.alloc(h, (size_t)9 * d.nP));
+  if (!h->dbg_eb) TRY(h->dbg_eb.alloc(h, (size_t)3 * d.nP));
   return PSBA_OK;
 }
 

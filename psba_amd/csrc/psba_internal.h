@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/psba_hip.h"
+#include "dev_buf.h"
 
 namespace psba {
 
@@ -145,75 +146,66 @@ constexpr int RUN_THREADS = 512;  // threads of a workgroup of k_schur_lds_runs:
 constexpr int RUN_MAX = 32;       // products a lane sums in registers before it touches the LDS at the latest
 }  // namespace psba
 
-struct psba_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-
+// ---- the handle's state, split by lifetime ----
+// ProblemState: everything an upload creates or invalidates -- the problem's buffers and schedules, the settings that
+// belong to a problem (lens model, loss, fixed blocks) and the state of the try in flight.  A new upload and
+// psba_destroy replace it by a default-constructed one: its members release what they own and every scalar is back
+// at its initial value.  A new per-problem field goes here, with its initial value, and nothing else has to be updated.
+struct ProblemState {
   psba::Dims d;
-  // multi-GPU
-  ncclComm_t comm = nullptr;
-  int nranks = 1, rank = 0;
-
-  // ---- device memory (all owned here) ----
-  double *camconst = nullptr;   // [nC][9]  K5 | q0(4)               (Kparas_buffer, initcams_buffer)
-  double *cams[2] = {nullptr, nullptr};  // [nC][6] cur / proposed   (cams_buffer, newCams_buffer)
-  double *pts[2] = {nullptr, nullptr};   // [nP][3] cur / proposed   (pts3D_buffer, newPts3D_buffer)
-  double *params0 = nullptr;    // [nT] the parameters as uploaded (psba_reset_params)
-  double *impts = nullptr;      // [nO][2]                           (impts_buffer)
+  // ---- device memory ----
+  psba::DevBuf<double> camconst;  // [nC][9]  K5 | q0(4)               (Kparas_buffer, initcams_buffer)
+  psba::DevBuf<double> cams[2];   // [nC][6] cur / proposed            (cams_buffer, newCams_buffer)
+  psba::DevBuf<double> pts[2];    // [nP][3] cur / proposed            (pts3D_buffer, newPts3D_buffer)
+  psba::DevBuf<double> params0;   // [nT] the parameters as uploaded (psba_reset_params)
+  psba::DevBuf<double> impts;     // [nO][2]                           (impts_buffer)
   // lens model (psba_set_distortion / psba_set_obs_covariance / psba_set_robust_loss; camera_model.h): the launch
   // sites pick the kernel instantiation from `lens` (bit 0 distortion, bit 1 covariances, bit 2 a robust loss other
   // than none); an upload resets it to none
   int lens = 0;
   int loss_kind = 0;            // PSBA_LOSS_* and its scale (whitened units)
   double loss_c = 1.0;
-  double *obs_s = nullptr;      // [nO] psba_obs_sq_residuals' device output, allocated on first use
-  double *lens_kc = nullptr;    // [nC][5] k1..k5, allocated while distortion is set
-  double *lens_w = nullptr;     // [nO][4] (l00, l01, l11, 0): L^T L = Sigma^-1, allocated while covariances are set
+  psba::DevBuf<double> obs_s;    // [nO] psba_obs_sq_residuals' device output, allocated on first use
+  psba::DevBuf<double> lens_kc;  // [nC][5] k1..k5, allocated while distortion is set
+  psba::DevBuf<double> lens_w;   // [nO][4] (l00, l01, l11, 0): L^T L = Sigma^-1, allocated while covariances are set
   // fixed parameter blocks (psba_set_fixed; camera_model.h FixedMask): byte masks on the device, allocated while a
   // mask of that kind with a non-zero entry is set; an upload resets them to none.  has_fixed selects the LENS_FIXED
   // kernel instantiations at the launch sites (lens_dispatch_fixed); struct_only = every camera is fixed
-  unsigned char *fix_cams = nullptr, *fix_pts = nullptr;  // [nC], [nP]
+  psba::DevBuf<unsigned char> fix_cams, fix_pts;  // [nC], [nP]
   int n_fix_cams = 0, n_fix_pts = 0;
   bool has_fixed = false, struct_only = false;
   bool try_shortcut = false;    // this try took the structure-only shortcut: nothing was assembled or factored
-  int *iidx = nullptr;          // [nO] point of each observation    (iidx_buffer)
-  int *jidx = nullptr;          // [nO] camera of each observation   (jidx_buffer)
-  int *ptr = nullptr;           // [nP+1] point CSR over observations (replaces blkIdx_buffer)
-  int *tile_pt = nullptr;       // [nTiles+1] first point of each tile
-  int *long_pts = nullptr;      // [nLong] points seen by more than TILE_OBS cameras (tiles of their own, handled by the *_long kernels)
+  psba::DevBuf<int> iidx;       // [nO] point of each observation    (iidx_buffer)
+  psba::DevBuf<int> jidx;       // [nO] camera of each observation   (jidx_buffer)
+  psba::DevBuf<int> ptr;        // [nP+1] point CSR over observations (replaces blkIdx_buffer)
+  psba::DevBuf<int> tile_pt;    // [nTiles+1] first point of each tile
+  psba::DevBuf<int> long_pts;   // [nLong] points seen by more than TILE_OBS cameras (tiles of their own, handled by the *_long kernels)
   int nLong = 0;
-  int4 *tile_desc = nullptr;    // [nTiles] (first point, end point, first observation, end observation): one load instead of a chain
-  double *W = nullptr;          // [nO][18] W_ij = coeff A^T B        (W_buffer)
-  double *PV = nullptr;         // [nP][9]  V_i sym6 | g_b,i          (V_buffer + g_buffer tail)
-  double *U = nullptr;          // [nC][36]                           (U_buffer)
-  double *ga = nullptr;         // [nA]                               (g_buffer head)
+  psba::DevBuf<int4> tile_desc;  // [nTiles] (first point, end point, first observation, end observation): one load instead of a chain
+  psba::DevBuf<double> W;        // [nO][18] W_ij = coeff A^T B        (W_buffer)
+  psba::DevBuf<double> PV;       // [nP][9]  V_i sym6 | g_b,i          (V_buffer + g_buffer tail)
+  psba::DevBuf<double> U;        // [nC][36]                           (U_buffer)
+  psba::DevBuf<double> ga;       // [nA]                               (g_buffer head)
   // second set of linearization outputs, written by psba_linearize_ahead for the proposed
   // parameters while the host decides about the step; psba_accept swaps the sets
-  double *W_alt = nullptr, *PV_alt = nullptr, *U_alt = nullptr, *ga_alt = nullptr;
+  psba::DevBuf<double> W_alt, PV_alt, U_alt, ga_alt;
   bool ahead = false;           // the alternate set holds the linearization at the proposed parameters
   bool lin_is_ahead = false;    // the current set was computed ahead: the next psba_linearize is a no-op
-  double *h_scal_dev = nullptr;     // device address of the pinned host block h_scal
-  hipEvent_t scal_event = nullptr;  // recorded behind the scalar copy of psba_backsub_async
-  hipStream_t stream2 = nullptr;    // with a communicator: the try's scalar all-reduce + copy run here
-  hipEvent_t k3_event = nullptr;    // K3 done (main stream) -> side stream
-  hipStream_t chol_side = nullptr;      // lowest-priority stream of the far updates (look-ahead of the blocked chain)
-  std::vector<hipEvent_t> chol_events;  // the look-ahead of the blocked Cholesky chain (two per super-panel)
-  bool scal_side = false;           // side-stream work the main stream has not been ordered behind yet
-  double *campart = nullptr;    // [nPart][nC][27] per-workgroup camera partial sums
+  bool scal_side = false;       // side-stream work the main stream has not been ordered behind yet
+  psba::DevBuf<double> campart;  // [nPart][nC][27] per-workgroup camera partial sums
   int nPart = 0;
   // many cameras (the 27 per-camera accumulators no longer fit a workgroup's LDS): K1 adds its
   // camera sums with global fp64 atomics into camacc [nC][27] (zeroed per launch) instead
   bool cam_global = false;
-  double *camacc = nullptr;
+  psba::DevBuf<double> camacc;
   // ... and those sums are formed by a camera-major pass: thread = (camera, segment of its
   // observations), 27 sums in registers, one set of atomic adds per segment
-  int *cam_obs = nullptr;       // [nO] observation indices sorted by camera (stable: points ascending)
-  int4 *cam_units = nullptr;    // [nCamUnits] (camera, first, end in cam_obs, 0)
+  psba::DevBuf<int> cam_obs;     // [nO] observation indices sorted by camera (stable: points ascending)
+  psba::DevBuf<int4> cam_units;  // [nCamUnits] (camera, first, end in cam_obs, 0)
   int nCamUnits = 0;
   // padded reduce buffer Lw[(n32+16)][n32], n32 = nA rounded up to 32: rows < nA = S (row stride
   // n32), rows nA..n32-1 identity padding, row n32 = ea, rows above zero (S_buffer, eab_buffer)
-  double *red = nullptr;
+  psba::DevBuf<double> red;
   int n32 = 0;
   // K2 (schur) static schedule, built once per problem by schur_plan.cpp
   int nGroups = 0;              // groups of blocks (one LDS partition each); 0: the owner route
@@ -222,93 +214,75 @@ struct psba_ctx {
   std::vector<int> gnwg;        // workgroups (= slabs) of group g
   std::vector<int> gnblk;       // blocks in group g's LDS partition (padded to 16)
   std::vector<size_t> gslab;    // first double of group g's slabs
-  psba::ReduceGroup *gtab = nullptr;  // device, for k_schur_reduce: one entry per run of 16 partition positions
-  psba::SchurWg *wg = nullptr;  // [nWg] ordered by position in the point sequence
-  unsigned long long *items = nullptr;   // work items, one per product Y_a W_b^T (or null)
+  psba::DevBuf<psba::ReduceGroup> gtab;  // for k_schur_reduce: one entry per run of 16 partition positions
+  psba::DevBuf<psba::SchurWg> wg;        // [nWg] ordered by position in the point sequence
+  psba::DevBuf<unsigned long long> items;  // work items, one per product Y_a W_b^T (or null)
+  bool schur_runs = false;      // K2's items are in the runs layout (k_schur_lds_runs)
+  bool schur_pairs = false;     // K2's item lists begin with pair items (SchurWg::itemD)
   // single rank: the K2 workgroups add their copies of the 21 blocks of the first 32x32 diagonal
   // block into diag0 (global atomics) while flushing, and one extra workgroup of the S-reduce
   // kernel factors that block -- the first step of the Cholesky chain off the critical path
-  double *redp = nullptr;       // with a communicator: the packed sums (slab order, lower block triangle + e_a) that are all-reduced
+  psba::DevBuf<double> redp;    // with a communicator: the packed sums (slab order, lower block triangle + e_a) that are all-reduced
   size_t packed_doubles = 0;
   bool packed_pending = false;  // this try's sums sit in redp, not yet in red
-  double *diag0 = nullptr;      // [21 * 36], zero between tries
+  psba::DevBuf<double> diag0;   // [21 * 36], zero between tries
   int h_diagpos[21] = {0};      // partition positions of the blocks (j, k), j <= 5
   int h_diaggrp[21] = {0};      // and their groups (-1: no such camera)
   bool diag_done = false;       // this try's S-reduce kernel has factored the first diagonal block
-  int *posblock = nullptr;      // per group, per partition position: (j << 16) | k of the block there, -1 = padding
-  double *slab = nullptr;       // per workgroup: its group's partition, 36 doubles per position
+  psba::DevBuf<int> posblock;   // per group, per partition position: (j << 16) | k of the block there, -1 = padding
+  psba::DevBuf<double> slab;    // per workgroup: its group's partition, 36 doubles per position
   size_t packedN = 0;           // 36 * nC (nC+1) / 2 doubles: packed lower block triangle of S
   int ring_nWg = 0, ring_nS = 0;  // (workgroups of the experimental ring route; 0 in the product build)
 #ifdef PSBA_BUILD_EXPERIMENTS
   // K2 ring route (few cameras): see RingPlanHost
-  psba::RingWg *ring_wg = nullptr;
-  psba::RingStep *ring_steps = nullptr;
-  unsigned *ring_entries = nullptr;
-  int *ring_ops = nullptr;
-  psba::RingJob *ring_jobs = nullptr;
-  int *ring_bl0 = nullptr;
-  int *ring_canon = nullptr;    // [tri(nC)] (j << 16) | k of every block of the canonical order
-  double *ring_slab = nullptr;  // [ring_nS][packedN] copies of the packed triangle
-  double *ring_pvi = nullptr;   // [nP][9] (V_i + mu I)^-1 (sym6) | (V_i + mu I)^-1 g_b,i of the current try (k_schur_vinv)
+  psba::DevBuf<psba::RingWg> ring_wg;
+  psba::DevBuf<psba::RingStep> ring_steps;
+  psba::DevBuf<unsigned> ring_entries;
+  psba::DevBuf<int> ring_ops;
+  psba::DevBuf<psba::RingJob> ring_jobs;
+  psba::DevBuf<int> ring_bl0;
+  psba::DevBuf<int> ring_canon;    // [tri(nC)] (j << 16) | k of every block of the canonical order
+  psba::DevBuf<double> ring_slab;  // [ring_nS][packedN] copies of the packed triangle
+  psba::DevBuf<double> ring_pvi;   // [nP][9] (V_i + mu I)^-1 (sym6) | (V_i + mu I)^-1 g_b,i of the current try (k_schur_vinv)
   long long ring_products = 0, ring_slots = 0;
   size_t ring_loaded_recs = 0;
-  bool ring_attr_set = false;
-  long long *chol_tim_ring = nullptr;  // dev instrumentation (PSBA_RING_TIMING): per-step s_memtime stamps of two workgroups
+  psba::DevBuf<long long> chol_tim_ring;  // dev instrumentation (PSBA_RING_TIMING): per-step s_memtime stamps of two workgroups
 #endif
   // block-sparse S + preconditioned CG (psba_set_solver, kernels_pcg.hip)
-  int solver = 0;               // PSBA_SOLVER_*
-  bool schur_runs = false;  // K2's items are in the runs layout (k_schur_lds_runs)
-  bool schur_pairs = false; // K2's item lists begin with pair items (SchurWg::itemD)
-  int cnp = 6;  // parameters per camera: 6 (fixed intrinsics, the reference's kernels) or 11 (psba_set_camera_model: free intrinsics)
-  double pcg_tol = 1e-10;
-  int pcg_maxit = 500, pcg_iters = 0;
+  int pcg_iters = 0;
   double pcg_relres = 0.0;
-  bool pcg_exhausted = false;  // the last solve used up max_iter without reaching tol
+  bool pcg_exhausted = false;   // the last solve used up max_iter without reaching tol
   long long bs_nblk = 0;
-  double *bs_val = nullptr;     // [bs_nblk][36] | e_a [nA] right behind (one all-reduce)
-  double *bs_ea = nullptr;      // = bs_val + 36 bs_nblk
-  int2 *bs_jk = nullptr;        // [bs_nblk] (j, k)
-  int *bs_diag = nullptr;       // [nC] index of block (j, j)
+  psba::DevBuf<double> bs_val;  // [bs_nblk][36] | e_a [nA] right behind (one all-reduce)
+  double *bs_ea = nullptr;      // = bs_val + 36 bs_nblk (not owned)
+  psba::DevBuf<int2> bs_jk;     // [bs_nblk] (j, k)
+  psba::DevBuf<int> bs_diag;    // [nC] index of block (j, j)
   // the full symmetric pattern by block row, for the product S p without atomics: row j's entries
   // [bs_rowptr[j], bs_rowptr[j + 1]) = (slot of the stored block, other camera | how to read it << 28:
   // 0 as stored (j is the block's row), 1 transposed (j is its column), 2 the diagonal block)
-  int *bs_rowptr = nullptr;
-  int2 *bs_rowent = nullptr;
-  double *pcg_vec = nullptr;    // r | z | p | q, nA each
-  double *pcg_minv = nullptr;   // [nC][36] inverses of the diagonal blocks
-  double *pcg_scal = nullptr, *pcg_host = nullptr;  // device scalars and their pinned mirror
-  std::vector<unsigned char> bs_pattern;  // sharded points without a communicator: the union of all ranks' blocks (psba_set_sparse_pattern)
+  psba::DevBuf<int> bs_rowptr;
+  psba::DevBuf<int2> bs_rowent;
+  psba::DevBuf<double> pcg_vec;   // r | z | p | q, nA each
+  psba::DevBuf<double> pcg_minv;  // [nC][36] inverses of the diagonal blocks
+  psba::DevBuf<double> pcg_scal;  // device scalars (their pinned mirror pcg_host lives with the handle)
   // K2 owner route (many cameras): see OwnerPlanHost
-  int2 *own_prod = nullptr;
-  psba::OwnerWave *own_waves = nullptr;
-  psba::OwnerUnit *own_units = nullptr;
+  psba::DevBuf<int2> own_prod;
+  psba::DevBuf<psba::OwnerWave> own_waves;
+  psba::DevBuf<psba::OwnerUnit> own_units;
   int own_nwaves = 0;
   long long own_products = 0;
-  double *dp = nullptr;         // [nT] dpa | dpb                     (dp_buffer)
-  double *trv[2] = {nullptr, nullptr};  // [nT] each: vectors of the trust-region operators (allocated on first use)
-  double *jmul_out = nullptr;   // [2 nO] J x of psba_compute_Jmultiply (allocated on first use)
-  hipGraphExec_t chol_graph[2] = {nullptr, nullptr};  // captured panel chain of kernels_chol_graph.hip, with / without its first step
+  psba::DevBuf<double> dp;        // [nT] dpa | dpb                     (dp_buffer)
+  psba::DevBuf<double> trv[2];    // [nT] each: vectors of the trust-region operators (allocated on first use)
+  psba::DevBuf<double> jmul_out;  // [2 nO] J x of psba_compute_Jmultiply (allocated on first use)
+  psba::GraphExec chol_graph[2];  // captured panel chain of kernels_chol_graph.hip, with / without its first step
   int chol_graph_n32[2] = {0, 0};
-  double *chol_graph_red[2] = {nullptr, nullptr};
-  long long *chol_tim = nullptr; // dev instrumentation: per-phase s_memtime ticks of the last solve (PSBA_CHOL_TIMING)
-  double *chol_L = nullptr;     // [(2 n32+16)][n32] panel chain: the Cholesky factor | forward-solved e_a row | L^-T
-  double *dist_buf = nullptr;   // sharded factorization: packed column blocks of one super-panel (allocated on first use)
-  double *chol_ws = nullptr;    // [ceil(nA/32)][32*32] inverses of the diagonal blocks of L (diagBlkAux_buffer)
-  double *scal = nullptr;       // [NSCAL]
-  // [4] generation stamps, never zeroed: [0] == try_id <=> some V_i singular in this try,
-  // [1] == try_id <=> the Cholesky of this try failed; [3] = try_id as seen by the graph-replayed
-  // Cholesky kernels (written by the K2 reduce kernel).  Lives in scal[8..9]
-  int *status = nullptr;
-  int try_id = 0;
-  double *h_scal = nullptr;     // pinned mirror of scal
-  int *h_status = nullptr;      // pinned mirror of status
+  double *chol_graph_red[2] = {nullptr, nullptr};  // (the reduce buffer the graph was captured for: compared, not owned)
+  psba::DevBuf<long long> chol_tim;  // dev instrumentation: per-phase s_memtime ticks of the last solve (PSBA_CHOL_TIMING)
+  psba::DevBuf<double> chol_L;    // [(2 n32+16)][n32] panel chain: the Cholesky factor | forward-solved e_a row | L^-T
+  psba::DevBuf<double> dist_buf;  // sharded factorization: packed column blocks of one super-panel (allocated on first use)
+  psba::DevBuf<double> chol_ws;   // [ceil(nA/32)][32*32] inverses of the diagonal blocks of L (diagBlkAux_buffer)
   // debug dumps for the sba_func.h mirror (allocated on first use)
-  double *dbg_ex = nullptr, *dbg_JA = nullptr, *dbg_JB = nullptr, *dbg_Y = nullptr,
-         *dbg_Vinv = nullptr, *dbg_eb = nullptr;
-
-  // kernels whose dynamic LDS exceeds 64 KiB need hipFuncSetAttribute once per device: kept per
-  // handle (one handle = one device), not per process
-  bool lds_attr_set = false, atomic_attr_set = false, chol_attr_set = false, lin_attr_set = false;
+  psba::DevBuf<double> dbg_ex, dbg_JA, dbg_JB, dbg_Y, dbg_Vinv, dbg_eb;
 
   // ---- state ----
   bool uploaded = false, linearized = false, assembled = false, solved = false, backsubbed = false;
@@ -318,11 +292,52 @@ struct psba_ctx {
   // and that linearization: publish_deferred = K3 queued, nothing published yet; publish_in_k1 = the
   // queued K1 carries them, the host waits for pub_seq in h_scal[NSCAL]
   bool publish_deferred = false, publish_in_k1 = false;
-  double pub_seq = 0.0;
   int cur = 0;                  // index of the current parameter set in cams[]/pts[]
   double coeff = 1.0, coeff_g = 1.0, mu = 0.0;
   double coeff_w = 1.0;         // the coefficient the stored W was formed with (last K1 launch)
   bool mu_applied = false;      // update_UV called (fine-grained mirror only)
+};
+
+// what lives as long as the handle: the device and its streams and events, the scalar blocks, the communicator, the
+// settings made before an upload (solver, camera block, block pattern), per-device flags, profiling -- and the
+// generation stamps try_id and pub_seq, which are compared with device and pinned words that are never zeroed (a stamp
+// that started again at zero would match a stale word)
+struct psba_ctx : ProblemState {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+
+  // multi-GPU
+  ncclComm_t comm = nullptr;
+  int nranks = 1, rank = 0;
+
+  double *h_scal_dev = nullptr;     // device address of the pinned host block h_scal
+  hipEvent_t scal_event = nullptr;  // recorded behind the scalar copy of psba_backsub_async
+  hipStream_t stream2 = nullptr;    // with a communicator: the try's scalar all-reduce + copy run here
+  hipEvent_t k3_event = nullptr;    // K3 done (main stream) -> side stream
+  hipStream_t chol_side = nullptr;      // lowest-priority stream of the far updates (look-ahead of the blocked chain)
+  std::vector<hipEvent_t> chol_events;  // the look-ahead of the blocked Cholesky chain (two per super-panel)
+
+  int solver = 0;               // PSBA_SOLVER_* (block-sparse S + preconditioned CG: psba_set_solver, kernels_pcg.hip)
+  int cnp = 6;  // parameters per camera: 6 (fixed intrinsics, the reference's kernels) or 11 (psba_set_camera_model: free intrinsics)
+  double pcg_tol = 1e-10;
+  int pcg_maxit = 500;
+  psba::PinnedBuf<double> pcg_host;       // pinned mirror of the PCG's device scalars (allocated by the first PCG upload)
+  std::vector<unsigned char> bs_pattern;  // sharded points without a communicator: the union of all ranks' blocks (psba_set_sparse_pattern)
+
+  psba::DevBuf<double> scal;    // [NSCAL]
+  // [4] generation stamps, never zeroed: [0] == try_id <=> some V_i singular in this try,
+  // [1] == try_id <=> the Cholesky of this try failed; [3] = try_id as seen by the graph-replayed
+  // Cholesky kernels (written by the K2 reduce kernel).  Lives in scal[8..9]
+  int *status = nullptr;
+  int try_id = 0;
+  double pub_seq = 0.0;         // stamp of the last try whose scalars the linearization queued ahead carries (h_scal[NSCAL])
+  psba::PinnedBuf<double> h_scal;  // pinned mirror of scal
+  int *h_status = nullptr;      // pinned mirror of status
+
+  // kernels whose dynamic LDS exceeds 64 KiB need hipFuncSetAttribute once per device: kept per
+  // handle (one handle = one device), not per process
+  bool lds_attr_set = false, atomic_attr_set = false, chol_attr_set = false, lin_attr_set = false, ring_attr_set = false;
 
   // ---- profiling ----
   unsigned prof = 0;            // bit k set: time kernel class k with HIP events
