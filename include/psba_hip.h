@@ -101,8 +101,40 @@ int psba_get_dims(psba_handle h, int *nCams, int *n3Dpts, int *n2Dprojs);
  * differences and a dense solve of the full normal equations.  Before psba_upload_problem. */
 #define PSBA_CAMERA_FIXED_K 0
 #define PSBA_CAMERA_FREE_K 1
+#define PSBA_CAMERA_FREE_KD 2
 int psba_set_camera_model(psba_handle h, int model);
-int psba_camera_block(psba_handle h, int *cnp); /* 6 or 11 */
+int psba_camera_block(psba_handle h, int *cnp); /* 6, 11 or 16 */
+
+/* ---- free intrinsics together with lens distortion ---------------------------------------
+ * PSBA_CAMERA_FREE_KD optimises the five intrinsics and the five distortion coefficients with the pose: the camera
+ * block is (fu, u0, v0, ar, s | k1, k2, k3, k4, k5 | v0, v1, v2 | t0, t1, t2), nA = 16 nCams, dp = [16 per camera ;
+ * 3 per point]; psba_get_params / psba_set_params move 16 doubles per camera.  Model (the same in
+ * psba_amd/csrc/camera_model.h and DESIGN.md; kc order and distortion as for psba_set_distortion below): with (x, y)
+ * the normalised point, r2 = x^2 + y^2 and (xd, yd) the distorted point,
+ *   d(u, v) / d(fu, u0, v0, ar, s) = [ xd, 1, 0, 0, yd ;  ar yd, 0, 1, fu yd, 0 ]
+ *   d xd / d(k1..k5) = (r2 x, r2^2 x, 2 x y, r2 + 2 x^2, r2^3 x),  d yd / d(k1..k5) = (r2 y, r2^2 y, r2 + 2 y^2, 2 x y, r2^3 y)
+ *   d u / dk = fu d xd + s d yd,  d v / dk = fu ar d yd;  the extrinsic columns and B as with fixed distortion.
+ * Starting distortion: under this model psba_set_distortion(h, kc) is allowed after psba_upload_problem and sets the
+ * starting kc -- columns 5..9 of the current parameters and of the copy psba_reset_params restores (an upload starts
+ * from zeros, NULL means zeros); it discards a linearization queued ahead and returns PSBA_E_STATE while a try is in
+ * flight.  psba_lens_model reports has_distortion = 1.
+ * Per-parameter mask: free10[k] != 0 = intrinsic k (order fu, u0, v0, ar, s, k1..k5) is optimised, 0 = it is held at
+ * its current value on every camera.  NULL = all ten free; all ten zero is legal (extrinsics only); the problem of
+ * Bundle Adjustment in the Large is {fu, k1, k2}.  After psba_upload_problem (a new upload resets to all free);
+ * PSBA_E_STATE under another camera model and while a try is in flight; a refused call changes nothing; setting the
+ * mask discards a linearization queued ahead.  Semantics as for fixed blocks, per coordinate: the column
+ * of A is zero, the stored diagonal entry of U_j is the placeholder coeff, g and dp are exactly 0, the proposed and
+ * accepted values are bit-identical to the current ones, psba_max_diag / psba_begin take the maximum over the free
+ * entries, row and column of S are zero off the diagonal with coeff + mu on it, and e_a is 0.
+ * Route (kernels_freekd.hip, psba_schur_path = 5): camera-major linearization and S assembly on
+ * v_mfma_f64_16x16x4_f64, no floating-point atomics -- two runs give bit-identical reduce buffers and logs.  Single
+ * rank, dense solver.  The fused verbs, psba_levmar, psba_get_dp, psba_get_gradient and psba_get / set_reduce_buffer
+ * work; covariances, robust losses, psba_set_fixed, PSBA_SOLVER_PCG, rank layouts, the sba_func.h mirror, the
+ * trust-region operators, psba_solve and psba_obs_sq_residuals return PSBA_E_STATE with a text that names
+ * PSBA_CAMERA_FREE_KD.  The reference has no arithmetic for this: PARITY UNPINNED -- checked against a numpy twin,
+ * central differences and a dense solve of the full normal equations. */
+int psba_set_intrinsics_mask(psba_handle h, const unsigned char free10[10]);
+int psba_intrinsics_mask(psba_handle h, unsigned char out10[10]);
 
 /* ---- lens distortion and per-observation image covariances --------------------------
  * Model (the same in psba_amd/csrc/camera_model.h and DESIGN.md): P = R'(q) M + t, (x, y) = (Px, Py) / Pz,
@@ -116,7 +148,8 @@ int psba_camera_block(psba_handle h, int *cnp); /* 6 or 11 */
  * projection (e <- L e, A <- L A, B <- L B).  Every verb then works on the whitened quantities: psba_residual,
  * the try scalars and the loop logs report the weighted cost, and psba_compute_exQT / psba_compute_jacobiQT
  * (and the U, V, W, g, S, e_a of the mirror) return the whitened e, A and B.
- * The fixed-intrinsics camera block only: PSBA_E_STATE before psba_upload_problem and under PSBA_CAMERA_FREE_K.
+ * The fixed-intrinsics camera block only: PSBA_E_STATE before psba_upload_problem and under PSBA_CAMERA_FREE_K
+ * (under PSBA_CAMERA_FREE_KD psba_set_distortion sets the starting kc instead, see above; covariances are refused).
  * Call after psba_upload_problem (a new upload resets both to none), while no try is in flight; setting either
  * discards a linearization queued ahead.  The reference reads both and uses neither (PSBA/readparams.cpp:272-283,
  * 380-412; PSBA/main.cpp:112): PARITY UNPINNED -- checked against an independent numpy twin that is itself pinned to
@@ -202,7 +235,8 @@ int psba_fixed_counts(psba_handle h, int *n_fixed_cams, int *n_fixed_pts);
  * products sorted by camera pair, sums in registers; PSBA_SCHUR_OWNER=1 forces it), 2 = global
  * fp64 atomics straight into S (the
  * first-generation kernel, kept for cross-checks: PSBA_SCHUR_ATOMIC=1), 3 = the ring route (opt-in
- * experiment, PSBA_SCHUR_RING=1), 4 = block-sparse S (PSBA_SOLVER_PCG).  The reference has one
+ * experiment, PSBA_SCHUR_RING=1), 4 = block-sparse S (PSBA_SOLVER_PCG), 5 = the 16-parameter camera block
+ * (PSBA_CAMERA_FREE_KD: products sorted by block, one MFMA per product).  The reference has one
  * route for every size (CL_files/compute_S.cl:6-78). */
 int psba_schur_path(psba_handle h, int *path);
 
@@ -299,6 +333,10 @@ typedef struct {
   int start_itno;   /* the reference shares itno between LM and TR (main.cpp:193-208) */
   double init_mu;   /* mu_0 = init_mu * max diag(U, V); 0 = the reference's PSBA_INIT_MU 1e-3 (psba.h:6,
                        levmar.cpp:114-116), a compile-time constant there */
+  double stop_cost; /* the loop ends with PSBA_ITER_ERR_SMALL_ENOUGH once ||e||^2 <= stop_cost; 0 = the reference's
+                       PSBA_STOP_THRESH 1e-12 (psba.h:7, levmar.cpp:247-248), an absolute figure in squared image
+                       units that ends a noise-free problem before fp64 is used up; negative = no such test (the
+                       relative tests on dp still end the loop) */
 } psba_lm_options;
 
 typedef struct {
@@ -554,6 +592,20 @@ psba_owner_plan_t psba_owner_plan_create(int nCams, int n3Dpts, int n2Dprojs, co
 int psba_owner_plan_info(psba_owner_plan_t p, long long info[4]);
 int psba_owner_plan_copy(psba_owner_plan_t p, long long *waves, int *units, int *prod, int *blocks, int *diag_slot);
 void psba_owner_plan_destroy(psba_owner_plan_t p);
+
+/* ---- test hook: the S-assembly schedule of the 16-parameter camera block (PSBA_CAMERA_FREE_KD), host only.
+ * Every product Y_a W_b^T (b <= a, both observations of one point) belongs to the block (camera of a, camera of b)
+ * of the lower block triangle; the products are sorted by block (ascending (j, k)), inside a block by point, and a
+ * block's list is cut into segments of at most seg_len products (PSBA_FKD_SEG at upload; one wave per segment).
+ * info[0..3] = blocks, segments, products, partial tiles (segments of blocks that have several).
+ * psba_blockprod_plan_copy: blocks[blocks][2] = (j, k); segs[segments][3] = block, first product, end product;
+ * prods[products][2] = observations (a, b).  Any pointer may be NULL. */
+typedef struct psba_blockprod_plan *psba_blockprod_plan_t;
+psba_blockprod_plan_t psba_blockprod_plan_create(int nCams, int n3Dpts, int n2Dprojs, const int *iidx, const int *jidx,
+                                                 int seg_len);
+int psba_blockprod_plan_info(psba_blockprod_plan_t p, long long info[4]);
+int psba_blockprod_plan_copy(psba_blockprod_plan_t p, int *blocks, int *segs, int *prods);
+void psba_blockprod_plan_destroy(psba_blockprod_plan_t p);
 
 #ifdef PSBA_BUILD_EXPERIMENTS
 /* (Only in a library built with PSBA_BUILD_EXPERIMENTS=1: round 3's ring route is an experiment that lost,

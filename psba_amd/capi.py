@@ -17,6 +17,8 @@ lib = C.CDLL(lib_path)
 PSBA_OK, PSBA_NOT_SPD, PSBA_SINGULAR_V = 0, 1, 2
 PARAMS_CUR, PARAMS_NEW = 0, 1
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY, LOSS_SOFT_L1 = 0, 1, 2, 3
+CAMERA_FIXED_K, CAMERA_FREE_K, CAMERA_FREE_KD = 0, 1, 2
+INTRINSICS_BAL = (1, 0, 0, 0, 0, 1, 1, 0, 0, 0)  # the free intrinsics of Bundle Adjustment in the Large: f, k1, k2
 ITER_TURN_TO_LM, ITER_TURN_TO_TR, ITER_CONTINUE, ITER_ERR = 1, 2, 3, 4
 ITER_DP_NO_CHANGE, ITER_ERR_SMALL_ENOUGH, ITER_PASS = 5, 6, 7
 K_LINEARIZE, K_SCHUR, K_CHOLESKY, K_BACKSUB, K_RESIDUAL, K_ALLREDUCE, K_SCHUR_REDUCE = range(7)
@@ -34,7 +36,8 @@ class TryScalars(C.Structure):
 
 class LmOptions(C.Structure):
     _fields_ = [("max_iter", C.c_int), ("tr_handoff", C.c_int), ("verbose", C.c_int),
-                ("log_cap", C.c_int), ("start_itno", C.c_int), ("init_mu", C.c_double)]
+                ("log_cap", C.c_int), ("start_itno", C.c_int), ("init_mu", C.c_double),
+                ("stop_cost", C.c_double)]
 
 
 class LmResult(C.Structure):
@@ -173,6 +176,12 @@ SIGNATURES = [
     ("psba_owner_plan_info", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     ("psba_owner_plan_copy", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _ip, _ip, _ip, _ip]),
     ("psba_owner_plan_destroy", None, [C.c_void_p]),
+    ("psba_set_intrinsics_mask", C.c_int, [_h, C.POINTER(C.c_ubyte)]),
+    ("psba_intrinsics_mask", C.c_int, [_h, C.POINTER(C.c_ubyte)]),
+    ("psba_blockprod_plan_create", C.c_void_p, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_int]),
+    ("psba_blockprod_plan_info", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    ("psba_blockprod_plan_copy", C.c_int, [C.c_void_p, _ip, _ip, _ip]),
+    ("psba_blockprod_plan_destroy", None, [C.c_void_p]),
 ]
 # only in a library built with PSBA_BUILD_EXPERIMENTS=1 (round 3's rejected ring route and its test hooks)
 EXPERIMENT_SIGNATURES = [
@@ -347,6 +356,27 @@ def owner_plan(n_cams, n_pts, iidx, jidx, pattern=None):
     return dict(waves=waves, units=units, prod=prod.reshape(rows, 64, 2), blocks=blocks, diag_slot=diag, products=products)
 
 
+def blockprod_plan(n_cams, n_pts, iidx, jidx, seg_len):
+    """The S-assembly schedule of the 16-parameter camera block (host only, no device): dict with blocks [nb, 2] =
+    (j, k), segs [ns, 3] = (block, first, end product), prods [np, 2] = observations (a, b), tiles."""
+    iidx = _c(iidx, np.int32)
+    jidx = _c(jidx, np.int32)
+    p = lib.psba_blockprod_plan_create(int(n_cams), int(n_pts), int(iidx.size), _i(iidx), _i(jidx), int(seg_len))
+    if not p:
+        raise PsbaError(-1, "psba_blockprod_plan_create failed")
+    try:
+        info = (C.c_longlong * 4)()
+        lib.psba_blockprod_plan_info(p, info)
+        nb, ns, npr, tiles = (int(x) for x in info)
+        blocks = np.zeros((nb, 2), dtype=np.int32)
+        segs = np.zeros((ns, 3), dtype=np.int32)
+        prods = np.zeros((npr, 2), dtype=np.int32)
+        lib.psba_blockprod_plan_copy(p, _i(blocks), _i(segs), _i(prods))
+    finally:
+        lib.psba_blockprod_plan_destroy(p)
+    return dict(blocks=blocks, segs=segs, prods=prods, tiles=tiles)
+
+
 def chol_dist_exchange_plan(n32, NB, nranks, JE):
     """[(block, owner, slot, doubles)] of the column exchange in front of the super-panel at column JE."""
     out = np.zeros((64, 4), dtype=np.int64)
@@ -442,12 +472,29 @@ class Psba:
         return rc
 
     # ---- setup ----
-    def set_camera_model(self, free_k):
-        """PSBA_CAMERA_FREE_K: camera blocks of 11 (fu, u0, v0, ar, s | rotation | translation); before upload."""
-        self._ck(lib.psba_set_camera_model(self._h, 1 if free_k else 0))
+    def set_camera_model(self, model):
+        """False / CAMERA_FIXED_K: blocks of 6; True / CAMERA_FREE_K: blocks of 11 (fu, u0, v0, ar, s | rotation |
+        translation); CAMERA_FREE_KD: blocks of 16 (... s | k1..k5 | rotation | translation).  Before upload."""
+        self._ck(lib.psba_set_camera_model(self._h, int(model)))
+
+    def set_intrinsics_mask(self, free=None):
+        """psba_set_intrinsics_mask: ten flags (fu, u0, v0, ar, s, k1..k5), non-zero = optimised; None = all free."""
+        if free is None:
+            return self._ck(lib.psba_set_intrinsics_mask(self._h, None))
+        m = np.ascontiguousarray((np.asarray(free).reshape(-1) != 0).astype(np.uint8))
+        if m.size != 10:
+            raise PsbaError(-1, f"set_intrinsics_mask: {m.size} flags for 10 intrinsics")
+        self._ck(lib.psba_set_intrinsics_mask(self._h, m.ctypes.data_as(C.POINTER(C.c_ubyte))))
+
+    def intrinsics_mask(self):
+        """psba_intrinsics_mask -> tuple of ten 0 / 1"""
+        m = np.zeros(10, dtype=np.uint8)
+        self._ck(lib.psba_intrinsics_mask(self._h, m.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return tuple(int(v) for v in m)
 
     def set_distortion(self, kc):
-        """psba_set_distortion: kc [nC, 5] = (k1, k2, k3, k4, k5) per camera, None = no distortion."""
+        """psba_set_distortion: kc [nC, 5] = (k1, k2, k3, k4, k5) per camera, None = no distortion.  Under
+        CAMERA_FREE_KD: the starting kc (columns 5..9 of the parameters), None = zeros."""
         k = None if kc is None else _c(kc).reshape(-1)
         if k is not None and k.size != 5 * self.nC:
             raise PsbaError(-1, f"set_distortion: {k.size} values for {self.nC} cameras (5 each)")
@@ -532,8 +579,8 @@ class Psba:
 
     # ---- fused verbs ----
     def schur_path(self):
-        """0: LDS-partition schedule, 1: owner route, 2: global-atomic assembly kernel, 3: ring route
-        (psba_schur_path)."""
+        """0: LDS-partition schedule, 1: owner route, 2: global-atomic assembly kernel, 3: ring route, 4: block-sparse,
+        5: the 16-parameter camera block (psba_schur_path)."""
         v = C.c_int()
         self._ck(lib.psba_schur_path(self._h, C.byref(v)))
         return v.value
@@ -653,8 +700,10 @@ class Psba:
         return self._out(lib.psba_update_p, self.nT)[1]
 
     # ---- LM ----
-    def levmar(self, max_iter=50, tr_handoff=False, verbose=False, log_cap=512, start_itno=0, init_mu=0.0):
-        opts = LmOptions(max_iter, int(tr_handoff), int(verbose), log_cap, start_itno, init_mu)
+    def levmar(self, max_iter=50, tr_handoff=False, verbose=False, log_cap=512, start_itno=0, init_mu=0.0,
+               stop_cost=0.0):
+        """stop_cost: end once the cost is at or below it; 0 = the default 1e-12, negative = no absolute stop."""
+        opts = LmOptions(max_iter, int(tr_handoff), int(verbose), log_cap, start_itno, init_mu, stop_cost)
         res = LmResult()
         log = np.zeros((max(log_cap, 1), 5))
         self._ck(lib.psba_levmar(self._h, C.byref(opts), C.byref(res), _d(log)))

@@ -271,6 +271,64 @@ PSBA_HD void linearize_obs_dist(const double *K, const double *q0, const double 
   }
 }
 
+// Free intrinsics with distortion (PSBA_CAMERA_FREE_KD; the same model in include/psba_hip.h and DESIGN 7d): camera
+// block p = (fu, u0, v0, ar, s | k1, k2, k3, k4, k5 | v0, v1, v2 | t0, t1, t2), kc = p + 5 in the order of distort().
+// With (x, y) the normalised point, r2 = x^2 + y^2 and (xd, yd) = distort(kc, x, y):
+//   d(u, v) / d(fu, u0, v0, ar, s) = [ xd, 1, 0, 0, yd ;  ar yd, 0, 1, fu yd, 0 ]
+//   d xd / d(k1..k5) = (r2 x, r2^2 x, 2 x y, r2 + 2 x^2, r2^3 x)
+//   d yd / d(k1..k5) = (r2 y, r2^2 y, r2 + 2 y^2, 2 x y, r2^3 y)
+//   d u / dk = fu d xd + s d yd,   d v / dk = fu ar d yd
+// and the six extrinsic columns and B are those of linearize_obs_dist.  A is 2 x 16 row-major.
+// free_mask: bit k set = intrinsic k (k < 10) is optimised; a cleared bit zeroes that column of A (psba_set_intrinsics_mask).
+constexpr int KD_CNP = 16;
+constexpr unsigned KD_ALL_FREE = 0x3FFu;
+PSBA_HD void linearize_obs_freekd(const double *p, const double *q0, const double *M, double mx, double my, double *e,
+                                  double *A, double *B, unsigned free_mask = KD_ALL_FREE) {
+  double A6[12];
+  linearize_obs_dist(p, q0, p + 10, M, p + 5, mx, my, e, A6, B);
+  // the normalised point once more (three products: cheaper than widening linearize_obs_dist's interface)
+  double sl, R[9];
+  const Quat q = compose_quat(q0, p[10], p[11], p[12], sl);
+  quat_matrix(q, R);
+  const double Px = R[0] * M[0] + R[1] * M[1] + R[2] * M[2] + p[13];
+  const double Py = R[3] * M[0] + R[4] * M[1] + R[5] * M[2] + p[14];
+  const double Pz = R[6] * M[0] + R[7] * M[1] + R[8] * M[2] + p[15];
+  const double inv = 1.0 / Pz;
+  const double x = Px * inv, y = Py * inv;
+  double xd, yd;
+  distort(p + 5, x, y, xd, yd);
+  const double r2 = x * x + y * y, xy2 = 2.0 * x * y;
+  const double dxd[5] = {r2 * x, r2 * r2 * x, xy2, r2 + 2.0 * x * x, r2 * r2 * r2 * x};
+  const double dyd[5] = {r2 * y, r2 * r2 * y, r2 + 2.0 * y * y, xy2, r2 * r2 * r2 * y};
+  const double fa = p[0] * p[3];
+  A[0] = xd;
+  A[1] = 1.0;
+  A[2] = 0.0;
+  A[3] = 0.0;
+  A[4] = yd;
+  A[KD_CNP + 0] = p[3] * yd;
+  A[KD_CNP + 1] = 0.0;
+  A[KD_CNP + 2] = 1.0;
+  A[KD_CNP + 3] = p[0] * yd;
+  A[KD_CNP + 4] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 5; k++) {
+    A[5 + k] = p[0] * dxd[k] + p[4] * dyd[k];
+    A[KD_CNP + 5 + k] = fa * dyd[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 10; k++) {
+    const bool fr = (free_mask >> k) & 1u;
+    A[k] = fr ? A[k] : 0.0;
+    A[KD_CNP + k] = fr ? A[KD_CNP + k] : 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    A[10 + k] = A6[k];
+    A[KD_CNP + 10 + k] = A6[6 + k];
+  }
+}
+
 // e <- L e, A <- L A, B <- L B with L = [l00 l01; 0 l11] (w = (l00, l01, l11))
 PSBA_HD void whiten2(const double *w, double &e0, double &e1) {
   const double t = w[0] * e0 + w[1] * e1;
@@ -504,6 +562,31 @@ PSBA_HD bool sym3_inverse(const double *v, double *o) {
   o[4] = (a12 * a13 - a11 * a23) * iT;
   o[5] = (a11 * a22 - a12 * a12) * iT;
   return fabs(T) < 1e-16;
+}
+
+// V y = w for a symmetric positive definite 3x3 V (same packing) by L D L^T and substitution.  Unlike a product
+// with the explicit inverse this is backward stable per right-hand side, which is what keeps Y_a W_b^T accurate when
+// V_i + mu I is nearly singular (a point seen once and a small mu: V_i has rank 2 and W, g_b carry no component along
+// its null direction -- an unstructured error of the inverse would be amplified by the condition number).
+struct Sym3Ldl {
+  double l10, l20, l21, i0, i1, i2;  // unit lower factor, reciprocals of D
+};
+PSBA_HD Sym3Ldl sym3_ldl(const double *v) {
+  Sym3Ldl f;
+  f.i0 = 1.0 / v[0];
+  f.l10 = v[1] * f.i0;
+  f.l20 = v[2] * f.i0;
+  const double d1 = v[3] - f.l10 * v[1];
+  f.i1 = 1.0 / d1;
+  f.l21 = (v[4] - f.l20 * v[1]) * f.i1;
+  f.i2 = 1.0 / (v[5] - f.l20 * v[2] - f.l21 * f.l21 * d1);
+  return f;
+}
+PSBA_HD void sym3_ldl_solve(const Sym3Ldl &f, double w0, double w1, double w2, double &y0, double &y1, double &y2) {
+  const double z1 = w1 - f.l10 * w0, z2 = w2 - f.l20 * w0 - f.l21 * z1;
+  y2 = z2 * f.i2;
+  y1 = z1 * f.i1 - f.l21 * y2;
+  y0 = w0 * f.i0 - f.l10 * y1 - f.l20 * y2;
 }
 
 }  // namespace psba

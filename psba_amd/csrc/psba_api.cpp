@@ -197,22 +197,24 @@ int psba_destroy(psba_handle h) {
 int psba_schur_path(psba_handle h, int *path) {
   CHECK_H(h);
   NEED(h, h->uploaded, "no problem uploaded");
-  if (path) *path = h->solver == PSBA_SOLVER_PCG ? 4 : getenv("PSBA_SCHUR_ATOMIC") ? 2 : h->ring_nWg > 0 ? 3 : h->nGroups > 0 ? 0 : 1;
+  if (path) *path = h->cnp == KD_CNP ? 5 : h->solver == PSBA_SOLVER_PCG ? 4 : getenv("PSBA_SCHUR_ATOMIC") ? 2 : h->ring_nWg > 0 ? 3 : h->nGroups > 0 ? 0 : 1;
   return PSBA_OK;
 }
 
 int psba_set_camera_model(psba_handle h, int model) {
   CHECK_H(h);
-  if (model != PSBA_CAMERA_FIXED_K && model != PSBA_CAMERA_FREE_K) return fail(h, PSBA_E_INVALID, "unknown camera model %d", model);
+  if (model != PSBA_CAMERA_FIXED_K && model != PSBA_CAMERA_FREE_K && model != PSBA_CAMERA_FREE_KD)
+    return fail(h, PSBA_E_INVALID, "unknown camera model %d", model);
   NEED(h, !h->uploaded, "psba_set_camera_model before psba_upload_problem (every buffer depends on the camera block)");
-  h->cnp = model == PSBA_CAMERA_FREE_K ? 11 : 6;
+  h->cnp = model == PSBA_CAMERA_FREE_KD ? KD_CNP : model == PSBA_CAMERA_FREE_K ? FK_CNP : 6;
   return PSBA_OK;
 }
 
 // ---- lens model (camera_model.h) -------------------------------------------------------------
 static int lens_settable(psba_ctx *h, const char *what) {
   if (!h->uploaded) return fail(h, PSBA_E_STATE, "%s: no problem uploaded", what);
-  if (h->cnp != 6) return fail(h, PSBA_E_STATE, "%s: the fixed-intrinsics camera block only (not PSBA_CAMERA_FREE_K)", what);
+  if (h->cnp != 6)
+    return fail(h, PSBA_E_STATE, "%s: the fixed-intrinsics camera block only (not PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)", what);
   if (h->backsub_pending) return fail(h, PSBA_E_STATE, "%s: a damping try is in flight (psba_backsub_wait first)", what);
   return PSBA_OK;
 }
@@ -224,8 +226,31 @@ static void lens_changed(psba_ctx *h) {
   h->linearized = h->assembled = h->solved = false;
 }
 
+// PSBA_CAMERA_FREE_KD: kc is part of the camera block -- the starting values go into columns 5..9 of the current
+// parameters and of the copy psba_reset_params restores
+static int set_start_distortion(psba_ctx *h, const double *kc) {
+  if (h->backsub_pending) return fail(h, PSBA_E_STATE, "psba_set_distortion: a damping try is in flight (psba_backsub_wait first)");
+  const int nC = h->d.nC;
+  for (int t = 0; kc && t < 5 * nC; t++)
+    if (!std::isfinite(kc[t])) return fail(h, PSBA_E_INVALID, "psba_set_distortion: kc[%d] of camera %d is not finite", t % 5, t / 5);
+  std::vector<double> c((size_t)h->d.nA);
+  double *dst[2] = {h->cams[h->cur], h->params0};
+  for (int k = 0; k < 2; k++) {
+    PSBA_HIP(h, hipMemcpyAsync(c.data(), dst[k], sizeof(double) * c.size(), hipMemcpyDeviceToHost, h->stream));
+    PSBA_HIP(h, hipStreamSynchronize(h->stream));
+    for (int j = 0; j < nC; j++)
+      for (int q = 0; q < 5; q++) c[(size_t)KD_CNP * j + 5 + q] = kc ? kc[5 * j + q] : 0.0;
+    PSBA_HIP(h, hipMemcpyAsync(dst[k], c.data(), sizeof(double) * c.size(), hipMemcpyHostToDevice, h->stream));
+    PSBA_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  h->ahead = h->lin_is_ahead = false;
+  h->linearized = h->assembled = h->solved = h->backsubbed = false;
+  return PSBA_OK;
+}
+
 int psba_set_distortion(psba_handle h, const double *kc) {
   CHECK_H(h);
+  if (h->uploaded && h->cnp == KD_CNP) return set_start_distortion(h, kc);
   TRY(lens_settable(h, __func__));
   if (!kc) {
     h->lens_kc.reset();
@@ -283,7 +308,7 @@ int psba_set_obs_covariance(psba_handle h, const double *cov) {
 
 int psba_lens_model(psba_handle h, int *has_distortion, int *has_covariance) {
   CHECK_H(h);
-  if (has_distortion) *has_distortion = (h->lens & LENS_DIST) ? 1 : 0;
+  if (has_distortion) *has_distortion = ((h->lens & LENS_DIST) || h->cnp == KD_CNP) ? 1 : 0;
   if (has_covariance) *has_covariance = (h->lens & LENS_COV) ? 1 : 0;
   return PSBA_OK;
 }
@@ -370,12 +395,33 @@ int psba_fixed_counts(psba_handle h, int *n_fixed_cams, int *n_fixed_pts) {
   return PSBA_OK;
 }
 
+// ---- per-parameter mask of the ten intrinsics (PSBA_CAMERA_FREE_KD) ----
+int psba_set_intrinsics_mask(psba_handle h, const unsigned char *free10) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp == KD_CNP, "psba_set_intrinsics_mask: PSBA_CAMERA_FREE_KD only");
+  NEED(h, !h->backsub_pending, "psba_set_intrinsics_mask: a damping try is in flight (psba_backsub_wait first)");
+  unsigned m = 0;
+  for (int k = 0; k < 10; k++) m |= (!free10 || free10[k]) ? 1u << k : 0u;
+  h->kd_mask = m;
+  lens_changed(h);
+  return PSBA_OK;
+}
+
+int psba_intrinsics_mask(psba_handle h, unsigned char *out10) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp == KD_CNP, "psba_intrinsics_mask: PSBA_CAMERA_FREE_KD only");
+  for (int k = 0; out10 && k < 10; k++) out10[k] = (h->kd_mask >> k) & 1u;
+  return PSBA_OK;
+}
+
 static int d2h(psba_ctx *h, void *dst, const void *src, size_t bytes);
 
 int psba_obs_sq_residuals(psba_handle h, int which, double *s) {
   CHECK_H(h);
   NEED(h, h->uploaded, "no problem uploaded");
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (not PSBA_CAMERA_FREE_K)");
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (not PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)");
   if (which != PSBA_PARAMS_CUR && which != PSBA_PARAMS_NEW) return fail(h, PSBA_E_INVALID, "%s: which = %d", __func__, which);
   if (!h->obs_s) TRY(h->obs_s.alloc(h, (size_t)h->d.nO));
   TRY(launch_residual(h, which, nullptr, h->obs_s));
@@ -416,6 +462,8 @@ static int build_point_csr(psba_ctx *h, Upload &u) {
   if (u.nC <= 0 || u.nP <= 0 || u.nO <= 0 || !u.Kparas || !u.impts || !u.initrot || !u.camsEx || !u.pts3D || !u.iidx ||
       !u.jidx)
     return fail(h, PSBA_E_INVALID, "psba_upload_problem: null pointer or non-positive size");
+  if (h->cnp == KD_CNP && (h->solver == PSBA_SOLVER_PCG || h->nranks > 1 || h->comm))
+    return fail(h, PSBA_E_STATE, "PSBA_CAMERA_FREE_KD: dense solver, single rank only");
   if (h->cnp != 6 && (h->solver == PSBA_SOLVER_PCG || h->nranks > 1 || h->comm))
     return fail(h, PSBA_E_INVALID, "free intrinsics: dense solver, single rank only");
   u.ptr.assign((size_t)u.nP + 1, 0);
@@ -458,7 +506,7 @@ static void cut_tiles(Upload &u) {
 
 // the sizes everything else is cut to, and which form K1's camera sums take
 static void set_dims(psba_ctx *h, const Upload &u) {
-  const int cnp = h->cnp;  // 6, or 11 with free intrinsics (kernels_freek.hip)
+  const int cnp = h->cnp;  // 6, 11 with free intrinsics (kernels_freek.hip) or 16 with distortion too (kernels_freekd.hip)
   Dims d;
   d.nC = u.nC;
   d.nP = u.nP;
@@ -508,7 +556,12 @@ static int alloc_work_buffers(psba_ctx *h) {
   TRY(h->ga.alloc(h, (size_t)d.nA));
   TRY(h->ga_alt.alloc(h, (size_t)d.nA));
   TRY(h->campart.alloc(h, (h->cam_global || cnp != 6) ? 1 : (size_t)(h->nPart + 1) * d.nC * CAM_ACC));  // (+1: the long points' slab)
-  if (cnp != 6) TRY(h->camacc.alloc(h, (size_t)d.nC * (cnp * (cnp + 1) / 2 + cnp)));  // kernels_freek.hip: 66 + 11 sums per camera
+  if (cnp == FK_CNP) TRY(h->camacc.alloc(h, (size_t)d.nC * (cnp * (cnp + 1) / 2 + cnp)));  // kernels_freek.hip: 66 + 11 sums per camera
+  if (cnp == KD_CNP) {  // kernels_freekd.hip (the per-unit buffers: upload_camera_index)
+    TRY(h->kd_Be.alloc(h, (size_t)8 * d.nO));
+    TRY(h->kd_Y.alloc(h, (size_t)3 * cnp * d.nO));
+    TRY(h->kd_red.alloc(h, (size_t)KD_RED));
+  }
   if (h->cam_global) TRY(h->camacc.alloc(h, (size_t)d.nC * CAM_ACC));
   // rows [0, n32 + 16) are the reduce buffer proper; n32 more rows below it are the working
   // space of the identity rows the panel chain carries along (kernels_chol_graph.hip)
@@ -525,8 +578,10 @@ static int alloc_work_buffers(psba_ctx *h) {
   return PSBA_OK;
 }
 
-// camera-major index of the observations, cut into segments of at most 256 (K1's camera sums with many cameras)
+// camera-major index of the observations, cut into segments of at most 256 (K1's camera sums with many cameras) or
+// KD_UNIT (the 16-parameter block: one observation per lane of a wave, and the units of each camera by kd_cuptr)
 static int upload_camera_index(psba_ctx *h, const Upload &u) {
+  const bool kd = h->cnp == KD_CNP;
   std::vector<int> cptr((size_t)u.nC + 1, 0), cobs((size_t)u.nO);
   for (int a = 0; a < u.nO; a++) cptr[(size_t)u.jidx[a] + 1]++;
   for (int j = 0; j < u.nC; j++) cptr[(size_t)j + 1] += cptr[j];
@@ -535,11 +590,19 @@ static int upload_camera_index(psba_ctx *h, const Upload &u) {
     for (int a = 0; a < u.nO; a++) cobs[(size_t)at[u.jidx[a]]++] = a;
   }
   std::vector<int4> units;
-  const int LSEG = 256;
-  for (int j = 0; j < u.nC; j++)
+  const int LSEG = kd ? KD_UNIT : 256;
+  std::vector<int> cuptr((size_t)u.nC + 1, 0);
+  for (int j = 0; j < u.nC; j++) {
     for (int f = cptr[j]; f < cptr[(size_t)j + 1]; f += LSEG)
       units.push_back(make_int4(j, f, std::min(f + LSEG, cptr[(size_t)j + 1]), 0));
+    cuptr[(size_t)j + 1] = (int)units.size();
+  }
   h->nCamUnits = (int)units.size();
+  if (kd) {
+    TRY(upload(h, h->kd_cuptr, cuptr));
+    TRY(h->kd_upart.alloc(h, (size_t)(KD_CNP * KD_CNP + KD_CNP) * units.size()));
+    TRY(h->kd_eapart.alloc(h, (size_t)KD_CNP * units.size()));
+  }
   TRY(upload(h, h->cam_obs, cobs));
   return upload(h, h->cam_units, units);
 }
@@ -721,13 +784,33 @@ static int plan_schur_lds(psba_ctx *h, const Upload &u) {
   return PSBA_OK;
 }
 
+// the 16-parameter block: products sorted by block, cut into segments (blockprod_plan.cpp); PSBA_FKD_SEG=n sets the
+// segment length for tests and sweeps
+static int plan_schur_blockprod(psba_ctx *h, const Upload &u) {
+  int seg = KD_SEG_DEFAULT;
+  if (const char *e = getenv("PSBA_FKD_SEG"))
+    if (atoi(e) > 0) seg = atoi(e);
+  BlockProdPlanHost plan;
+  if (build_blockprod_plan(u.nC, u.nO, u.iidx, u.jidx, u.ptr.data(), seg, plan) != PSBA_OK)
+    return fail(h, PSBA_E_INVALID, "PSBA_CAMERA_FREE_KD: more than 2^31 products Y_a W_b^T");
+  TRY(upload(h, h->kd_blocks, plan.blocks));
+  TRY(upload(h, h->kd_segs, plan.segs));
+  TRY(upload(h, h->kd_prods, plan.prods));
+  if (!plan.multi.empty()) TRY(upload(h, h->kd_multi, plan.multi));
+  TRY(h->kd_tiles.alloc(h, (size_t)256 * (plan.ntiles ? plan.ntiles : 1)));
+  h->kd_nsegs = (int)plan.segs.size();
+  h->kd_nmulti = (int)plan.multi.size();
+  return PSBA_OK;
+}
+
 static int plan_schur(psba_ctx *h, const Upload &u) {
   if (h->solver == PSBA_SOLVER_PCG) return plan_schur_sparse(h, u);
 #ifdef PSBA_BUILD_EXPERIMENTS
   TRY(plan_schur_ring(h, u));
   if (h->ring_nWg) return PSBA_OK;
 #endif
-  if (h->cnp != 6) return PSBA_OK;  // the free-intrinsics route needs no schedule (global atomics straight into S)
+  if (h->cnp == KD_CNP) return plan_schur_blockprod(h, u);
+  if (h->cnp != 6) return PSBA_OK;  // the 11-parameter route needs no schedule (global atomics straight into S)
   return plan_schur_lds(h, u);
 }
 
@@ -750,12 +833,12 @@ static int copy_inputs(psba_ctx *h, const Upload &u) {
   if (tile_desc.empty()) tile_desc.push_back(make_int4(0, 0, 0, 0));  // (only long points: an empty tile keeps the grids non-empty)
   TRY(upload(h, h->tile_desc, tile_desc));
   const double *cams = u.camsEx;
-  std::vector<double> cam11;  // free intrinsics: the camera block is (K | local rotation | translation)
+  std::vector<double> cam11;  // free intrinsics: the camera block is (K | [kc = 0: psba_set_distortion] | local rotation | translation)
   if (h->cnp != 6) {
-    cam11.resize((size_t)d.nA);
+    cam11.assign((size_t)d.nA, 0.0);
     for (int j = 0; j < u.nC; j++) {
       for (int k = 0; k < 5; k++) cam11[(size_t)h->cnp * j + k] = u.Kparas[5 * j + k];
-      for (int k = 0; k < 6; k++) cam11[(size_t)h->cnp * j + 5 + k] = u.camsEx[6 * j + k];
+      for (int k = 0; k < 6; k++) cam11[(size_t)h->cnp * j + h->cnp - 6 + k] = u.camsEx[6 * j + k];
     }
     cams = cam11.data();
   }
@@ -784,7 +867,7 @@ int psba_upload_problem(psba_handle h, int nCams, int n3Dpts, int n2Dprojs, cons
   drop_problem(h);  // from here on the handle holds no problem until this upload has succeeded
   set_dims(h, u);
   TRY(alloc_work_buffers(h));
-  if (h->cam_global) TRY(upload_camera_index(h, u));
+  if (h->cam_global || h->cnp == KD_CNP) TRY(upload_camera_index(h, u));
   TRY(plan_schur(h, u));
   TRY(copy_inputs(h, u));
   // the blocking copies went through the null stream, which this handle's non-blocking stream does not wait for:
@@ -1202,7 +1285,7 @@ static int ensure_trv(psba_ctx *h) {
 
 int psba_jmul_dots(psba_handle h, const double *x1, const double *x2, double dots[3]) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
   NEED(h, h->uploaded, "no problem uploaded");
   if (!x1 || !dots) return fail(h, PSBA_E_INVALID, "psba_jmul_dots: null pointer");
   TRY(ensure_trv(h));
@@ -1297,7 +1380,7 @@ int psba_allreduce_scalars(psba_handle h, double *v, int n) {
 
 int psba_compute_Jmultiply(psba_handle h, const double *x, double *Jmul) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
   NEED(h, h->uploaded, "no problem uploaded");
   if (!x) return fail(h, PSBA_E_INVALID, "psba_compute_Jmultiply: null pointer");
   TRY(ensure_trv(h));
@@ -1309,7 +1392,17 @@ int psba_compute_Jmultiply(psba_handle h, const double *x, double *Jmul) {
 
 int psba_get_gradient(psba_handle h, double *g) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
+  if (h->cnp == KD_CNP) {  // a copy: g_a as stored, g_b,i from the tail of each point's record
+    NEED(h, h->linearized, "psba_linearize first");
+    if (!g) return PSBA_E_INVALID;
+    TRY(d2h(h, g, h->ga, sizeof(double) * (size_t)h->d.nA));
+    std::vector<double> pv((size_t)9 * h->d.nP);
+    TRY(d2h(h, pv.data(), h->PV, sizeof(double) * pv.size()));
+    for (int i = 0; i < h->d.nP; i++)
+      for (int k = 0; k < 3; k++) g[h->d.nA + 3 * (size_t)i + k] = pv[(size_t)9 * i + 6 + k];
+    return PSBA_OK;
+  }
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
   NEED(h, h->linearized, "psba_linearize first");
   if (!g) return PSBA_E_INVALID;
   TRY(ensure_trv(h));
@@ -1327,7 +1420,7 @@ int psba_get_dp(psba_handle h, double *dp) {
 
 int psba_set_step(psba_handle h, const double *dp) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
   NEED(h, h->uploaded, "no problem uploaded");
   if (!dp) return PSBA_E_INVALID;
   PSBA_HIP(h, hipMemcpyAsync(h->dp, dp, sizeof(double) * (size_t)h->d.nT, hipMemcpyHostToDevice, h->stream));
@@ -1339,7 +1432,7 @@ int psba_set_step(psba_handle h, const double *dp) {
 
 int psba_cholmod_lambda(psba_handle h, int reassemble, double *lambda, double *info3) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
   NEED(h, h->uploaded, "no problem uploaded");
   if (h->nranks > 1 && !h->comm)
     return fail(h, PSBA_E_INVALID, "psba_cholmod_lambda on a rank layout needs the communicator (S must be complete)");
@@ -1441,7 +1534,7 @@ int psba_compute_jacobiQT(psba_handle h, double *jac_A, double *jac_B) {
 
 int psba_compute_U(psba_handle h, double coeff, double *out) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
   NEED(h, h->uploaded, "no problem uploaded");
   h->coeff = coeff;
   TRY(relinearize_dump(h));
@@ -1464,7 +1557,7 @@ static int download_V(psba_ctx *h, double *out, double mu) {
 
 int psba_compute_V(psba_handle h, double coeff, double *out) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
   NEED(h, h->uploaded, "no problem uploaded");
   h->coeff = coeff;
   TRY(relinearize_dump(h));
@@ -1475,7 +1568,7 @@ int psba_maxElmOfUV(psba_handle h, double *out) { return psba_max_diag(h, out); 
 
 int psba_update_UV(psba_handle h, double mu, double *U, double *V) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
   NEED(h, h->linearized, "linearise first");
   h->mu = mu;
   h->mu_applied = true;
@@ -1502,7 +1595,7 @@ int psba_compute_Vinv(psba_handle h, double *Vinv) {
 
 int psba_compute_Wblks(psba_handle h, double coeff, double *Wblks) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
   NEED(h, h->uploaded, "no problem uploaded");
   h->coeff = coeff;
   TRY(relinearize_dump(h));
@@ -1527,7 +1620,7 @@ int psba_compute_S(psba_handle h, double *S) {
 
 int psba_compute_g(psba_handle h, double coeff, double *g) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
+  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
   NEED(h, h->uploaded, "no problem uploaded");
   h->coeff_g = coeff;
   TRY(relinearize_dump(h));
@@ -1651,7 +1744,7 @@ int psba_comm_init(psba_handle h, int nranks, int rank, const void *id128) {
 
 int psba_set_rank_layout(psba_handle h, int nranks, int rank) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6 || nranks <= 1, "free intrinsics: single rank only");
+  NEED(h, h->cnp == 6 || nranks <= 1, "free intrinsics (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD): single rank only");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, PSBA_E_INVALID, "bad rank %d / %d", rank, nranks);
   if (h->comm) return fail(h, PSBA_E_STATE, "a communicator is attached: its layout is fixed");
   if (h->solver == PSBA_SOLVER_PCG && h->uploaded && nranks != h->nranks)
@@ -1686,7 +1779,7 @@ int psba_get_reduce_buffer(psba_handle h, double *out) {
 
 int psba_set_reduce_buffer(psba_handle h, const double *in) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (free intrinsics: the fused verbs and psba_levmar)");
+  NEED(h, h->cnp == 6 || h->cnp == KD_CNP, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
   NEED(h, h->assembled, "psba_schur_assemble first");
   NEED(h, !h->comm, "the reduce-buffer verbs are for handles without a communicator");
   NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");

@@ -142,6 +142,20 @@ struct SchurPlanHost {
   long long tasks = 0;
   long long pair_items = 0;  // rows layout: items that carry two products of one observation (SchurWg::itemD)
 };
+// ---- the 16-parameter camera block (PSBA_CAMERA_FREE_KD, kernels_freekd.hip): the products Y_a W_b^T, b <= a of one
+// point, sorted by block (j_a, j_b) of the lower block triangle and inside a block by point; every block's list cut
+// into segments of at most seg_len products (one wave each).  blockprod_plan.cpp, host only
+struct BlockProdPlanHost {
+  std::vector<int2> blocks;  // (j, k), k <= j, ascending by (j, k): the blocks with at least one product
+  std::vector<int4> segs;    // (block, first product, end product, partial tile or -1: the block's only segment)
+  std::vector<int2> prods;   // (a, b) observation indices
+  std::vector<int4> multi;   // the blocks with several segments: (j, k, first partial tile, tiles)
+  int ntiles = 0;            // partial tiles (16 x 16 doubles each)
+  int seg_len = 0;
+};
+constexpr int KD_UNIT = 64;        // observations of a camera unit on this route: one wave, one observation per lane
+constexpr int KD_SEG_DEFAULT = 64; // products per segment (PSBA_FKD_SEG overrides)
+constexpr int KD_RED = 4 * 520;    // doubles of the reduction scratch: camera terms | up to 512 workgroups x 4 sums
 constexpr int RUN_THREADS = 512;  // threads of a workgroup of k_schur_lds_runs: 192 VGPRs with the 36 accumulators, two waves per SIMD (768 threads = 168 VGPRs spill 27 registers: 85 against 59 us)
 constexpr int RUN_MAX = 32;       // products a lane sums in registers before it touches the LDS at the latest
 }  // namespace psba
@@ -271,6 +285,18 @@ struct ProblemState {
   psba::DevBuf<psba::OwnerUnit> own_units;
   int own_nwaves = 0;
   long long own_products = 0;
+  // the 16-parameter camera block (PSBA_CAMERA_FREE_KD, kernels_freekd.hip): no floating-point atomics on this route
+  unsigned kd_mask = 0x3FFu;       // psba_set_intrinsics_mask: bit k set = intrinsic k is optimised
+  psba::DevBuf<int> kd_cuptr;      // [nC+1] the units cam_units[kd_cuptr[j] .. kd_cuptr[j+1]) of camera j
+  psba::DevBuf<double> kd_Be;      // [nO][8] B (2 x 3) | e of the linearization in flight (read by the per-point pass)
+  psba::DevBuf<double> kd_upart;   // [nCamUnits][272] per-unit sums A^T A (16 x 16) | A^T e
+  psba::DevBuf<double> kd_Y;       // [nO][48] Y_a = W_a (V_i + mu I)^-1 of the try
+  psba::DevBuf<double> kd_eapart;  // [nCamUnits][16] per-unit sums Y_a g_b,i
+  psba::DevBuf<int2> kd_blocks, kd_prods;  // BlockProdPlanHost on the device
+  psba::DevBuf<int4> kd_segs, kd_multi;
+  psba::DevBuf<double> kd_tiles;   // [ntiles][256] partial tiles of the blocks with several segments
+  int kd_nsegs = 0, kd_nmulti = 0;
+  psba::DevBuf<double> kd_red;     // [KD_RED] per-workgroup partial sums (cost; the try's four sums)
   psba::DevBuf<double> dp;        // [nT] dpa | dpb                     (dp_buffer)
   psba::DevBuf<double> trv[2];    // [nT] each: vectors of the trust-region operators (allocated on first use)
   psba::DevBuf<double> jmul_out;  // [2 nO] J x of psba_compute_Jmultiply (allocated on first use)
@@ -319,7 +345,7 @@ struct psba_ctx : ProblemState {
   std::vector<hipEvent_t> chol_events;  // the look-ahead of the blocked Cholesky chain (two per super-panel)
 
   int solver = 0;               // PSBA_SOLVER_* (block-sparse S + preconditioned CG: psba_set_solver, kernels_pcg.hip)
-  int cnp = 6;  // parameters per camera: 6 (fixed intrinsics, the reference's kernels) or 11 (psba_set_camera_model: free intrinsics)
+  int cnp = 6;  // parameters per camera: 6 (fixed intrinsics, the reference's kernels), 11 (psba_set_camera_model: free intrinsics) or 16 (free intrinsics and distortion)
   double pcg_tol = 1e-10;
   int pcg_maxit = 500;
   psba::PinnedBuf<double> pcg_host;       // pinned mirror of the PCG's device scalars (allocated by the first PCG upload)
@@ -395,6 +421,14 @@ int launch_residual_fk(psba_ctx *h, int which);
 int launch_max_diag_fk(psba_ctx *h);
 int launch_schur_fk(psba_ctx *h, double mu);
 int launch_backsub_fk(psba_ctx *h, double mu);
+// kernels_freekd.hip: the 16-parameter camera block (free intrinsics and distortion), MFMA sums in fixed order
+int build_blockprod_plan(int nCams, int nObs, const int *iidx, const int *jidx, const int *ptr, int seg_len,
+                         BlockProdPlanHost &out);  // blockprod_plan.cpp
+int launch_linearize_kd(psba_ctx *h, bool ahead, bool publish);
+int launch_residual_kd(psba_ctx *h, int which);
+int launch_max_diag_kd(psba_ctx *h);
+int launch_schur_kd(psba_ctx *h, double mu);
+int launch_backsub_kd(psba_ctx *h, double mu);
 // kernels_pcg.hip
 int launch_bsr_finalize(psba_ctx *h, double mu);
 int launch_pcg_solve(psba_ctx *h);

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "camera_model.h"
 #include "psba_internal.h"
 
 extern "C" int psba_jmul_dots(psba_handle h, const double *x1, const double *x2, double dots[3]);
@@ -102,7 +103,8 @@ void psba_tr_default_options(psba_tr_options *o) {
 
 int psba_trust_region(psba_handle h, const psba_tr_options *opts, psba_tr_result *res, double *log) {
   if (!h || !opts || !res) return PSBA_E_INVALID;
-  if (h->cnp != 6) return PSBA_E_STATE;  // free intrinsics: psba_levmar only (include/psba_hip.h)
+  if (h->cnp != 6)  // free intrinsics: psba_levmar only (include/psba_hip.h)
+    return psba::fail(h, PSBA_E_STATE, "psba_trust_region: six-parameter camera blocks only (not PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)");
   const double EPS2 = 1e-12, MAX_DELTA = 10000;  // psba.h:9, trust_region.cpp:18
   *res = psba_tr_result();
   auto t_begin = std::chrono::steady_clock::now();
@@ -280,6 +282,8 @@ int psba_trust_region(psba_handle h, const psba_tr_options *opts, psba_tr_result
 // hands back (ITER_TURN_TO_LM); itno is shared and capped at max_iter in total.
 int psba_solve(psba_handle h, int max_iter, int verbose, psba_solve_result *res) {
   if (!h || !res) return PSBA_E_INVALID;
+  if (h->cnp == psba::KD_CNP)
+    return psba::fail(h, PSBA_E_STATE, "psba_solve: not under PSBA_CAMERA_FREE_KD (psba_levmar; the trust-region operators are six-parameter only)");
   *res = psba_solve_result();
   auto t_begin = std::chrono::steady_clock::now();
   int itno = 0, flag = PSBA_ITER_CONTINUE;

@@ -1,0 +1,81 @@
+"""ms per LM iteration and the per-class kernel times of psba_profile_get (linearize, S assembly, Cholesky,
+back-substitution) with camera blocks of 11 (PSBA_CAMERA_FREE_K) and of 16 (PSBA_CAMERA_FREE_KD: all ten intrinsics
+free, and the mask of Bundle Adjustment in the Large), on 54camsvarK / 54pts and on the venice-shaped problem.  The
+variants are alternated within one process (one LM run of each per round), so that drift of the machine hits all of
+them alike.  --seg sweeps the segment length of the 16-block S assembly (PSBA_FKD_SEG, read at upload).
+Usage: python scripts/freekd_time.py [--rounds N] [--iters N] [--seg 16,64,256] [--problem p54|venice|both]"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import psba_amd  # noqa: E402
+from psba_amd import synth  # noqa: E402
+
+CLASSES = [("linearize", 0), ("S assembly", 1), ("Cholesky", 2), ("back-subst.", 3)]
+
+
+def open_handle(prob, model, free, seg):
+    if seg:
+        os.environ["PSBA_FKD_SEG"] = str(seg)
+    else:
+        os.environ.pop("PSBA_FKD_SEG", None)
+    h = psba_amd.Psba(0)
+    h.set_camera_model(model)
+    h.upload_problem(prob)
+    if model == psba_amd.CAMERA_FREE_KD:
+        h.set_intrinsics_mask(free)
+    return h
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--seg", default="")
+    ap.add_argument("--problem", default="both")
+    args = ap.parse_args()
+    data = os.path.join(ROOT, "tests", "golden", "data")
+    probs = []
+    if args.problem in ("p54", "both"):
+        probs.append(("54camsvarK", psba_amd.read_problem(os.path.join(data, "54camsvarK.txt"), os.path.join(data, "54pts.txt"))))
+    if args.problem in ("venice", "both"):
+        probs.append(("venice-shaped", synth.venice_shaped()))
+    segs = [int(s) for s in args.seg.split(",") if s] or [0]
+    for pname, prob in probs:
+        print(f"{pname}: {prob['nC']} cameras, {prob['nP']} points, {prob['nO']} observations; {args.iters} LM iterations "
+              f"per run, {args.rounds} rounds (+1 warm-up)", flush=True)
+        variants = [("FREE_K (11)", psba_amd.CAMERA_FREE_K, None, 0)]
+        for s in segs:
+            tag = f" L={s}" if s else ""
+            variants.append((f"FREE_KD all free{tag}", psba_amd.CAMERA_FREE_KD, None, s))
+            variants.append((f"FREE_KD f,k1,k2{tag}", psba_amd.CAMERA_FREE_KD, psba_amd.INTRINSICS_BAL, s))
+        handles = [(name, open_handle(prob, model, free, s)) for name, model, free, s in variants]
+        ms = {name: [] for name, _ in handles}
+        for rnd in range(args.rounds + 1):
+            for name, h in handles:
+                h.reset_params()
+                res, _ = h.levmar(max_iter=args.iters)
+                if rnd:  # round 0 warms up
+                    ms[name].append(1e3 * res.seconds / max(res.tries, 1))
+        for name, h in handles:
+            h.reset_params()
+            h.profile_enable(True)
+            h.profile_reset()
+            res, _ = h.levmar(max_iter=args.iters)
+            parts = []
+            for cn, ck in CLASSES:
+                t, n = h.profile_get(ck)
+                parts.append(f"{cn} {1e3 * t / max(res.tries, 1):.1f} us")
+            h.profile_enable(False)
+            print(f"  {name:26s} ms/try median {np.median(ms[name]):.4f} (min {min(ms[name]):.4f} max {max(ms[name]):.4f}); "
+                  f"per try: " + "  ".join(parts) + f"  [{res.tries} tries, cost {res.init_err:.4e} -> {res.final_err:.4e}]",
+                  flush=True)
+            h.close()
+
+
+if __name__ == "__main__":
+    main()

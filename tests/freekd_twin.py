@@ -1,0 +1,280 @@
+"""Independent (test-only) numpy twin of PSBA_CAMERA_FREE_KD: camera blocks of 16 parameters
+(fu, u0, v0, ar, s | k1, k2, k3, k4, k5 | v0, v1, v2 | t0, t1, t2) with a mask over the ten intrinsics.
+
+Built on lens_twin.Twin (projection, the six extrinsic columns and B); this file adds the ten intrinsic columns
+(include/psba_hip.h): with (x, y) the normalised point, r2 = x^2 + y^2, (xd, yd) the distorted point,
+    d(u, v) / d(fu, u0, v0, ar, s) = [ xd, 1, 0, 0, yd ;  ar yd, 0, 1, fu yd, 0 ]
+    d xd / d(k1..k5) = (r2 x, r2^2 x, 2 x y, r2 + 2 x^2, r2^3 x)
+    d yd / d(k1..k5) = (r2 y, r2^2 y, r2 + 2 y^2, 2 x y, r2^3 y)
+    d u / dk = fu d xd + s d yd,   d v / dk = fu ar d yd
+a dense J, N = J^T J with the placeholder 1 on the diagonal of masked coordinates, S and e_a by a dense solve of the
+point block, and a dense LM that restates the damping and accept rules of psba_amd/csrc/lm_loop.cpp.  Formulated
+differently from the HIP route on purpose: one dense matrix, no blocks, no Schur elimination inside the LM.
+"""
+import numpy as np
+
+import lens_twin
+
+CNP = 16
+BAL = (1, 0, 0, 0, 0, 1, 1, 0, 0, 0)
+
+
+class LmResult:
+    pass
+
+
+class TwinKD:
+    """prob: Problem / dict (K, initrot, cams, pts, impts, iidx, jidx); kc [nC, 5] starting distortion or None;
+    free [10] the intrinsics mask (non-zero = optimised), None = all free."""
+
+    def __init__(self, prob, kc=None, free=None):
+        self.t = lens_twin.Twin(prob, kc)
+        t = self.t
+        self.nC, self.nP, self.nO = t.nC, t.nP, t.nO
+        self.i, self.j = t.i, t.j
+        self.cams = np.hstack([t.K, t.kc, t.cams]).copy()  # [nC, 16]
+        self.pts = t.pts.copy()
+        self.free = np.ones(10, dtype=bool) if free is None else (np.asarray(free).reshape(10) != 0)
+        self.nA, self.nB = CNP * self.nC, 3 * self.nP
+        self.nT = self.nA + self.nB
+        # per coordinate of the camera part: is it optimised?
+        self.free_a = np.tile(np.r_[self.free, np.ones(6, dtype=bool)], self.nC)
+
+    def _set(self, cams, pts):
+        cams = self.cams if cams is None else np.asarray(cams, dtype=np.float64).reshape(self.nC, CNP)
+        pts = self.pts if pts is None else np.asarray(pts, dtype=np.float64).reshape(self.nP, 3)
+        self.t.K, self.t.kc = cams[:, :5], cams[:, 5:10]
+        return cams, pts
+
+    def residual(self, cams=None, pts=None):
+        cams, pts = self._set(cams, pts)
+        return self.t.m - self.t.project(cams[:, 10:], pts)
+
+    def cost(self, cams=None, pts=None):
+        e = self.residual(cams, pts)
+        return float((e * e).sum())
+
+    def linearize(self, cams=None, pts=None, masked=True):
+        """e [nO, 2], A [nO, 2, 16] (masked columns zero), B [nO, 2, 3]: derivatives of the projection"""
+        cams, pts = self._set(cams, pts)
+        proj, A6, B = self.t.project(cams[:, 10:], pts, jac=True)
+        e = self.t.m - proj
+        c, M = cams[self.j], pts[self.i]
+        s, u, _ = lens_twin._quat(self.t.q0[self.j], c[:, 10:13])
+        P = np.einsum("nab,nb->na", lens_twin._rot(s, u), M) + c[:, 13:]
+        x, y = P[:, 0] / P[:, 2], P[:, 1] / P[:, 2]
+        xd, yd, _ = lens_twin.distort(c[:, 5:10], x, y)
+        fu, ar, sk = c[:, 0], c[:, 3], c[:, 4]
+        r2 = x * x + y * y
+        A = np.zeros((self.nO, 2, CNP))
+        A[:, 0, 0], A[:, 0, 1], A[:, 0, 4] = xd, 1.0, yd
+        A[:, 1, 0], A[:, 1, 2], A[:, 1, 3] = ar * yd, 1.0, fu * yd
+        dxd = np.stack([r2 * x, r2 ** 2 * x, 2 * x * y, r2 + 2 * x * x, r2 ** 3 * x], 1)
+        dyd = np.stack([r2 * y, r2 ** 2 * y, r2 + 2 * y * y, 2 * x * y, r2 ** 3 * y], 1)
+        A[:, 0, 5:10] = fu[:, None] * dxd + sk[:, None] * dyd
+        A[:, 1, 5:10] = (fu * ar)[:, None] * dyd
+        A[:, :, 10:] = A6
+        if masked:
+            A[:, :, :10] *= self.free[None, None, :]
+        return e, A, B
+
+    def jacobian(self, masked=True):
+        """dense J [2 nO, nA + nB] of the projection (columns: cameras, then points)"""
+        e, A, B = self.linearize(masked=masked)
+        J = np.zeros((2 * self.nO, self.nT))
+        for a in range(self.nO):
+            J[2 * a:2 * a + 2, CNP * self.j[a]:CNP * self.j[a] + CNP] = A[a]
+            J[2 * a:2 * a + 2, self.nA + 3 * self.i[a]:self.nA + 3 * self.i[a] + 3] = B[a]
+        return e, J
+
+    def normal(self):
+        """(cost, N = J^T J with 1 on the diagonal of masked coordinates, g = J^T e)"""
+        e, J = self.jacobian()
+        N = J.T @ J
+        held = np.flatnonzero(~self.free_a)
+        N[held, held] = 1.0
+        return float((e * e).sum()), N, J.T @ e.reshape(-1)
+
+    def max_diag(self, N):
+        d = np.diag(N).copy()
+        d[:self.nA][~self.free_a] = 0.0
+        return d.max()
+
+    def schur(self, N, g, mu):
+        """S = U* - W V*^-1 W^T, e_a = g_a - W V*^-1 g_b by a dense solve of the (damped) point block"""
+        nA = self.nA
+        Nbb = N[nA:, nA:] + mu * np.eye(self.nB)
+        X = np.linalg.solve(Nbb, np.c_[N[:nA, nA:].T, g[nA:]])
+        S = N[:nA, :nA] + mu * np.eye(nA) - N[:nA, nA:] @ X[:, :nA]
+        ea = g[:nA] - N[:nA, nA:] @ X[:, nA]
+        return S, ea
+
+    def schur_blocks(self, mu, dtype=np.longdouble):
+        """The same S and e_a from the fp64 Jacobian blocks with every sum in `dtype` (80-bit by default), block by
+        block: what the fp64 twin's own rounding is measured against."""
+        e, A, B = self.linearize()
+        e, A, B = e.astype(dtype), A.astype(dtype), B.astype(dtype)
+        nC, nP = self.nC, self.nP
+        U = np.zeros((nC, CNP, CNP), dtype)
+        ga = np.zeros((nC, CNP), dtype)
+        np.add.at(U, self.j, np.einsum("nri,nrk->nik", A, A))
+        np.add.at(ga, self.j, np.einsum("nri,nr->ni", A, e))
+        V = np.zeros((nP, 3, 3), dtype)
+        gb = np.zeros((nP, 3), dtype)
+        np.add.at(V, self.i, np.einsum("nri,nrk->nik", B, B))
+        np.add.at(gb, self.i, np.einsum("nri,nr->ni", B, e))
+        W = np.einsum("nri,nrk->nik", A, B)
+        S = np.zeros((self.nA, self.nA), dtype)
+        ea = ga.reshape(-1).copy()
+        for j in range(nC):
+            Uj = U[j].copy()
+            for k in np.flatnonzero(~self.free):
+                Uj[k, k] = 1
+            S[CNP * j:CNP * j + CNP, CNP * j:CNP * j + CNP] = Uj + dtype(mu) * np.eye(CNP, dtype=dtype)
+        order = np.argsort(self.i, kind="stable")
+        bounds = np.searchsorted(self.i[order], np.arange(nP + 1))
+        for i in range(nP):
+            obs = order[bounds[i]:bounds[i + 1]]
+            if obs.size == 0:
+                continue
+            # Y = W (V + mu I)^-1 by L D L^T and substitution: backward stable per row, so a nearly singular block
+            # (a point seen once, small mu) does not amplify rounding the way a product with its inverse would
+            v = V[i] + dtype(mu) * np.eye(3, dtype=dtype)
+            l10, l20 = v[0, 1] / v[0, 0], v[0, 2] / v[0, 0]
+            d1 = v[1, 1] - l10 * v[0, 1]
+            l21 = (v[1, 2] - l20 * v[0, 1]) / d1
+            d2 = v[2, 2] - l20 * v[0, 2] - l21 * l21 * d1
+            Wi = W[obs].reshape(-1, 3)                 # rows: (observation, parameter)
+            z1 = Wi[:, 1] - l10 * Wi[:, 0]
+            z2 = Wi[:, 2] - l20 * Wi[:, 0] - l21 * z1
+            y2 = z2 / d2
+            y1 = z1 / d1 - l21 * y2
+            Yi = np.stack([Wi[:, 0] / v[0, 0] - l10 * y1 - l20 * y2, y1, y2], 1)
+            rows = (CNP * self.j[obs][:, None] + np.arange(CNP)[None, :]).reshape(-1)
+            S[np.ix_(rows, rows)] -= Yi @ Wi.T
+            ea[rows] -= Yi @ gb[i]
+        return S, ea
+
+    def levmar(self, max_iter=20, init_mu=0.0, stop_small=True):
+        """psba_amd/csrc/lm_loop.cpp restated (tr_handoff off): Nielsen's mu / nu update, the same stop tests, one
+        log row (itno, cost after the try, rho, mu, accepted) per damping try.  stop_small=False leaves out the
+        loop's absolute stop (cost <= 1e-12), which ends a noise-free problem before fp64 is used up."""
+        STOP, EPS_SQ = 1e-12, 1e-24
+        tau = init_mu if init_mu != 0.0 else 1e-3
+        res, log = LmResult(), []
+        ex, N, g = self.normal()
+        res.init_err = ex
+        mu, nu, p_L2, first, flag, tries = 0.0, 2, 0.0, True, 0, 0
+        itno = 0
+        while itno < max_iter and flag == 0:
+            if not first:
+                _, N, g = self.normal()
+            else:
+                mu, p_L2, nu, first = tau * self.max_diag(N), 1e3, 2, False
+                res.mu0 = mu
+            while True:
+                tries += 1
+                try:
+                    L = np.linalg.cholesky(N + mu * np.eye(self.nT))
+                    dp = np.linalg.solve(L.T, np.linalg.solve(L, g))
+                except np.linalg.LinAlgError:
+                    dp = None
+                if dp is not None:
+                    dp[:self.nA][~self.free_a] = 0.0
+                    dp_L2 = float(dp @ dp)
+                    if dp_L2 < p_L2 * STOP * STOP:
+                        flag = 1
+                        break
+                    if dp_L2 >= (p_L2 + STOP) / EPS_SQ:
+                        flag = 2
+                        break
+                    newc = self.cams + dp[:self.nA].reshape(self.nC, CNP)
+                    newp = self.pts + dp[self.nA:].reshape(self.nP, 3)
+                    new_ex = self.cost(newc, newp)
+                    rho = (ex - new_ex) / float(dp @ (mu * dp + g))
+                    log.append([itno, new_ex, rho, mu, 1.0 if rho > 0 else 0.0])
+                    if rho > 0:
+                        tmp = 2 * rho - 1
+                        tmp = 1.0 - tmp * tmp * tmp
+                        mu *= tmp if tmp >= 1.0 / 3.0 else 1.0 / 3.0
+                        nu = 2
+                        self.cams, self.pts = newc, newp
+                        p_L2 = float((newc * newc).sum() + (newp * newp).sum())
+                        ex = new_ex
+                        break
+                else:
+                    log.append([itno, np.nan, np.nan, mu, -1.0])
+                mu *= nu
+                if 2.0 * nu > 1e9:
+                    flag = 2
+                    break
+                nu *= 2
+            if stop_small and ex <= STOP:
+                flag = 3
+            itno += 1
+        res.flag, res.iters, res.tries, res.final_err, res.mu_final = flag, itno, tries, ex, mu
+        return res, np.asarray(log).reshape(-1, 5)
+
+
+# ---- the test problems of tests/test_freekd_*.py ----
+def start_kc(nC):
+    """(2e-2, -5e-3, 1e-3, -1e-3, 1e-3) (1 + 0.1 N(0, 1)) per camera, default_rng(1)"""
+    rng = np.random.default_rng(1)
+    return np.array([2e-2, -5e-3, 1e-3, -1e-3, 1e-3]) * (1.0 + 0.1 * rng.standard_normal((nC, 5)))
+
+
+def _rot_to_quat(R):
+    """unit quaternion (s, u) with R'(q) = R (R a rotation, trace > -1)"""
+    s = 0.5 * np.sqrt(1.0 + np.trace(R))
+    u = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]) / (4.0 * s)
+    return np.r_[s, u]
+
+
+def tiny_problem():
+    """2 cameras, 3 points: point 0 seen by both, point 1 by camera 0 only, point 2 by camera 1 only."""
+    rng = np.random.default_rng(5)
+    pts = np.array([[0.1, -0.2, 0.3], [-0.4, 0.3, -0.1], [0.5, 0.2, 0.2]])
+    K = np.array([[800.0, 3.0, -2.0, 1.01, 0.5], [820.0, -1.0, 4.0, 0.99, -0.3]])
+    q0 = np.array([[1.0, 0, 0, 0], [np.cos(0.1), 0, np.sin(0.1), 0]])
+    cams = np.array([[0.01, -0.02, 0.005, 0.1, -0.1, 5.0], [-0.01, 0.015, 0.02, -0.2, 0.1, 5.5]])
+    iidx, jidx = np.array([0, 0, 1, 2], dtype=np.int32), np.array([0, 1, 0, 1], dtype=np.int32)
+    prob = dict(K=K, initrot=q0, cams=cams, pts=pts, impts=np.zeros((4, 2)), iidx=iidx, jidx=jidx, nC=2, nP=3, nO=4)
+    prob["impts"] = lens_twin.Twin(prob, start_kc(2)).project() + rng.standard_normal((4, 2))
+    return prob
+
+
+def ring_problem(seed=7):
+    """6 cameras at radius 5 looking at the origin, 120 points uniform in [-1, 1]^3, 30 % of the observations dropped
+    (not those of cameras 0 and 1); exact projections with K = (800 (1 + 0.05 N), 0, 0, 1, 0) and kc = (-0.05, 0.01,
+    0, 0, 0) (1 + 0.2 N).  Returns (start problem, start kc = 0, true K [6, 5], true kc [6, 5])."""
+    rng = np.random.default_rng(seed)
+    nC, nP = 6, 120
+    pts = rng.uniform(-1.0, 1.0, (nP, 3))
+    q0, t = np.zeros((nC, 4)), np.zeros((nC, 3))
+    for j in range(nC):
+        th = 2.0 * np.pi * j / nC
+        centre = 5.0 * np.array([np.cos(th), 0.0, np.sin(th)])
+        z = -centre / np.linalg.norm(centre)
+        x = np.cross([0.0, 1.0, 0.0], z)
+        x /= np.linalg.norm(x)
+        R = np.stack([x, np.cross(z, x), z])      # rows: camera axes in world coordinates
+        q0[j] = _rot_to_quat(R)
+        t[j] = -R @ centre
+    K = np.zeros((nC, 5))
+    K[:, 0] = 800.0 * (1.0 + 0.05 * rng.standard_normal(nC))
+    K[:, 3] = 1.0
+    kc = np.array([-0.05, 0.01, 0.0, 0.0, 0.0]) * (1.0 + 0.2 * rng.standard_normal((nC, 5)))
+    keep = rng.uniform(size=(nP, nC)) >= 0.3
+    keep[:, :2] = True
+    iidx, jidx = np.nonzero(keep)
+    cams = np.hstack([np.zeros((nC, 3)), t])
+    true = dict(K=K, initrot=q0, cams=cams, pts=pts, impts=np.zeros((iidx.size, 2)), iidx=iidx.astype(np.int32),
+                jidx=jidx.astype(np.int32), nC=nC, nP=nP, nO=int(iidx.size))
+    impts = lens_twin.Twin(true, kc).project()
+    Ks = K.copy()
+    Ks[:, 0] *= 1.03
+    cs = cams.copy()
+    cs[:, :3] += 0.005 * rng.standard_normal((nC, 3))
+    cs[:, 3:] += 0.02 * rng.standard_normal((nC, 3))
+    start = dict(true, K=Ks, cams=cs, pts=pts + 0.02 * rng.standard_normal((nP, 3)), impts=impts)
+    return start, np.zeros((nC, 5)), K, kc
