@@ -135,7 +135,9 @@ __global__ __launch_bounds__(256) void k_fk_max_diag(const double *U, const doub
   }
 }
 
-// S (lower block triangle) -= Y_a W_b^T, e_a -= Y_a g_b,i; thread per observation a, partners b <= a of its point
+// S (lower block triangle) -= Y_a W_b^T, e_a -= Y_a g_b,i; thread per observation a, partners b <= a of its point.
+// Y_a = W_a (V_i + mu I)^-1 by L D L^T and substitution, as k_kd_Y forms it: the closed-form inverse loses the points
+// seen once at a small mu
 __global__ __launch_bounds__(256) void k_fk_schur(const double *W, const double *PV, const int *iidx, const int *jidx,
                                                   const int *ptr, double *S, double *ea, int ld, double mu, int nO,
                                                   int *status, int try_id) {
@@ -148,16 +150,14 @@ __global__ __launch_bounds__(256) void k_fk_schur(const double *W, const double 
     v[0] += mu;
     v[3] += mu;
     v[5] += mu;
-    if (sym3_inverse(v, vi)) status[0] = try_id;
+    if (sym3_inverse(v, vi)) status[0] = try_id;  // (the singular flag as on the other routes; Y by substitution)
+    const Sym3Ldl f = sym3_ldl(v);
     const double g0 = pv[6], g1 = pv[7], g2 = pv[8];
     const double *w = W + FK_W * (size_t)a;
     double Y[FK_W];
 #pragma unroll
     for (int r = 0; r < FK_CNP; r++) {
-      const double w0 = w[3 * r], w1 = w[3 * r + 1], w2 = w[3 * r + 2];
-      Y[3 * r] = w0 * vi[0] + w1 * vi[1] + w2 * vi[2];
-      Y[3 * r + 1] = w0 * vi[1] + w1 * vi[3] + w2 * vi[4];
-      Y[3 * r + 2] = w0 * vi[2] + w1 * vi[4] + w2 * vi[5];
+      sym3_ldl_solve(f, w[3 * r], w[3 * r + 1], w[3 * r + 2], Y[3 * r], Y[3 * r + 1], Y[3 * r + 2]);
       atomicAdd(&ea[FK_CNP * ja + r], -(Y[3 * r] * g0 + Y[3 * r + 1] * g1 + Y[3 * r + 2] * g2));
     }
     for (int b = ptr[i]; b <= a; b++) {
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void k_fk_finalize(double *S, double *ea, cons
   write_padding(S, nA, n32, 1.0, gtid, gsize);
 }
 
-// back-substitution, thread per point: e_b,i = g_b,i - sum_j W_ij^T dpa_j, dpb_i = V*_i^-1 e_b,i, proposed point;
+// back-substitution, thread per point: e_b,i = g_b,i - sum_j W_ij^T dpa_j, V*_i dpb_i = e_b,i (L D L^T), proposed point;
 // then the residuals of its observations at the proposal; the four sums of the try as k_backsub forms them
 struct FkBackArgs {
   const double *W, *PV, *camconst, *cams, *pts, *impts, *ga;
@@ -254,15 +254,13 @@ __global__ __launch_bounds__(256) void k_fk_backsub_pts(FkBackArgs p) {
         e2 -= w[3 * k + 2] * da[k];
       }
     }
-    double v[6], vi[6];
+    double v[6], d[3];
 #pragma unroll
     for (int k = 0; k < 6; k++) v[k] = pv[k];
     v[0] += p.mu;
     v[3] += p.mu;
     v[5] += p.mu;
-    sym3_inverse(v, vi);
-    const double d[3] = {vi[0] * e0 + vi[1] * e1 + vi[2] * e2, vi[1] * e0 + vi[3] * e1 + vi[4] * e2,
-                         vi[2] * e0 + vi[4] * e1 + vi[5] * e2};
+    sym3_ldl_solve(sym3_ldl(v), e0, e1, e2, d[0], d[1], d[2]);
     double n3[3];
 #pragma unroll
     for (int q = 0; q < 3; q++) {

@@ -1,0 +1,285 @@
+"""Host judges of the two free-intrinsics routes (PSBA_CAMERA_FREE_K, camera blocks of 11, and PSBA_CAMERA_FREE_KD,
+blocks of 16) for one damping try, entry by entry (no GPU): tests/test_free_entrywise_ref.py applies them to a plain
+fp64 numpy evaluation and to injected faults, tests/test_gpu_free_entrywise.py to the kernels.
+
+The reference is the numpy twin tests/freekd_twin.py: its fp64 Jacobian blocks e, A, B with every sum in extended
+precision (np.longdouble, assembly_ref.LD).  The 11-block route is TwinKD(p, None, K_ONLY) restricted to the columns
+SEL11 = (0..4, 10..15) of every camera.  Notation, gamma(k) and u = 2^-53 + 2^-63 are assembly_ref's; every bound is
+built from the entry's own terms, none from the maximum of an array, and no constant is fitted to a GPU result.
+
+S and e_a (C1) use the scaled measure of test_gpu_freekd.py: |dS_rc| <= tol d_r d_c, |de_a,r| <= tol d_r sqrt(cost),
+d = sqrt(diag N + mu), tol = scaled_tol(p) = 64 eps (largest observation count of one camera + 16).
+
+dp_a (C2) is judged as a solve of the system it was computed from (the S and e_a read back from the device): with
+D = diag(S)^-1/2 the normwise backward error of D^-1 dp_a for (D S D) y = D e_a must stay below
+test_gpu_dense_solve.ETA_MAX.  An unpivoted Cholesky commutes with a diagonal scaling up to the roundings of the scaling
+itself, so this is the backward error the factorization can be held to; in the unscaled system the focal-length rows
+(1e12) would hide every other row.  The forward error against dense_ref.refined_solution of the scaled system is held
+to 2 cond_2(D S D) 1e-14, the rule of test_gpu_dense_solve.py.
+
+dp_b (C3) is judged per point as a residual: with the device's dp_a and dp_b, and V_i, W_a, g_b,i summed in extended
+precision from the twin's blocks,
+    r_i = (V_i + mu I) dp_b,i - (g_b,i - sum_a W_a^T dp_a,j(a)).
+The kernel solves (V*_k + dV) dp_b = e_b,k with ITS V*_k and e_b,k, so r_i = (V* - V*_k) dp_b - dV dp_b + (e_b,k - e_b)
+and every entry r of r_i is bounded by the sum of
+  * the L D L^T solve: |dV| <= gamma(LDL_K) |L| |D| |L^T| (Higham, Thm 10.4: 3 n + 1 = 10 roundings for a Cholesky
+    solve with n = 3; sym3_ldl / sym3_ldl_solve multiply by a stored reciprocal in six places where the theorem
+    divides, one more rounding each: LDL_K = 16), and (|L| |D| |L^T|)_rc <= sqrt(V*_rr V*_cc) for a positive definite
+    V* (Cauchy-Schwarz on the rows of D^1/2 L^T): gamma(16) sum_c sqrt(V*_rr V*_cc) |dp_b,c|;
+  * env(V*)_rc |dp_b,c|, env(V*) = |c| gamma(n_i + 2) sum |B|^T |B| (assembly_ref's K1 rule for a sum of n_i terms in
+    any order) + u |V*_rr| on the diagonal (the damping add) + the Jacobian slack below;
+  * env(g_b)_r = |c_g| gamma(n_i + 2) sum |B|^T |e| + the slacks below;
+  * e_b's own sum: cnp n_i products and the subtraction, gamma(cnp n_i + 2) (|g_b,r| + sum_a sum_k |W_a,kr| |dp_a,k|);
+  * env(W_a)_kr |dp_a,k|, env(W) = |c| gamma(3) |A|^T |B| (two products, one add, the scaling) + the Jacobian slack.
+Slacks.  The kernel and the twin are two fp64 evaluations of the same derivatives, the argument assembly_ref makes for
+JACOBIAN_SLACK = 2^-40 and RESIDUAL_SLACK = 2^-44; both constants are taken from there unchanged.  Here the two
+texts differ (the twin composes d(u, v)/dP with matrix products, the kernel expands it), so an entry that cancels in
+one text need not in the other: the slack of an entry of A is 2^-40 times the LARGEST entry (both rows) of that
+observation's Jacobian within the same parameter group -- intrinsics, distortion, rotation, translation -- and of an
+entry of B 2^-40 times the largest entry of B_a; never the entry's own magnitude.  With sA, sB these slacks:
+env(W) += |c| (sA^T |B| + |A|^T sB + sA^T sB), env(V) += |c| sum (sB^T |B| + |B|^T sB + sB^T sB),
+env(g) += |c_g| sum (sJ^T (|e| + es) + |J|^T es), es = assembly_ref.residual_slack(m, proj).
+This slack is an assumption nobody has measured against a GPU; it is about 1000 gamma, so it is the bound wherever it
+applies (DESIGN 7d records the worst ratios found).
+
+The four try scalars (C4) are assembly_ref.try_scalars' (it takes nA, not a block size): dp_l2, gain_den and newp_l2
+from the device's own dp and proposal summed in extended precision, gain_den with env(g) above; new_cost against the
+twin's residuals at the device's proposal, per observation gamma(2) s (+ gamma(8) s for the loss slot, the identity
+here) and the residual slack rule."""
+import numpy as np
+
+import assembly_ref as ar
+import dense_ref as dr
+from freekd_twin import CNP, TwinKD, start_kc
+
+LD = ar.LD
+ALL = (1,) * 10
+K_ONLY = (1, 1, 1, 1, 1, 0, 0, 0, 0, 0)
+SEL11 = np.r_[0:5, 10:16]
+GROUPS = {16: (slice(0, 5), slice(5, 10), slice(10, 13), slice(13, 16)), 11: (slice(0, 5), slice(5, 8), slice(8, 11))}
+LDL_K = 16
+
+
+class Route:
+    """cnp = 16: TwinKD(p, start_kc, free); cnp = 11: TwinKD(p, None, K_ONLY) and the columns SEL11"""
+
+    def __init__(self, p, cnp, free=None):
+        self.p, self.cnp = p, cnp
+        self.nC, self.nP, self.nO = int(p["nC"]), int(p["nP"]), int(p["nO"])
+        if cnp == 16:
+            self.free = ALL if free is None else tuple(free)
+            self.twin = TwinKD(p, start_kc(self.nC), self.free)
+        else:
+            self.free = K_ONLY
+            self.twin = TwinKD(p, None, K_ONLY)
+        self.i, self.j = self.twin.i, self.twin.j
+        self.nA, self.nB = cnp * self.nC, 3 * self.nP
+        self.nT = self.nA + self.nB
+        # rows / columns of the twin's 16-wide camera part that this route has
+        sel = np.arange(CNP) if cnp == 16 else SEL11
+        self.rows = (CNP * np.arange(self.nC)[:, None] + sel[None, :]).reshape(-1)
+        self.held = np.flatnonzero(~self.twin.free_a[self.rows])
+
+    def cams16(self, cams):
+        """[nC, cnp] of this route -> the twin's [nC, 16]"""
+        cams = np.asarray(cams, dtype=np.float64).reshape(self.nC, self.cnp)
+        if self.cnp == 16:
+            return cams
+        out = np.zeros((self.nC, CNP))
+        out[:, SEL11] = cams
+        return out
+
+    def blocks(self):
+        """e [nO, 2], A [nO, 2, cnp], B [nO, 2, 3], proj [nO, 2] at the start"""
+        e, A, B = self.twin.linearize()
+        return e, A[:, :, np.arange(CNP) if self.cnp == 16 else SEL11], B, self.twin.t.m - e
+
+    def residuals(self, cams, pts):
+        """fp64 residuals [nO, 2] and projections at (cams [nC, cnp], pts)"""
+        e = self.twin.residual(self.cams16(cams), pts)
+        self.twin._set(None, None)
+        return e, self.twin.t.m - e
+
+    def pick(self, S, ea):
+        """the twin's 16-wide S, e_a restricted to this route"""
+        return S[np.ix_(self.rows, self.rows)], ea[self.rows]
+
+    def pick_full(self, N, g):
+        """the twin's dense N, g (cameras then points) restricted to this route"""
+        idx = np.r_[self.rows, CNP * self.nC + np.arange(self.nB)]
+        return N[np.ix_(idx, idx)], g[idx]
+
+
+def group_slack(A, groups):
+    """JACOBIAN_SLACK times the largest entry (both rows) of each observation's block within the parameter group"""
+    s = np.zeros(A.shape)
+    a = np.abs(A)
+    for g in groups:
+        s[:, :, g] = a[:, :, g].max(axis=(1, 2))[:, None, None]
+    return ar.JACOBIAN_SLACK * s
+
+
+def sums(rt, coeff=1.0, coeff_g=1.0):
+    """V [nP,3,3], W [nO,cnp,3], g [nT] of the route summed in extended precision from the twin's blocks, with the
+    envelopes of the module docstring; also diagU [nA] (the fp64 diagonal of U with the placeholder) and cost."""
+    e, A, B, proj = rt.blocks()
+    i, j, nC, nP = rt.i, rt.j, rt.nC, rt.nP
+    AL, BL, eL = ar.ld(A), ar.ld(B), ar.ld(e)
+    aA, aB, ae = np.abs(A), np.abs(B), np.abs(e)
+    sA, sB = group_slack(A, GROUPS[rt.cnp]), group_slack(B, (slice(0, 3),))
+    es = ar.residual_slack(rt.twin.t.m, proj)
+    c, cg = abs(coeff), abs(coeff_g)
+    W = LD(coeff) * np.einsum("ark,arc->akc", AL, BL)
+    envW = c * (ar.gamma(3) * np.einsum("ark,arc->akc", aA, aB) + np.einsum("ark,arc->akc", sA, aB + sB)
+                + np.einsum("ark,arc->akc", aA, sB))
+    Vx, n_i = ar._segsum(np.einsum("ari,ark->aik", BL, BL), i, nP)
+    Va, _ = ar._segsum(np.einsum("ari,ark->aik", aB, aB), i, nP)
+    Vs, _ = ar._segsum(np.einsum("ari,ark->aik", sB, 2 * aB + sB), i, nP)
+    envV = c * (ar.gamma(n_i + 2)[:, None, None] * Va + Vs)
+    gbx, _ = ar._segsum(np.einsum("ari,ar->ai", BL, eL), i, nP)
+    gba, _ = ar._segsum(np.einsum("ari,ar->ai", aB, ae), i, nP)
+    gbs, _ = ar._segsum(np.einsum("ari,ar->ai", sB, ae + es) + np.einsum("ari,ar->ai", aB, es), i, nP)
+    gax, n_j = ar._segsum(np.einsum("ari,ar->ai", AL, eL), j, nC)
+    gaa, _ = ar._segsum(np.einsum("ari,ar->ai", aA, ae), j, nC)
+    gas, _ = ar._segsum(np.einsum("ari,ar->ai", sA, ae + es) + np.einsum("ari,ar->ai", aA, es), j, nC)
+    g = LD(coeff_g) * np.concatenate([gax.reshape(-1), gbx.reshape(-1)])
+    envg = cg * np.concatenate([(ar.gamma(n_j + 2)[:, None] * gaa + gas).reshape(-1),
+                                (ar.gamma(n_i + 2)[:, None] * gba + gbs).reshape(-1)])
+    diagU, _ = ar._segsum((A * A).sum(axis=1), j, nC)
+    diagU = coeff * diagU.reshape(-1)
+    diagU[rt.held] = coeff
+    diagV, _ = ar._segsum((B * B).sum(axis=1), i, nP)
+    return dict(W=W, envW=envW, V=LD(coeff) * Vx, envV=envV, g=g, envg=envg, n_i=n_i, n_j=n_j, diagU=diagU,
+                diagV=coeff * diagV.reshape(-1), cost=float(np.sum(eL * eL)), A=A, B=B, e=e)
+
+
+def dpb_residual(rt, sm, dp, mu):
+    """(r [nB], bound [nB]) of the module docstring from the step dp [nT] (cameras then points) being judged"""
+    cnp, nA = rt.cnp, rt.nA
+    dpa = np.asarray(dp[:nA], dtype=np.float64).reshape(-1, cnp)
+    dpb = np.asarray(dp[nA:], dtype=np.float64).reshape(-1, 3)
+    Vs = sm["V"].copy()
+    k = np.arange(3)
+    Vs[:, k, k] += LD(mu)
+    dL, ad = ar.ld(dpa)[rt.j], np.abs(dpa)[rt.j]
+    t, n_i = ar._segsum(np.einsum("akc,ak->ac", sm["W"], dL), rt.i, rt.nP)
+    gb = sm["g"][nA:].reshape(-1, 3)
+    r = np.einsum("irc,ic->ir", Vs, ar.ld(dpb)) - (gb - t)
+    aW = np.abs(sm["W"].astype(np.float64))
+    wd, _ = ar._segsum(np.einsum("akc,ak->ac", aW, ad), rt.i, rt.nP)
+    wenv, _ = ar._segsum(np.einsum("akc,ak->ac", sm["envW"], ad), rt.i, rt.nP)
+    Vd = Vs.astype(np.float64)
+    dg = np.sqrt(Vd[:, k, k])
+    envV = sm["envV"].copy()
+    envV[:, k, k] += ar.U * Vd[:, k, k]
+    ab = np.abs(dpb)
+    bound = (ar.gamma(LDL_K) * dg * (dg * ab).sum(axis=1)[:, None] + np.einsum("irc,ic->ir", envV, ab)
+             + sm["envg"][nA:].reshape(-1, 3) + ar.gamma(cnp * n_i + 2)[:, None] * (np.abs(gb.astype(np.float64)) + wd)
+             + wenv)
+    return r.reshape(-1), bound.reshape(-1)
+
+
+def scalars(rt, sm, dp, newcams, newpts, mu):
+    """assembly_ref.try_scalars for this route: {name: (exact, bound)} from the step and proposal being judged"""
+    e_new, proj = rt.residuals(newcams, newpts)
+    newp = np.concatenate([np.asarray(newcams).reshape(-1), np.asarray(newpts).reshape(-1)])
+    return ar.try_scalars(dp, newp, mu, sm["g"], rt.nA, (e_new * e_new).sum(axis=1),
+                          e_slack=ar.residual_slack(rt.twin.t.m, proj), envg=sm["envg"])
+
+
+def solve_judge(S, ea, dpa):
+    """(backward error of D^-1 dp_a for (D S D) y = D e_a, its forward error against the refined solution,
+    cond_2(D S D)), D = diag(S)^-1/2"""
+    S = np.asarray(S, dtype=np.float64)
+    d = 1.0 / np.sqrt(np.diag(S))
+    A = d[:, None] * S * d[None, :]
+    y, b = np.asarray(dpa) / d, d * np.asarray(ea)
+    return dr.backward_error(A, y, b), dr.forward_error(y, dr.refined_solution(A, b)), dr.cond2(A)
+
+
+# ---- plain fp64 evaluations (what the kernels compute, in numpy): the judges' own test ---------------------------------
+
+def ldl_solve(v, w):
+    """camera_model.h's sym3_ldl / sym3_ldl_solve in fp64 numpy: v [n, 3, 3], w [n, m, 3] -> y with (v) y = w per row"""
+    i0 = 1.0 / v[:, 0, 0]
+    l10, l20 = v[:, 0, 1] * i0, v[:, 0, 2] * i0
+    d1 = v[:, 1, 1] - l10 * v[:, 0, 1]
+    i1 = 1.0 / d1
+    l21 = (v[:, 1, 2] - l20 * v[:, 0, 1]) * i1
+    i2 = 1.0 / (v[:, 2, 2] - l20 * v[:, 0, 2] - l21 * l21 * d1)
+    b = lambda x: x[:, None]  # noqa: E731
+    z1 = w[:, :, 1] - b(l10) * w[:, :, 0]
+    z2 = w[:, :, 2] - b(l20) * w[:, :, 0] - b(l21) * z1
+    y2 = z2 * b(i2)
+    y1 = z1 * b(i1) - b(l21) * y2
+    y0 = w[:, :, 0] * b(i0) - b(l10) * y1 - b(l20) * y2
+    return np.stack([y0, y1, y2], axis=2)
+
+
+def closed_form_solve(v, w):
+    """w times camera_model.h's sym3_inverse (adjugate over T = -det) in fp64 numpy"""
+    a11, a12, a13, a22, a23, a33 = v[:, 0, 0], v[:, 0, 1], v[:, 0, 2], v[:, 1, 1], v[:, 1, 2], v[:, 2, 2]
+    T = a33 * a12 * a12 - 2.0 * a12 * a13 * a23 + a22 * a13 * a13 + a11 * a23 * a23 - a11 * a22 * a33
+    iT = -1.0 / T
+    X = np.empty_like(v)
+    X[:, 0, 0] = (a22 * a33 - a23 * a23) * iT
+    X[:, 0, 1] = X[:, 1, 0] = (a13 * a23 - a12 * a33) * iT
+    X[:, 0, 2] = X[:, 2, 0] = (a12 * a23 - a13 * a22) * iT
+    X[:, 1, 1] = (a11 * a33 - a13 * a13) * iT
+    X[:, 1, 2] = X[:, 2, 1] = (a12 * a13 - a11 * a23) * iT
+    X[:, 2, 2] = (a11 * a22 - a12 * a12) * iT
+    return w @ X
+
+
+def plain_schur(rt, mu, point_solve=ldl_solve):
+    """S [nA, nA], e_a, and the pieces (V*, W, g) in fp64 from the twin's blocks, Y = W V*^-1 by `point_solve`"""
+    e, A, B, _ = rt.blocks()
+    nC, nP, cnp, nA = rt.nC, rt.nP, rt.cnp, rt.nA
+    U = np.zeros((nC, cnp, cnp))
+    np.add.at(U, rt.j, np.einsum("ari,ark->aik", A, A))
+    ga = np.zeros((nC, cnp))
+    np.add.at(ga, rt.j, np.einsum("ari,ar->ai", A, e))
+    V = np.zeros((nP, 3, 3))
+    np.add.at(V, rt.i, np.einsum("ari,ark->aik", B, B))
+    gb = np.zeros((nP, 3))
+    np.add.at(gb, rt.i, np.einsum("ari,ar->ai", B, e))
+    W = np.einsum("ark,arc->akc", A, B)
+    Vs = V + mu * np.eye(3)[None]
+    Y = point_solve(Vs[rt.i], W)
+    S = np.zeros((nA, nA))
+    for j in range(nC):
+        S[cnp * j:cnp * j + cnp, cnp * j:cnp * j + cnp] = U[j]
+    S[rt.held, rt.held] = 1.0
+    S[np.arange(nA), np.arange(nA)] += mu
+    ea = ga.reshape(-1).copy()
+    order = np.argsort(rt.i, kind="stable")
+    ptr = np.searchsorted(rt.i[order], np.arange(nP + 1))
+    for i in range(nP):
+        obs = order[ptr[i]:ptr[i + 1]]
+        if obs.size == 0:
+            continue
+        rows = (cnp * rt.j[obs][:, None] + np.arange(cnp)[None, :]).reshape(-1)
+        S[np.ix_(rows, rows)] -= Y[obs].reshape(-1, 3) @ W[obs].reshape(-1, 3).T
+        ea[rows] -= Y[obs].reshape(-1, 3) @ gb[i]
+    return S, ea, dict(Vs=Vs, W=W, g=np.concatenate([ga.reshape(-1), gb.reshape(-1)]))
+
+
+def plain_try(rt, mu):
+    """One damping try in plain fp64: dp [nT] (dp_a by a Cholesky of the scaled S, dp_b by L D L^T), the proposal and
+    the four sums"""
+    S, ea, pc = plain_schur(rt, mu)
+    d = 1.0 / np.sqrt(np.diag(S))
+    L = np.linalg.cholesky(d[:, None] * S * d[None, :])
+    dpa = d * np.linalg.solve(L.T, np.linalg.solve(L, d * ea))
+    dpa[rt.held] = 0.0
+    eb = pc["g"][rt.nA:].reshape(-1, 3).copy()
+    np.subtract.at(eb, rt.i, np.einsum("akc,ak->ac", pc["W"], dpa.reshape(-1, rt.cnp)[rt.j]))
+    dpb = ldl_solve(pc["Vs"], eb[:, None, :])[:, 0, :]
+    dp = np.concatenate([dpa, dpb.reshape(-1)])
+    cams = rt.twin.cams[:, np.arange(CNP) if rt.cnp == 16 else SEL11]
+    newcams, newpts = cams + dpa.reshape(-1, rt.cnp), rt.twin.pts + dpb
+    e_new, _ = rt.residuals(newcams, newpts)
+    newp = np.concatenate([newcams.reshape(-1), newpts.reshape(-1)])
+    sc = dict(dp_l2=float(dp @ dp), gain_den=float(dp @ (mu * dp + pc["g"])), newp_l2=float(newp @ newp),
+              new_cost=float((e_new * e_new).sum()))
+    return dict(S=S, ea=ea, dp=dp, newcams=newcams, newpts=newpts, sc=sc)

@@ -278,3 +278,98 @@ def ring_problem(seed=7):
     cs[:, 3:] += 0.02 * rng.standard_normal((nC, 3))
     start = dict(true, K=Ks, cams=cs, pts=pts + 0.02 * rng.standard_normal((nP, 3)), impts=impts)
     return start, np.zeros((nC, 5)), K, kc
+
+
+def _rot_to_quat_any(R):
+    """_rot_to_quat for any rotation (a ring of 4 k cameras holds a half turn, trace = -1): the largest of the four
+    components from the diagonal, the other three from the off-diagonal sums and differences"""
+    tr = np.trace(R)
+    c2 = np.r_[1.0 + tr, 1.0 + 2.0 * np.diag(R) - tr] / 4.0
+    k = int(np.argmax(c2))
+    if k == 0:
+        return _rot_to_quat(R)
+    a = k - 1
+    b, c = (a + 1) % 3, (a + 2) % 3
+    q = np.zeros(4)
+    q[k] = np.sqrt(c2[k])
+    q[0] = (R[c, b] - R[b, c]) / (4.0 * q[k])
+    q[1 + b] = (R[a, b] + R[b, a]) / (4.0 * q[k])
+    q[1 + c] = (R[a, c] + R[c, a]) / (4.0 * q[k])
+    return q
+
+
+def _ring_cameras(nC, radius=5.0):
+    """initrot [nC, 4] and translations [nC, 3] of nC cameras on a ring in the x-z plane, looking at the origin"""
+    q0, t = np.zeros((nC, 4)), np.zeros((nC, 3))
+    for j in range(nC):
+        th = 2.0 * np.pi * j / nC
+        centre = radius * np.array([np.cos(th), 0.0, np.sin(th)])
+        z = -centre / np.linalg.norm(centre)
+        x = np.cross([0.0, 1.0, 0.0], z)
+        x /= np.linalg.norm(x)
+        R = np.stack([x, np.cross(z, x), z])
+        q0[j] = _rot_to_quat_any(R)
+        t[j] = -R @ centre
+    return q0, t
+
+
+def _varied_K(rng, nC):
+    """f 800 (1 +- 2 %), u0 / v0 a few pixels, ar 1 +- 1 %, skew +- 0.3: no intrinsic column is degenerate"""
+    return np.stack([800.0 * (1.0 + rng.uniform(-0.02, 0.02, nC)), rng.uniform(-5.0, 5.0, nC), rng.uniform(-5.0, 5.0, nC),
+                     1.0 + rng.uniform(-0.01, 0.01, nC), rng.uniform(-0.3, 0.3, nC)], 1)
+
+
+def _scene(rng, nC, pts, keep):
+    """The problem of a visibility table keep [nP, nC]: ring cameras, perturbed K, projections through start_kc(nC)
+    with one pixel of noise; point-major observations with ascending cameras.  The start is the generating scene with
+    the points moved by 0.01 N(0, 1)."""
+    q0, t = _ring_cameras(nC)
+    iidx, jidx = np.nonzero(keep)
+    prob = dict(K=_varied_K(rng, nC), initrot=q0, cams=np.hstack([np.zeros((nC, 3)), t]), pts=pts,
+                impts=np.zeros((iidx.size, 2)), iidx=iidx.astype(np.int32), jidx=jidx.astype(np.int32), nC=nC,
+                nP=pts.shape[0], nO=int(iidx.size))
+    prob["impts"] = lens_twin.Twin(prob, start_kc(nC)).project() + rng.standard_normal((iidx.size, 2))
+    prob["pts"] = pts + 0.01 * rng.standard_normal(pts.shape)
+    return prob
+
+
+WIDE_COUNTS = (64, 65, 63, 1, 0)   # observations of cameras 0..4 of wide_problem: a full unit, one more, one less, one, none
+
+
+def wide_problem(nC, nP=240, seed=11):
+    """nC >= 16 ring cameras, nP >= 120 points in [-1, 1]^3 with few views each, so that the launch geometry changes
+    with nC alone (65 cameras of 16 / 94 of 11: the first second trip of the finalize kernels' grid-stride loop) while
+    the dense twin stays small.  The visibility table is drawn and then cut down to:
+      * cameras 0, 1, 2, 3, 4 with exactly 64, 65, 63, 1 and 0 observations (WIDE_COUNTS),
+      * the last point without any observation,
+      * the first nP // 8 points (12.5 %) seen by exactly one camera, the others by at least three."""
+    rng = np.random.default_rng(seed)
+    assert nC >= 16 and nP >= 120
+    pts = rng.uniform(-1.0, 1.0, (nP, 3))
+    n1 = nP // 8
+    keep = np.zeros((nP, nC), dtype=bool)
+    for i in range(nP - 1):
+        k = 1 if i < n1 else int(rng.integers(3, 9))
+        keep[i, 5 + rng.choice(nC - 5, size=k, replace=False)] = True
+    keep[:, :5] = False
+    for j, n in enumerate(WIDE_COUNTS):
+        keep[n1 + rng.choice(nP - 1 - n1, size=n, replace=False), j] = True
+    keep[nP - 1] = False
+    per_cam, per_pt = keep.sum(0), keep.sum(1)
+    assert tuple(per_cam[:5]) == WIDE_COUNTS and per_pt[nP - 1] == 0
+    assert (per_pt == 1).sum() >= 0.1 * nP and (per_pt == 0).sum() == 1 and np.all(per_cam[5:] > 0)
+    return _scene(rng, nC, pts, keep)
+
+
+def many_obs_problem(seed=13):
+    """65 cameras, 6600 points with ten views each: 66 000 observations (the residual kernels' 256 x 256 threads
+    first stride at 65 537), about 1000 per camera (16 units of 64) and 363 000 products on 2145 blocks (several
+    default-length segments per block)."""
+    rng = np.random.default_rng(seed)
+    nC, nP, views = 65, 6600, 10
+    pts = rng.uniform(-1.0, 1.0, (nP, 3))
+    keep = np.zeros((nP, nC), dtype=bool)
+    cols = np.argsort(rng.uniform(size=(nP, nC)), axis=1)[:, :views]
+    keep[np.arange(nP)[:, None], cols] = True
+    assert keep.sum() == nP * views > 65536
+    return _scene(rng, nC, pts, keep)
