@@ -236,7 +236,9 @@ int psba_fixed_counts(psba_handle h, int *n_fixed_cams, int *n_fixed_pts);
  * fp64 atomics straight into S (the
  * first-generation kernel, kept for cross-checks: PSBA_SCHUR_ATOMIC=1), 3 = the ring route (opt-in
  * experiment, PSBA_SCHUR_RING=1), 4 = block-sparse S (PSBA_SOLVER_PCG), 5 = the 16-parameter camera block
- * (PSBA_CAMERA_FREE_KD: products sorted by block, one MFMA per product).  The reference has one
+ * (PSBA_CAMERA_FREE_KD: products sorted by block, one MFMA per product).  The 11-parameter block (PSBA_CAMERA_FREE_K)
+ * has no number of its own: it runs the thread-per-observation route of kernels_freek.hip (global fp64 atomics) and
+ * the call reports 1 for it, which says nothing about that route.  The reference has one
  * route for every size (CL_files/compute_S.cl:6-78). */
 int psba_schur_path(psba_handle h, int *path);
 

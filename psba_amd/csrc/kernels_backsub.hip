@@ -395,7 +395,7 @@ static void enqueue_backsub(psba_ctx *h, const BackArgs &a, const RobustLoss &rl
 }
 
 int launch_backsub(psba_ctx *h, double mu, bool dump) {
-  if (h->cnp != 6) return dump ? fail(h, PSBA_E_STATE, "the sba_func.h mirror is six-parameter only (not PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)") : h->cnp == KD_CNP ? launch_backsub_kd(h, mu) : launch_backsub_fk(h, mu);
+  if (h->cnp != 6) return dump ? mirror_refused(h) : h->cnp == KD_CNP ? launch_backsub_kd(h, mu) : launch_backsub_fk(h, mu);
   const Dims &d = h->d;
   BackArgs a;
   a.W = h->W;

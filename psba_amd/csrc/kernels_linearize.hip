@@ -711,7 +711,7 @@ static void enqueue_linearize(psba_ctx *h, const LinArgs &a, const RobustLoss &r
 }
 
 int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
-  if (h->cnp != 6) return dump ? fail(h, PSBA_E_STATE, "the sba_func.h mirror is six-parameter only (not PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)") : h->cnp == KD_CNP ? launch_linearize_kd(h, ahead, publish) : launch_linearize_fk(h, ahead, publish);
+  if (h->cnp != 6) return dump ? mirror_refused(h) : h->cnp == KD_CNP ? launch_linearize_kd(h, ahead, publish) : launch_linearize_fk(h, ahead, publish);
   const Dims &d = h->d;
   LinArgs a;
   a.camconst = h->camconst;
@@ -775,7 +775,7 @@ int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
 }
 
 int launch_residual(psba_ctx *h, int which, double *ex_out_dev, double *s_out_dev) {
-  if (h->cnp != 6) return ex_out_dev || s_out_dev ? fail(h, PSBA_E_STATE, "the sba_func.h mirror is six-parameter only (not PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)") : h->cnp == KD_CNP ? launch_residual_kd(h, which) : launch_residual_fk(h, which);
+  if (h->cnp != 6) return ex_out_dev || s_out_dev ? mirror_refused(h) : h->cnp == KD_CNP ? launch_residual_kd(h, which) : launch_residual_fk(h, which);
   const Dims &d = h->d;
   const int set = which == PSBA_PARAMS_NEW ? 1 - h->cur : h->cur;
   PSBA_HIP(h, hipMemsetAsync(h->scal + SC_COST, 0, sizeof(double), h->stream));

@@ -34,6 +34,10 @@ int fail(psba_ctx *h, int code, const char *fmt, ...) {
   return code;
 }
 
+int mirror_refused(psba_ctx *h) {
+  return fail(h, PSBA_E_STATE, "the sba_func.h mirror is six-parameter only (not PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)");
+}
+
 ProfScope::ProfScope(psba_ctx *hh, int kind) : h(hh) {
   if (kind < 0 || !(h->prof & (1u << kind))) return;
   if (h->spans_used == h->spans.size()) {
@@ -76,6 +80,9 @@ ProfScope::~ProfScope() {
   do {                                                                  \
     if (!(cond)) return fail((h), PSBA_E_STATE, "%s: %s", __func__, what); \
   } while (0)
+// the verbs that exist for the six-parameter camera block only
+#define SIX_ONLY "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)"
+#define NEED_SIX(h) NEED(h, (h)->cnp == 6, SIX_ONLY)
 #define RCCL(h, call)                                                                   \
   do {                                                                                  \
     ncclResult_t r__ = (call);                                                          \
@@ -1285,7 +1292,7 @@ static int ensure_trv(psba_ctx *h) {
 
 int psba_jmul_dots(psba_handle h, const double *x1, const double *x2, double dots[3]) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
+  NEED_SIX(h);
   NEED(h, h->uploaded, "no problem uploaded");
   if (!x1 || !dots) return fail(h, PSBA_E_INVALID, "psba_jmul_dots: null pointer");
   TRY(ensure_trv(h));
@@ -1380,7 +1387,7 @@ int psba_allreduce_scalars(psba_handle h, double *v, int n) {
 
 int psba_compute_Jmultiply(psba_handle h, const double *x, double *Jmul) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
+  NEED_SIX(h);
   NEED(h, h->uploaded, "no problem uploaded");
   if (!x) return fail(h, PSBA_E_INVALID, "psba_compute_Jmultiply: null pointer");
   TRY(ensure_trv(h));
@@ -1402,7 +1409,7 @@ int psba_get_gradient(psba_handle h, double *g) {
       for (int k = 0; k < 3; k++) g[h->d.nA + 3 * (size_t)i + k] = pv[(size_t)9 * i + 6 + k];
     return PSBA_OK;
   }
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
+  NEED_SIX(h);
   NEED(h, h->linearized, "psba_linearize first");
   if (!g) return PSBA_E_INVALID;
   TRY(ensure_trv(h));
@@ -1420,7 +1427,7 @@ int psba_get_dp(psba_handle h, double *dp) {
 
 int psba_set_step(psba_handle h, const double *dp) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
+  NEED_SIX(h);
   NEED(h, h->uploaded, "no problem uploaded");
   if (!dp) return PSBA_E_INVALID;
   PSBA_HIP(h, hipMemcpyAsync(h->dp, dp, sizeof(double) * (size_t)h->d.nT, hipMemcpyHostToDevice, h->stream));
@@ -1432,7 +1439,7 @@ int psba_set_step(psba_handle h, const double *dp) {
 
 int psba_cholmod_lambda(psba_handle h, int reassemble, double *lambda, double *info3) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
+  NEED_SIX(h);
   NEED(h, h->uploaded, "no problem uploaded");
   if (h->nranks > 1 && !h->comm)
     return fail(h, PSBA_E_INVALID, "psba_cholmod_lambda on a rank layout needs the communicator (S must be complete)");
@@ -1534,7 +1541,7 @@ int psba_compute_jacobiQT(psba_handle h, double *jac_A, double *jac_B) {
 
 int psba_compute_U(psba_handle h, double coeff, double *out) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
+  NEED_SIX(h);
   NEED(h, h->uploaded, "no problem uploaded");
   h->coeff = coeff;
   TRY(relinearize_dump(h));
@@ -1557,7 +1564,7 @@ static int download_V(psba_ctx *h, double *out, double mu) {
 
 int psba_compute_V(psba_handle h, double coeff, double *out) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
+  NEED_SIX(h);
   NEED(h, h->uploaded, "no problem uploaded");
   h->coeff = coeff;
   TRY(relinearize_dump(h));
@@ -1568,7 +1575,7 @@ int psba_maxElmOfUV(psba_handle h, double *out) { return psba_max_diag(h, out); 
 
 int psba_update_UV(psba_handle h, double mu, double *U, double *V) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
+  NEED_SIX(h);
   NEED(h, h->linearized, "linearise first");
   h->mu = mu;
   h->mu_applied = true;
@@ -1595,7 +1602,7 @@ int psba_compute_Vinv(psba_handle h, double *Vinv) {
 
 int psba_compute_Wblks(psba_handle h, double coeff, double *Wblks) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
+  NEED_SIX(h);
   NEED(h, h->uploaded, "no problem uploaded");
   h->coeff = coeff;
   TRY(relinearize_dump(h));
@@ -1620,7 +1627,7 @@ int psba_compute_S(psba_handle h, double *S) {
 
 int psba_compute_g(psba_handle h, double coeff, double *g) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
+  NEED_SIX(h);
   NEED(h, h->uploaded, "no problem uploaded");
   h->coeff_g = coeff;
   TRY(relinearize_dump(h));
@@ -1779,7 +1786,7 @@ int psba_get_reduce_buffer(psba_handle h, double *out) {
 
 int psba_set_reduce_buffer(psba_handle h, const double *in) {
   CHECK_H(h);
-  NEED(h, h->cnp == 6 || h->cnp == KD_CNP, "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)");
+  NEED(h, h->cnp == 6 || h->cnp == KD_CNP, SIX_ONLY);
   NEED(h, h->assembled, "psba_schur_assemble first");
   NEED(h, !h->comm, "the reduce-buffer verbs are for handles without a communicator");
   NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");

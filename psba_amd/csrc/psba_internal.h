@@ -415,6 +415,7 @@ int launch_schur(psba_ctx *h, double mu, bool dump);
 int launch_schur_expand(psba_ctx *h);
 // kernels_chol.hip
 int launch_chol_solve(psba_ctx *h);
+int mirror_refused(psba_ctx *h);  // the sba_func.h mirror (dumps, per-observation outputs) asked of a block wider than 6
 // kernels_freek.hip: the 11-parameter camera block (free intrinsics), one plain route
 int launch_linearize_fk(psba_ctx *h, bool ahead, bool publish);
 int launch_residual_fk(psba_ctx *h, int which);
