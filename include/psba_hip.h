@@ -389,6 +389,12 @@ int psba_set_step(psba_handle h, const double *dp);
  * diagonally dominant -- or 1e-6 max_i of those margins when S is diagonally dominant already;
  * info3 = (min margin, max margin, 0). */
 int psba_cholmod_lambda(psba_handle h, int reassemble, double *lambda, double *info3);
+/* ---- test hook: the factor L of that modified Cholesky, L[6 nCams][6 nCams] row-major (the strict upper triangle
+ * holds the zeros the kernel wrote).  Valid only directly after a dense-mode psba_cholmod_lambda: the factor lives in
+ * the buffer of the Cholesky chain, so psba_schur_assemble, psba_schur_solve, psba_chol_dist_*, the sba_func.h mirror's
+ * assembly and solve and psba_upload_problem invalidate it -- PSBA_E_STATE then, as before any psba_cholmod_lambda and
+ * under PSBA_SOLVER_PCG (no factor exists: the estimate is a Gershgorin shift). */
+int psba_get_cholmod_factor(psba_handle h, double *L);
 
 typedef struct {
   int max_iter;     /* literal 50, shared with levmar() through itno (trust_region.cpp:112) */

@@ -136,6 +136,7 @@ SIGNATURES = [
     ("psba_get_dp", C.c_int, [_h, _dp]),
     ("psba_set_step", C.c_int, [_h, _dp]),
     ("psba_cholmod_lambda", C.c_int, [_h, C.c_int, _dp, _dp]),
+    ("psba_get_cholmod_factor", C.c_int, [_h, _dp]),
     ("psba_tr_default_options", None, [C.POINTER(TrOptions)]),
     ("psba_trust_region", C.c_int, [_h, C.POINTER(TrOptions), C.POINTER(TrResult), _dp]),
     ("psba_solve", C.c_int, [_h, C.c_int, C.c_int, C.POINTER(SolveResult)]),
@@ -795,6 +796,10 @@ class Psba:
         lam, info = C.c_double(), np.empty(3)
         self._ck(lib.psba_cholmod_lambda(self._h, int(reassemble), C.byref(lam), _d(info)))
         return lam.value, info
+
+    def cholmod_factor(self):
+        """psba_get_cholmod_factor (test hook): L [nA, nA] of the last dense-mode cholmod_lambda."""
+        return self._out(lib.psba_get_cholmod_factor, self.nA * self.nA)[1].reshape(self.nA, self.nA)
 
     def trust_region(self, max_iter=50, start_itno=0, verbose=False, log_cap=512, init_lambda=0.0):
         opts = TrOptions(max_iter, start_itno, int(verbose), log_cap, init_lambda)

@@ -1018,6 +1018,7 @@ int psba_schur_assemble(psba_handle h, double mu) {
   // every camera fixed: no coupled system.  dpa = 0 and K3's point part is the whole solve, so K2, the S-reduce and the
   // factorization are not queued at all (PSBA_FIXED_NO_SHORTCUT=1: the general route, for the test that compares them)
   h->try_shortcut = h->struct_only && h->cnp == 6 && !getenv("PSBA_FIXED_NO_SHORTCUT");
+  h->cholmod_factor = false;  // the S-reduce kernel may factor the first diagonal block into chol_L
   if (h->try_shortcut)
     TRY(launch_struct_only_try(h, mu));
   else
@@ -1066,6 +1067,7 @@ int psba_schur_solve(psba_handle h) {
     return PSBA_OK;
   }
   if (h->packed_pending) TRY(allreduce_schur(h));  // psba_schur_reduce was skipped
+  h->cholmod_factor = false;
   if (h->solver == PSBA_SOLVER_PCG) {
     TRY(launch_pcg_solve(h));
     h->assembled = false;
@@ -1251,12 +1253,14 @@ int psba_chol_dist_begin(psba_handle h) {
     TRY(launch_schur_expand(h));
     h->packed_pending = false;
   }
+  h->cholmod_factor = false;
   return chol_dist_begin(h);
 }
 int psba_chol_dist_superpanel(psba_handle h, int J) {
   CHECK_H(h);
   NEED(h, h->assembled, "psba_schur_assemble first");
   if (J < 0 || J >= h->n32) return fail(h, PSBA_E_INVALID, "super-panel column %d out of range", J);
+  h->cholmod_factor = false;
   return chol_dist_superpanel(h, J);
 }
 int psba_chol_dist_block(psba_handle h, int B, int set, double *buf, long long *n_doubles) {
@@ -1269,6 +1273,7 @@ int psba_chol_dist_block(psba_handle h, int B, int set, double *buf, long long *
   if (!buf) return PSBA_OK;
   if (!h->dist_buf) TRY(h->dist_buf.alloc(h, (size_t)(h->n32 + 1) * 64 * 8));
   if (set) {
+    h->cholmod_factor = false;
     PSBA_HIP(h, hipMemcpyAsync(h->dist_buf, buf, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream));
     return chol_dist_block(h, B, h->dist_buf, 1);
   }
@@ -1278,6 +1283,7 @@ int psba_chol_dist_block(psba_handle h, int B, int set, double *buf, long long *
 int psba_chol_dist_finish(psba_handle h) {
   CHECK_H(h);
   NEED(h, h->assembled, "psba_schur_assemble first");
+  h->cholmod_factor = false;
   TRY(chol_dist_finish(h));
   h->assembled = false;
   h->solved = true;
@@ -1451,6 +1457,7 @@ int psba_cholmod_lambda(psba_handle h, int reassemble, double *lambda, double *i
     reassemble = 1;
     h->try_shortcut = false;
   }
+  h->cholmod_factor = false;
   if (h->solver == PSBA_SOLVER_PCG) {
     // block-sparse mode: no dense S to factor -- the damping estimate is the Gershgorin shift of the stored blocks
     // (kernels_pcg.hip; no reference counterpart: the reference has no sparse mode)
@@ -1481,6 +1488,21 @@ int psba_cholmod_lambda(psba_handle h, int reassemble, double *lambda, double *i
   if (info3)
     for (int k = 0; k < 3; k++) info3[k] = h->h_scal[SC_CHOLMOD + 1 + k];
   h->assembled = h->solved = false;
+  h->cholmod_factor = true;
+  return PSBA_OK;
+}
+
+// test hook (psba_hip.h): the factor the modified Cholesky left in chol_L
+int psba_get_cholmod_factor(psba_handle h, double *L) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->solver != PSBA_SOLVER_PCG, "no modified Cholesky factor with PSBA_SOLVER_PCG (the estimate is a Gershgorin shift)");
+  NEED(h, h->cholmod_factor, "psba_cholmod_lambda first (every verb that factors or assembles S overwrites the factor)");
+  if (!L) return fail(h, PSBA_E_INVALID, "psba_get_cholmod_factor: null pointer");
+  const size_t n = (size_t)h->d.nA;
+  PSBA_HIP(h, hipMemcpy2DAsync(L, sizeof(double) * n, h->chol_L, sizeof(double) * (size_t)h->n32, sizeof(double) * n, n,
+                               hipMemcpyDeviceToHost, h->stream));
+  PSBA_HIP(h, hipStreamSynchronize(h->stream));
   return PSBA_OK;
 }
 
@@ -1516,6 +1538,7 @@ static int reassemble_dump(psba_ctx *h) {
   NEED(h, h->linearized, "linearise first (compute_jacobiQT / compute_U / ...)");
   TRY(ensure_dbg(h));
   h->try_shortcut = false;  // the mirror always takes the general route
+  h->cholmod_factor = false;
   TRY(launch_schur(h, h->mu_applied ? h->mu : 0.0, true));
   h->assembled = true;
   h->solved = h->backsubbed = false;
@@ -1650,6 +1673,7 @@ int psba_SPDinv_matVec(psba_handle h, double *dpa) {
   CHECK_H(h);
   NEED(h, h->assembled, "compute_S / compute_ea first");
   NEED(h, !h->try_shortcut, "every camera is fixed: psba_schur_assemble assembled no S (compute_S / compute_ea first)");
+  h->cholmod_factor = false;
   TRY(launch_chol_solve(h));
   h->assembled = false;
   h->solved = true;

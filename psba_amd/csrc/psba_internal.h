@@ -243,6 +243,7 @@ struct ProblemState {
   int h_diagpos[21] = {0};      // partition positions of the blocks (j, k), j <= 5
   int h_diaggrp[21] = {0};      // and their groups (-1: no such camera)
   bool diag_done = false;       // this try's S-reduce kernel has factored the first diagonal block
+  bool cholmod_factor = false;  // chol_L holds the factor of the last dense psba_cholmod_lambda (psba_get_cholmod_factor)
   psba::DevBuf<int> posblock;   // per group, per partition position: (j << 16) | k of the block there, -1 = padding
   psba::DevBuf<double> slab;    // per workgroup: its group's partition, 36 doubles per position
   size_t packedN = 0;           // 36 * nC (nC+1) / 2 doubles: packed lower block triangle of S
