@@ -136,6 +136,34 @@ int psba_camera_block(psba_handle h, int *cnp); /* 6, 11 or 16 */
 int psba_set_intrinsics_mask(psba_handle h, const unsigned char free10[10]);
 int psba_intrinsics_mask(psba_handle h, unsigned char out10[10]);
 
+/* ---- intrinsics shared between cameras (PSBA_CAMERA_FREE_KD) ----------------------------------
+ * One physical camera takes many images: group_of_cam[j] is any int, cameras with equal labels share their ten
+ * intrinsics (fu, u0, v0, ar, s, k1..k5).  The representative rep(j) of a group is its lowest camera index; P maps
+ * the reduced parameters to the per-camera ones (a free intrinsic coordinate k of a member j takes the value of
+ * coordinate k of rep(j)), J_shared = J P, and because P leaves the points alone the Schur complement commutes with it:
+ *   S_shared = P^T (U - W (V + mu I)^-1 W^T) P + mu I,   e_a,shared = P^T e_a.
+ * The fold is stored embedded in the full-size system (nA = 16 nCams stays): row and column of a free intrinsic
+ * coordinate of a representative are the sums of its members' rows and columns in ascending camera order, mu added
+ * once after the sum; a free intrinsic coordinate of a non-representative member becomes what a masked coordinate is
+ * (zero off the diagonal, coeff + mu on it, e_a = 0).  Coordinates held by psba_set_intrinsics_mask stay held on every
+ * camera and are not summed; mask and groups compose in either order.  After the solve the representative's dp is
+ * copied to its members: psba_get_dp returns the expanded per-camera step, and members that start bit-identical stay
+ * bit-identical.  Every reduction counts a shared parameter once: psba_max_diag / psba_begin take the maximum over the
+ * folded diagonal of U (the group sum for shared coordinates, free entries only); dp_l2 and newp_l2 skip the
+ * intrinsic entries of non-representatives; gain_den = sum over all entries of dp g + mu times the sum over the
+ * distinct parameters of dp^2.  psba_get_gradient keeps returning the per-camera g: the sum over a group is the
+ * derivative with respect to the shared parameter.  psba_get_reduce_buffer returns the folded, embedded [S | e_a].
+ * NULL or a labelling in which every camera is alone is no grouping: the handle runs exactly the kernels of one that
+ * never set any.  Members must hold bit-identical intrinsics (columns 0..9) in the current parameters and in the copy
+ * psba_reset_params restores: PSBA_E_INVALID names the first offending camera and column; while groups are set
+ * psba_set_params and psba_set_distortion make the same check on their host arrays before touching the device.
+ * After psba_upload_problem (a new upload resets to none); PSBA_E_STATE under another camera model and while a try is
+ * in flight; a refused call changes nothing; setting groups discards a linearization queued ahead.  No floating-point
+ * atomics: two runs stay bit-identical.  psba_intrinsics_groups: rep_of_cam[j] = rep(j) (j itself without groups;
+ * may be NULL) and the number of groups (nCams without groups). */
+int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam);
+int psba_intrinsics_groups(psba_handle h, int *rep_of_cam, int *n_groups);
+
 /* ---- lens distortion and per-observation image covariances --------------------------
  * Model (the same in psba_amd/csrc/camera_model.h and DESIGN.md): P = R'(q) M + t, (x, y) = (Px, Py) / Pz,
  * r2 = x^2 + y^2, kc = (k1, k2, k3, k4, k5) in the Camera Calibration Toolbox order (the column order of the

@@ -179,6 +179,8 @@ SIGNATURES = [
     ("psba_owner_plan_destroy", None, [C.c_void_p]),
     ("psba_set_intrinsics_mask", C.c_int, [_h, C.POINTER(C.c_ubyte)]),
     ("psba_intrinsics_mask", C.c_int, [_h, C.POINTER(C.c_ubyte)]),
+    ("psba_set_intrinsics_groups", C.c_int, [_h, C.POINTER(C.c_int)]),
+    ("psba_intrinsics_groups", C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("psba_blockprod_plan_create", C.c_void_p, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_int]),
     ("psba_blockprod_plan_info", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     ("psba_blockprod_plan_copy", C.c_int, [C.c_void_p, _ip, _ip, _ip]),
@@ -492,6 +494,23 @@ class Psba:
         m = np.zeros(10, dtype=np.uint8)
         self._ck(lib.psba_intrinsics_mask(self._h, m.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return tuple(int(v) for v in m)
+
+    def set_intrinsics_groups(self, group_of_cam=None):
+        """psba_set_intrinsics_groups: one label (any int) per camera, equal labels share their ten intrinsics;
+        None = no sharing.  CAMERA_FREE_KD only; members must hold bit-identical intrinsics."""
+        if group_of_cam is None:
+            return self._ck(lib.psba_set_intrinsics_groups(self._h, None))
+        g = np.ascontiguousarray(np.asarray(group_of_cam).reshape(-1), dtype=np.int32)
+        if g.size != self.nC:
+            raise PsbaError(-1, f"set_intrinsics_groups: {g.size} labels for {self.nC} cameras")
+        self._ck(lib.psba_set_intrinsics_groups(self._h, g.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def intrinsics_groups(self):
+        """psba_intrinsics_groups -> (representative of each camera [nC], number of groups)"""
+        rep = np.zeros(self.nC, dtype=np.int32)
+        n = C.c_int(0)
+        self._ck(lib.psba_intrinsics_groups(self._h, rep.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n)))
+        return rep, int(n.value)
 
     def set_distortion(self, kc):
         """psba_set_distortion: kc [nC, 5] = (k1, k2, k3, k4, k5) per camera, None = no distortion.  Under

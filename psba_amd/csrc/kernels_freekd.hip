@@ -419,6 +419,177 @@ __global__ __launch_bounds__(256) void k_kd_backsub_pts(KdBackArgs p) {
   kd_block_sums4(v4, sRed, p.red + 4 * (size_t)(1 + blockIdx.x));
 }
 
+// ---- intrinsics shared between cameras (psba_set_intrinsics_groups) ----
+// A free intrinsic coordinate k < 10 of a camera that is not the representative (lowest member) of its group is
+// "folded away": its row and column are added to the representative's and it is left as a masked coordinate is.
+// The kernels below run only on a handle with groups; every sum goes over the members in ascending camera order.
+struct KdGroups {
+  const int *rep;   // [nC] representative of each camera
+  const int *gidx;  // [nC] the camera's group among those with several members, -1: alone
+  const int *gptr;  // [nmg + 1] CSR over gmem
+  const int *gmem;  // members, ascending; the first of a group is its representative
+  int nmg;
+  unsigned mask;
+};
+__device__ __forceinline__ bool kd_folded(const KdGroups &G, int t) {  // t: coordinate of the camera part
+  const int k = t % KD_CNP;
+  return k < 10 && ((G.mask >> k) & 1u) && G.rep[t / KD_CNP] != t / KD_CNP;
+}
+
+// k_kd_finalize without the damping and with the whole square symmetric entry by entry (the diagonal blocks of
+// -sum Y_a W_a^T are symmetric only to rounding: their lower triangle is the matrix), so that the fold may read any
+// entry: S = blockdiag(U) - sum Y W^T, e_a, identity padding, the accumulators zeroed, the try stamp set
+__global__ __launch_bounds__(256) void k_kd_finalize_sym(double *S, double *ea, const double *U, const double *ga,
+                                                         const double *eapart, const int *cuptr, int nA, int n32,
+                                                         double *scal, int *status, int try_id) {
+  if (blockIdx.x == 0 && threadIdx.x < 4 * SC_NPART) scal[SC_PART + threadIdx.x] = 0.0;
+  if (blockIdx.x == 0 && threadIdx.x == 64) status[3] = try_id;
+  const size_t n2 = (size_t)nA * nA;
+  const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gsize = (size_t)gridDim.x * blockDim.x;
+  for (size_t t = gtid; t < n2; t += gsize) {
+    const int r = (int)(t / nA), c = (int)(t % nA);
+    const int kb = r / KD_CNP, lb = c / KD_CNP;
+    const size_t at = (size_t)r * n32 + c;
+    if (lb > kb) {
+      S[at] = S[(size_t)c * n32 + r];
+    } else if (lb == kb && r >= c) {  // (the entries above the diagonal of a diagonal block: written from below)
+      const double v = S[at] + U[(size_t)KD_CNP * KD_CNP * kb + KD_CNP * (r - KD_CNP * kb) + (c - KD_CNP * lb)];
+      S[at] = v;
+      if (r > c) S[(size_t)c * n32 + r] = v;
+    }
+  }
+  for (size_t t = gtid; t < (size_t)nA; t += gsize) {
+    const int j = (int)(t / KD_CNP), r = (int)(t % KD_CNP);
+    double s = 0.0;
+    for (int u = cuptr[j]; u < cuptr[j + 1]; u++) s += eapart[KD_CNP * (size_t)u + r];
+    ea[t] = ga[t] - s;
+  }
+  write_padding(S, nA, n32, 1.0, gtid, gsize);
+}
+
+// row pass: thread = (group, intrinsic k, column c) owns S[(m, k)][c] of every member m; the representative's row
+// becomes the sum of the members' rows (the other rows are left for k_kd_fold_finish to clear)
+__global__ __launch_bounds__(256) void k_kd_fold_rows(double *S, KdGroups G, int nA, int n32) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)G.nmg * 10 * nA) return;
+  const int c = (int)(t % nA), gk = (int)(t / nA);
+  const int g = gk / 10, k = gk % 10;
+  if (!((G.mask >> k) & 1u)) return;
+  const int m0 = G.gptr[g], m1 = G.gptr[g + 1];
+  double s = 0.0;
+  for (int q = m0; q < m1; q++) s += S[(size_t)(KD_CNP * G.gmem[q] + k) * n32 + c];
+  S[(size_t)(KD_CNP * G.gmem[m0] + k) * n32 + c] = s;
+}
+
+// column pass, a launch of its own behind the row pass: thread = (group, row r, intrinsic k) owns S[r][(m, k)] of
+// every member m.  Row nA stands for the e_a row of the reduce buffer (row n32)
+__global__ __launch_bounds__(256) void k_kd_fold_cols(double *S, KdGroups G, int nA, int n32) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)G.nmg * (nA + 1) * 10) return;
+  const int k = (int)(t % 10);
+  const size_t u = t / 10;
+  const int r = (int)(u % (nA + 1)), g = (int)(u / (nA + 1));
+  if (!((G.mask >> k) & 1u)) return;
+  double *row = S + (size_t)(r == nA ? n32 : r) * n32;
+  const int m0 = G.gptr[g], m1 = G.gptr[g + 1];
+  double s = 0.0;
+  for (int q = m0; q < m1; q++) s += row[KD_CNP * G.gmem[q] + k];
+  row[KD_CNP * G.gmem[m0] + k] = s;
+}
+
+// behind the column pass: the folded-away coordinates cleared to what a masked coordinate is (zero row and column,
+// coeff + mu on the diagonal, e_a = 0), mu added once to the other diagonal entries, the upper triangle an exact
+// copy of the lower (the two passes sum a mirrored pair in different orders)
+__global__ __launch_bounds__(256) void k_kd_fold_finish(double *S, double *ea, KdGroups G, double coeff, double mu, int nA,
+                                                        int n32) {
+  const size_t n2 = (size_t)nA * nA;
+  const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gsize = (size_t)gridDim.x * blockDim.x;
+  for (size_t t = gtid; t < n2; t += gsize) {
+    const int r = (int)(t / nA), c = (int)(t % nA);
+    const size_t at = (size_t)r * n32 + c;
+    if (kd_folded(G, r) || kd_folded(G, c))
+      S[at] = r == c ? coeff + mu : 0.0;
+    else if (r == c)
+      S[at] += mu;
+    else if (r < c)
+      S[at] = S[(size_t)c * n32 + r];  // (below the diagonal a kept entry is not written by this kernel)
+  }
+  for (size_t t = gtid; t < (size_t)nA; t += gsize)
+    if (kd_folded(G, (int)t)) ea[t] = 0.0;
+}
+
+// k_kd_max_diag over the folded diagonal of U: a shared free coordinate counts once, with the sum over its group
+__global__ __launch_bounds__(1024) void k_kd_max_diag_groups(const double *U, const double *PV, int nC, int nP, KdGroups G,
+                                                             double *out) {
+  __shared__ double sRed[16];
+  double m = 0.0;
+  for (int t = threadIdx.x; t < KD_CNP * nC; t += blockDim.x) {
+    const int j = t / KD_CNP, r = t % KD_CNP;
+    if (r < 10 && !((G.mask >> r) & 1u)) continue;
+    const int g = r < 10 ? G.gidx[j] : -1;
+    if (g < 0) {
+      m = fmax(m, U[(size_t)KD_CNP * KD_CNP * j + (KD_CNP + 1) * r]);
+    } else if (G.rep[j] == j) {
+      double s = 0.0;
+      for (int q = G.gptr[g]; q < G.gptr[g + 1]; q++) s += U[(size_t)KD_CNP * KD_CNP * G.gmem[q] + (KD_CNP + 1) * r];
+      m = fmax(m, s);
+    }
+  }
+  for (int i = threadIdx.x; i < nP; i += blockDim.x) {
+    const double *v = PV + 9 * (size_t)i;
+    m = fmax(m, fmax(v[0], fmax(v[3], v[5])));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off, 64));
+  if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 16; w++) m = fmax(m, sRed[w]);
+    *out = m;
+  }
+}
+
+// k_kd_backsub_cams with the step expanded: a folded-away entry reads its representative's dp (which the
+// representative's own thread leaves as solved) and writes only its own; dp_l2, mu dp^2 and newp_l2 count a shared
+// parameter once, dp g goes over every entry (sum_all dp g = dp_shared P^T g)
+__global__ __launch_bounds__(256) void k_kd_backsub_cams_groups(KdBackArgs p, const int *rep) {
+  __shared__ double sRed[4][4];
+  double v4[4] = {0.0, 0.0, 0.0, 0.0};
+  if (threadIdx.x == 0) {
+    p.scal[SC_STATUS_V] = (p.status[0] == p.status[3]) ? 1.0 : 0.0;
+    p.scal[SC_STATUS_SPD] = (p.status[1] == p.status[3]) ? 1.0 : 0.0;
+  }
+  for (int t = threadIdx.x; t < p.nA; t += blockDim.x) {
+    const int j = t / KD_CNP, r = t % KD_CNP;
+    const bool held = r < 10 && !((p.mask >> r) & 1u);
+    const bool copy = r < 10 && !held && rep[j] != j;
+    double d = copy ? p.dp[KD_CNP * (size_t)rep[j] + r] : p.dp[t];
+    if (held) d = 0.0;
+    if (held || copy) p.dp[t] = d;
+    const double c = p.cams[t] + d;
+    p.newcams[t] = c;
+    if (!copy) {
+      v4[0] += d * d;
+      v4[1] += d * (p.mu * d + p.ga[t]);
+      v4[3] += c * c;
+    } else {
+      v4[1] += d * p.ga[t];
+    }
+  }
+  kd_block_sums4(v4, sRed, p.red);
+}
+
+static KdGroups kd_groups(psba_ctx *h) {
+  KdGroups G;
+  G.rep = h->kd_rep;
+  G.gidx = h->kd_gidx;
+  G.gptr = h->kd_gptr;
+  G.gmem = h->kd_gmem;
+  G.nmg = h->kd_nmg;
+  G.mask = h->kd_mask;
+  return G;
+}
+
 static KdArgs kd_args(psba_ctx *h, int set) {
   KdArgs a;
   a.camconst = h->camconst;
@@ -480,8 +651,12 @@ int launch_residual_kd(psba_ctx *h, int which) {
 }
 
 int launch_max_diag_kd(psba_ctx *h) {
-  hipLaunchKernelGGL(k_kd_max_diag, dim3(1), dim3(1024), 0, h->stream, h->U, h->PV, h->d.nC, h->d.nP, h->kd_mask,
-                     h->scal + SC_MAXDIAG);
+  if (h->kd_rep)
+    hipLaunchKernelGGL(k_kd_max_diag_groups, dim3(1), dim3(1024), 0, h->stream, h->U, h->PV, h->d.nC, h->d.nP, kd_groups(h),
+                       h->scal + SC_MAXDIAG);
+  else
+    hipLaunchKernelGGL(k_kd_max_diag, dim3(1), dim3(1024), 0, h->stream, h->U, h->PV, h->d.nC, h->d.nP, h->kd_mask,
+                       h->scal + SC_MAXDIAG);
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }
@@ -502,8 +677,18 @@ int launch_schur_kd(psba_ctx *h, double mu) {
       hipLaunchKernelGGL(k_kd_combine, dim3(h->kd_nmulti), dim3(256), 0, h->stream, h->kd_multi, h->kd_tiles, S, h->n32);
     const size_t n2 = (size_t)d.nA * d.nA;
     const int fgrid = (int)((n2 + 255) / 256 > 4096 ? 4096 : (n2 + 255) / 256);
-    hipLaunchKernelGGL(k_kd_finalize, dim3(fgrid), dim3(256), 0, h->stream, S, ea, h->U, h->ga, h->kd_eapart, h->kd_cuptr, mu,
-                       d.nA, h->n32, h->scal, h->status, h->try_id);
+    if (h->kd_rep) {  // shared intrinsics: the undamped symmetric square, the fold in two passes, then mu and the mirror
+      const KdGroups G = kd_groups(h);
+      const size_t nrow = (size_t)G.nmg * 10 * d.nA, ncol = (size_t)G.nmg * 10 * (d.nA + 1);
+      hipLaunchKernelGGL(k_kd_finalize_sym, dim3(fgrid), dim3(256), 0, h->stream, S, ea, h->U, h->ga, h->kd_eapart,
+                         h->kd_cuptr, d.nA, h->n32, h->scal, h->status, h->try_id);
+      hipLaunchKernelGGL(k_kd_fold_rows, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, h->stream, S, G, d.nA, h->n32);
+      hipLaunchKernelGGL(k_kd_fold_cols, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, h->stream, S, G, d.nA, h->n32);
+      hipLaunchKernelGGL(k_kd_fold_finish, dim3(fgrid), dim3(256), 0, h->stream, S, ea, G, h->coeff, mu, d.nA, h->n32);
+    } else {
+      hipLaunchKernelGGL(k_kd_finalize, dim3(fgrid), dim3(256), 0, h->stream, S, ea, h->U, h->ga, h->kd_eapart, h->kd_cuptr,
+                         mu, d.nA, h->n32, h->scal, h->status, h->try_id);
+    }
   }
   h->packed_pending = false;
   PSBA_HIP(h, hipGetLastError());
@@ -534,7 +719,10 @@ int launch_backsub_kd(psba_ctx *h, double mu) {
   a.nP = d.nP;
   const int grid = kd_grid(d.nP, KD_RED / 4 - 8);
   ProfScope ps(h, PSBA_K_BACKSUB);
-  hipLaunchKernelGGL(k_kd_backsub_cams, dim3(1), dim3(256), 0, h->stream, a);
+  if (h->kd_rep)
+    hipLaunchKernelGGL(k_kd_backsub_cams_groups, dim3(1), dim3(256), 0, h->stream, a, (const int *)h->kd_rep);
+  else
+    hipLaunchKernelGGL(k_kd_backsub_cams, dim3(1), dim3(256), 0, h->stream, a);
   hipLaunchKernelGGL(k_kd_backsub_pts, dim3(grid), dim3(256), 0, h->stream, a);
   // set 0 of the SC_NPART partial sets carries the whole sums (k_kd_finalize zeroed the others)
   hipLaunchKernelGGL(k_kd_sum_columns, dim3(1), dim3(64), 0, h->stream, (const double *)h->kd_red, (const double *)h->kd_red + 4,

@@ -233,6 +233,9 @@ static void lens_changed(psba_ctx *h) {
   h->linearized = h->assembled = h->solved = false;
 }
 
+static int groups_split(psba_ctx *h, const char *who, const std::vector<int> &rep, const double *v, int stride, int ncols,
+                        int col0);
+
 // PSBA_CAMERA_FREE_KD: kc is part of the camera block -- the starting values go into columns 5..9 of the current
 // parameters and of the copy psba_reset_params restores
 static int set_start_distortion(psba_ctx *h, const double *kc) {
@@ -240,6 +243,7 @@ static int set_start_distortion(psba_ctx *h, const double *kc) {
   const int nC = h->d.nC;
   for (int t = 0; kc && t < 5 * nC; t++)
     if (!std::isfinite(kc[t])) return fail(h, PSBA_E_INVALID, "psba_set_distortion: kc[%d] of camera %d is not finite", t % 5, t / 5);
+  if (kc && !h->kd_rep_h.empty()) TRY(groups_split(h, "psba_set_distortion", h->kd_rep_h, kc, 5, 5, 5));
   std::vector<double> c((size_t)h->d.nA);
   double *dst[2] = {h->cams[h->cur], h->params0};
   for (int k = 0; k < 2; k++) {
@@ -420,6 +424,96 @@ int psba_intrinsics_mask(psba_handle h, unsigned char *out10) {
   NEED(h, h->uploaded, "no problem uploaded");
   NEED(h, h->cnp == KD_CNP, "psba_intrinsics_mask: PSBA_CAMERA_FREE_KD only");
   for (int k = 0; out10 && k < 10; k++) out10[k] = (h->kd_mask >> k) & 1u;
+  return PSBA_OK;
+}
+
+// ---- intrinsics shared between cameras (PSBA_CAMERA_FREE_KD) ----
+// members of a group hold bit-identical intrinsics: v[stride j + k], k < ncols, against the representative's; the
+// message counts columns from col0 (the camera block's numbering)
+static int groups_split(psba_ctx *h, const char *who, const std::vector<int> &rep, const double *v, int stride, int ncols,
+                        int col0) {
+  for (int j = 0; j < (int)rep.size(); j++)
+    for (int k = 0; rep[j] != j && k < ncols; k++)
+      if (memcmp(v + (size_t)stride * j + k, v + (size_t)stride * rep[j] + k, sizeof(double)) != 0)
+        return fail(h, PSBA_E_INVALID, "%s: camera %d differs from camera %d, the representative of its group, in column %d "
+                    "(%.17g against %.17g): members of a group hold bit-identical intrinsics",
+                    who, j, rep[j], col0 + k, v[(size_t)stride * j + k], v[(size_t)stride * rep[j] + k]);
+  return PSBA_OK;
+}
+
+int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp == KD_CNP, "psba_set_intrinsics_groups: PSBA_CAMERA_FREE_KD only");
+  NEED(h, !h->backsub_pending, "psba_set_intrinsics_groups: a damping try is in flight (psba_backsub_wait first)");
+  const int nC = h->d.nC;
+  // the representative of a label is the first camera that carries it
+  std::vector<int> rep((size_t)nC), order((size_t)nC);
+  for (int j = 0; j < nC; j++) order[j] = j;
+  if (group_of_cam)
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return group_of_cam[a] < group_of_cam[b]; });
+  int ngroups = 0;
+  for (int t = 0; t < nC; t++) {
+    const bool first = !group_of_cam || t == 0 || group_of_cam[order[t]] != group_of_cam[order[t - 1]];
+    rep[order[t]] = first ? order[t] : rep[order[t - 1]];
+    ngroups += first ? 1 : 0;
+  }
+  std::vector<int> gidx((size_t)nC, -1), gptr(1, 0), gmem;
+  DevBuf<int> d_rep, d_gidx, d_gptr, d_gmem;
+  if (ngroups < nC) {  // (every camera alone is no grouping: the ungrouped launches)
+    std::vector<double> c((size_t)h->d.nA);
+    const double *src[2] = {h->cams[h->cur], h->params0};
+    const char *who[2] = {"psba_set_intrinsics_groups (current parameters)", "psba_set_intrinsics_groups (the psba_reset_params copy)"};
+    for (int k = 0; k < 2; k++) {
+      PSBA_HIP(h, hipMemcpyAsync(c.data(), src[k], sizeof(double) * c.size(), hipMemcpyDeviceToHost, h->stream));
+      PSBA_HIP(h, hipStreamSynchronize(h->stream));
+      TRY(groups_split(h, who[k], rep, c.data(), KD_CNP, 10, 0));
+    }
+    std::vector<int> count((size_t)nC, 0);
+    for (int j = 0; j < nC; j++) count[rep[j]]++;
+    for (int j = 0; j < nC; j++)  // groups in the order of their representatives, members ascending
+      if (rep[j] == j && count[j] > 1) {
+        for (int m = j; m < nC; m++)
+          if (rep[m] == j) {
+            gidx[m] = (int)gptr.size() - 1;
+            gmem.push_back(m);
+          }
+        gptr.push_back((int)gmem.size());
+      }
+    // staged in buffers of their own and swapped in when all are on the device (as psba_set_fixed does)
+    auto stage = [&](DevBuf<int> &dst, const std::vector<int> &v) -> int {
+      TRY(dst.alloc(h, v.size()));
+      PSBA_HIP(h, hipMemcpyAsync(dst, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice, h->stream));
+      return PSBA_OK;
+    };
+    int rc = stage(d_rep, rep);
+    if (rc == PSBA_OK) rc = stage(d_gidx, gidx);
+    if (rc == PSBA_OK) rc = stage(d_gptr, gptr);
+    if (rc == PSBA_OK) rc = stage(d_gmem, gmem);
+    const hipError_t e = hipStreamSynchronize(h->stream);  // (also before a staged buffer goes)
+    if (rc != PSBA_OK) return rc;
+    PSBA_HIP(h, e);
+  } else {
+    PSBA_HIP(h, hipStreamSynchronize(h->stream));  // nothing queued still reads the old tables
+    rep.clear();
+  }
+  h->kd_rep_h = std::move(rep);
+  h->kd_ngroups = h->kd_rep_h.empty() ? 0 : ngroups;
+  h->kd_nmg = (int)gptr.size() - 1;
+  h->kd_rep = std::move(d_rep);
+  h->kd_gidx = std::move(d_gidx);
+  h->kd_gptr = std::move(d_gptr);
+  h->kd_gmem = std::move(d_gmem);
+  lens_changed(h);
+  return PSBA_OK;
+}
+
+int psba_intrinsics_groups(psba_handle h, int *rep_of_cam, int *n_groups) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp == KD_CNP, "psba_intrinsics_groups: PSBA_CAMERA_FREE_KD only");
+  for (int j = 0; rep_of_cam && j < h->d.nC; j++) rep_of_cam[j] = h->kd_rep_h.empty() ? j : h->kd_rep_h[j];
+  if (n_groups) *n_groups = h->kd_rep_h.empty() ? h->d.nC : h->kd_ngroups;
   return PSBA_OK;
 }
 
@@ -887,6 +981,7 @@ int psba_upload_problem(psba_handle h, int nCams, int n3Dpts, int n2Dprojs, cons
 int psba_set_params(psba_handle h, const double *camsEx, const double *pts3D) {
   CHECK_H(h);
   NEED(h, h->uploaded, "no problem uploaded");
+  if (!h->kd_rep_h.empty()) TRY(groups_split(h, "psba_set_params", h->kd_rep_h, camsEx, KD_CNP, 10, 0));
   PSBA_HIP(h, hipMemcpyAsync(h->cams[h->cur], camsEx, sizeof(double) * h->d.nA,
                              hipMemcpyHostToDevice, h->stream));
   PSBA_HIP(h, hipMemcpyAsync(h->pts[h->cur], pts3D, sizeof(double) * h->d.nB,

@@ -298,6 +298,14 @@ struct ProblemState {
   psba::DevBuf<double> kd_tiles;   // [ntiles][256] partial tiles of the blocks with several segments
   int kd_nsegs = 0, kd_nmulti = 0;
   psba::DevBuf<double> kd_red;     // [KD_RED] per-workgroup partial sums (cost; the try's four sums)
+  // shared intrinsics (psba_set_intrinsics_groups): empty / null = no grouping, the ungrouped launches
+  std::vector<int> kd_rep_h;       // [nC] representative (lowest member) of each camera's group; empty: none
+  int kd_ngroups = 0;              // groups in all (singletons included) while kd_rep_h is set
+  psba::DevBuf<int> kd_rep;        // [nC] kd_rep_h on the device
+  psba::DevBuf<int> kd_gidx;       // [nC] index of the camera's group among those with several members, -1: alone
+  psba::DevBuf<int> kd_gptr;       // [kd_nmg + 1] CSR over kd_gmem of the groups with several members
+  psba::DevBuf<int> kd_gmem;       // their members in ascending camera order (the first is the representative)
+  int kd_nmg = 0;
   psba::DevBuf<double> dp;        // [nT] dpa | dpb                     (dp_buffer)
   psba::DevBuf<double> trv[2];    // [nT] each: vectors of the trust-region operators (allocated on first use)
   psba::DevBuf<double> jmul_out;  // [2 nO] J x of psba_compute_Jmultiply (allocated on first use)
