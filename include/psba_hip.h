@@ -94,8 +94,9 @@ int psba_get_dims(psba_handle h, int *nCams, int *n3Dpts, int *n2Dprojs);
  * optimise six (CL_files/PSBA.cl:5-7).  PSBA_CAMERA_FREE_K optimises all eleven: the camera block becomes
  * (fu, u0, v0, ar, s | v0, v1, v2 | t0, t1, t2), nA = 11 nCams, dp = [11 per camera ; 3 per point].
  * psba_upload_problem takes the same arrays (Kparas and camsEx are joined inside); psba_get_params /
- * psba_set_params then move 11 doubles per camera.  One plain route (kernels_freek.hip: global-atomic assembly,
- * the generic dense factorization), single rank, dense solver; the fused verbs and psba_levmar work, the
+ * psba_set_params then move 11 doubles per camera.  The route is PSBA_CAMERA_FREE_KD's (kernels_free.hip, templated on
+ * the block: a 16 x 16 MFMA tile with five idle rows and columns, no floating-point atomics, two runs bit-identical;
+ * psba_schur_path = 5), single rank, dense solver; the fused verbs and psba_levmar work, the
  * sba_func.h mirror, the trust-region operators and psba_solve return PSBA_E_STATE.  The reference has no
  * arithmetic for this (it never implemented it): PARITY UNPINNED -- checked against the oracle's twin, finite
  * differences and a dense solve of the full normal equations.  Before psba_upload_problem. */
@@ -126,7 +127,7 @@ int psba_camera_block(psba_handle h, int *cnp); /* 6, 11 or 16 */
  * of A is zero, the stored diagonal entry of U_j is the placeholder coeff, g and dp are exactly 0, the proposed and
  * accepted values are bit-identical to the current ones, psba_max_diag / psba_begin take the maximum over the free
  * entries, row and column of S are zero off the diagonal with coeff + mu on it, and e_a is 0.
- * Route (kernels_freekd.hip, psba_schur_path = 5): camera-major linearization and S assembly on
+ * Route (kernels_free.hip, psba_schur_path = 5): camera-major linearization and S assembly on
  * v_mfma_f64_16x16x4_f64, no floating-point atomics -- two runs give bit-identical reduce buffers and logs.  Single
  * rank, dense solver.  The fused verbs, psba_levmar, psba_get_dp, psba_get_gradient and psba_get / set_reduce_buffer
  * work; covariances, robust losses, psba_set_fixed, PSBA_SOLVER_PCG, rank layouts, the sba_func.h mirror, the
@@ -263,10 +264,8 @@ int psba_fixed_counts(psba_handle h, int *n_fixed_cams, int *n_fixed_pts);
  * products sorted by camera pair, sums in registers; PSBA_SCHUR_OWNER=1 forces it), 2 = global
  * fp64 atomics straight into S (the
  * first-generation kernel, kept for cross-checks: PSBA_SCHUR_ATOMIC=1), 3 = the ring route (opt-in
- * experiment, PSBA_SCHUR_RING=1), 4 = block-sparse S (PSBA_SOLVER_PCG), 5 = the 16-parameter camera block
- * (PSBA_CAMERA_FREE_KD: products sorted by block, one MFMA per product).  The 11-parameter block (PSBA_CAMERA_FREE_K)
- * has no number of its own: it runs the thread-per-observation route of kernels_freek.hip (global fp64 atomics) and
- * the call reports 1 for it, which says nothing about that route.  The reference has one
+ * experiment, PSBA_SCHUR_RING=1), 4 = block-sparse S (PSBA_SOLVER_PCG), 5 = the free-intrinsics route (blocks of 11
+ * and 16: products sorted by block, one MFMA per product).  The reference has one
  * route for every size (CL_files/compute_S.cl:6-78). */
 int psba_schur_path(psba_handle h, int *path);
 

@@ -600,8 +600,7 @@ class Psba:
     # ---- fused verbs ----
     def schur_path(self):
         """0: LDS-partition schedule, 1: owner route, 2: global-atomic assembly kernel, 3: ring route, 4: block-sparse,
-        5: the 16-parameter camera block (psba_schur_path).  Blocks of 11 report 1 although they run a route of their
-        own (kernels_freek.hip, global atomics): the value says nothing about it."""
+        5: the free-intrinsics route (blocks of 11 and 16) (psba_schur_path)."""
         v = C.c_int()
         self._ck(lib.psba_schur_path(self._h, C.byref(v)))
         return v.value

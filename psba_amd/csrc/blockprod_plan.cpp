@@ -1,4 +1,4 @@
-// blockprod_plan.cpp -- the S-assembly schedule of the 16-parameter camera block (kernels_freekd.hip),
+// blockprod_plan.cpp -- the S-assembly schedule of the free-intrinsics camera blocks (kernels_free.hip),
 // built once per upload on the host: every product Y_a W_b^T (b <= a, both observations of one point) belongs to the
 // block (camera of a, camera of b) of the lower block triangle.  The products are sorted by block, inside a block by
 // point (the order the sums are formed in: fixed by the problem, not by the run), and every block's list is cut into

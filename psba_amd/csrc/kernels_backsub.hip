@@ -395,7 +395,7 @@ static void enqueue_backsub(psba_ctx *h, const BackArgs &a, const RobustLoss &rl
 }
 
 int launch_backsub(psba_ctx *h, double mu, bool dump) {
-  if (h->cnp != 6) return dump ? mirror_refused(h) : h->cnp == KD_CNP ? launch_backsub_kd(h, mu) : launch_backsub_fk(h, mu);
+  if (h->cnp != 6) return dump ? mirror_refused(h) : launch_backsub_free(h, mu);
   const Dims &d = h->d;
   BackArgs a;
   a.W = h->W;

@@ -711,7 +711,7 @@ static void enqueue_linearize(psba_ctx *h, const LinArgs &a, const RobustLoss &r
 }
 
 int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
-  if (h->cnp != 6) return dump ? mirror_refused(h) : h->cnp == KD_CNP ? launch_linearize_kd(h, ahead, publish) : launch_linearize_fk(h, ahead, publish);
+  if (h->cnp != 6) return dump ? mirror_refused(h) : launch_linearize_free(h, ahead, publish);
   const Dims &d = h->d;
   LinArgs a;
   a.camconst = h->camconst;
@@ -775,7 +775,7 @@ int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
 }
 
 int launch_residual(psba_ctx *h, int which, double *ex_out_dev, double *s_out_dev) {
-  if (h->cnp != 6) return ex_out_dev || s_out_dev ? mirror_refused(h) : h->cnp == KD_CNP ? launch_residual_kd(h, which) : launch_residual_fk(h, which);
+  if (h->cnp != 6) return ex_out_dev || s_out_dev ? mirror_refused(h) : launch_residual_free(h, which);
   const Dims &d = h->d;
   const int set = which == PSBA_PARAMS_NEW ? 1 - h->cur : h->cur;
   PSBA_HIP(h, hipMemsetAsync(h->scal + SC_COST, 0, sizeof(double), h->stream));
@@ -796,7 +796,7 @@ int launch_residual(psba_ctx *h, int which, double *ex_out_dev, double *s_out_de
 }
 
 int launch_max_diag(psba_ctx *h) {
-  if (h->cnp != 6) return h->cnp == KD_CNP ? launch_max_diag_kd(h) : launch_max_diag_fk(h);
+  if (h->cnp != 6) return launch_max_diag_free(h);
   PSBA_HIP(h, hipMemsetAsync(h->scal + SC_MAXDIAG, 0, sizeof(double), h->stream));
   int grid = (h->d.nP + 255) / 256;
   if (grid > 512) grid = 512;

@@ -894,7 +894,7 @@ static int launch_schur_sparse(psba_ctx *h, double mu) {
 }
 
 int launch_schur(psba_ctx *h, double mu, bool dump) {
-  if (h->cnp != 6) return dump ? mirror_refused(h) : h->cnp == KD_CNP ? launch_schur_kd(h, mu) : launch_schur_fk(h, mu);
+  if (h->cnp != 6) return dump ? mirror_refused(h) : launch_schur_free(h, mu);
   h->try_id++;
   h->diag_done = false;
   h->packed_pending = false;  // status words are generation stamps: nothing to zero

@@ -204,7 +204,7 @@ int psba_destroy(psba_handle h) {
 int psba_schur_path(psba_handle h, int *path) {
   CHECK_H(h);
   NEED(h, h->uploaded, "no problem uploaded");
-  if (path) *path = h->cnp == KD_CNP ? 5 : h->solver == PSBA_SOLVER_PCG ? 4 : getenv("PSBA_SCHUR_ATOMIC") ? 2 : h->ring_nWg > 0 ? 3 : h->nGroups > 0 ? 0 : 1;
+  if (path) *path = h->cnp != 6 ? 5 : h->solver == PSBA_SOLVER_PCG ? 4 : getenv("PSBA_SCHUR_ATOMIC") ? 2 : h->ring_nWg > 0 ? 3 : h->nGroups > 0 ? 0 : 1;
   return PSBA_OK;
 }
 
@@ -607,7 +607,7 @@ static void cut_tiles(Upload &u) {
 
 // the sizes everything else is cut to, and which form K1's camera sums take
 static void set_dims(psba_ctx *h, const Upload &u) {
-  const int cnp = h->cnp;  // 6, 11 with free intrinsics (kernels_freek.hip) or 16 with distortion too (kernels_freekd.hip)
+  const int cnp = h->cnp;  // 6, 11 with free intrinsics or 16 with distortion too (both kernels_free.hip)
   Dims d;
   d.nC = u.nC;
   d.nP = u.nP;
@@ -657,11 +657,10 @@ static int alloc_work_buffers(psba_ctx *h) {
   TRY(h->ga.alloc(h, (size_t)d.nA));
   TRY(h->ga_alt.alloc(h, (size_t)d.nA));
   TRY(h->campart.alloc(h, (h->cam_global || cnp != 6) ? 1 : (size_t)(h->nPart + 1) * d.nC * CAM_ACC));  // (+1: the long points' slab)
-  if (cnp == FK_CNP) TRY(h->camacc.alloc(h, (size_t)d.nC * (cnp * (cnp + 1) / 2 + cnp)));  // kernels_freek.hip: 66 + 11 sums per camera
-  if (cnp == KD_CNP) {  // kernels_freekd.hip (the per-unit buffers: upload_camera_index)
-    TRY(h->kd_Be.alloc(h, (size_t)8 * d.nO));
-    TRY(h->kd_Y.alloc(h, (size_t)3 * cnp * d.nO));
-    TRY(h->kd_red.alloc(h, (size_t)KD_RED));
+  if (cnp != 6) {  // kernels_free.hip (the per-unit buffers: upload_camera_index)
+    TRY(h->free_Be.alloc(h, (size_t)8 * d.nO));
+    TRY(h->free_Y.alloc(h, (size_t)3 * cnp * d.nO));
+    TRY(h->free_red.alloc(h, (size_t)KD_RED));
   }
   if (h->cam_global) TRY(h->camacc.alloc(h, (size_t)d.nC * CAM_ACC));
   // rows [0, n32 + 16) are the reduce buffer proper; n32 more rows below it are the working
@@ -680,9 +679,10 @@ static int alloc_work_buffers(psba_ctx *h) {
 }
 
 // camera-major index of the observations, cut into segments of at most 256 (K1's camera sums with many cameras) or
-// KD_UNIT (the 16-parameter block: one observation per lane of a wave, and the units of each camera by kd_cuptr)
+// KD_UNIT (free intrinsics: one observation per lane of a wave, and the units of each camera by free_cuptr)
 static int upload_camera_index(psba_ctx *h, const Upload &u) {
-  const bool kd = h->cnp == KD_CNP;
+  const int cnp = h->cnp;
+  const bool kd = cnp != 6;
   std::vector<int> cptr((size_t)u.nC + 1, 0), cobs((size_t)u.nO);
   for (int a = 0; a < u.nO; a++) cptr[(size_t)u.jidx[a] + 1]++;
   for (int j = 0; j < u.nC; j++) cptr[(size_t)j + 1] += cptr[j];
@@ -700,9 +700,9 @@ static int upload_camera_index(psba_ctx *h, const Upload &u) {
   }
   h->nCamUnits = (int)units.size();
   if (kd) {
-    TRY(upload(h, h->kd_cuptr, cuptr));
-    TRY(h->kd_upart.alloc(h, (size_t)(KD_CNP * KD_CNP + KD_CNP) * units.size()));
-    TRY(h->kd_eapart.alloc(h, (size_t)KD_CNP * units.size()));
+    TRY(upload(h, h->free_cuptr, cuptr));
+    TRY(h->free_upart.alloc(h, (size_t)(cnp * cnp + cnp) * units.size()));
+    TRY(h->free_eapart.alloc(h, (size_t)cnp * units.size()));
   }
   TRY(upload(h, h->cam_obs, cobs));
   return upload(h, h->cam_units, units);
@@ -885,7 +885,7 @@ static int plan_schur_lds(psba_ctx *h, const Upload &u) {
   return PSBA_OK;
 }
 
-// the 16-parameter block: products sorted by block, cut into segments (blockprod_plan.cpp); PSBA_FKD_SEG=n sets the
+// free intrinsics: products sorted by block, cut into segments (blockprod_plan.cpp); PSBA_FKD_SEG=n sets the
 // segment length for tests and sweeps
 static int plan_schur_blockprod(psba_ctx *h, const Upload &u) {
   int seg = KD_SEG_DEFAULT;
@@ -893,14 +893,14 @@ static int plan_schur_blockprod(psba_ctx *h, const Upload &u) {
     if (atoi(e) > 0) seg = atoi(e);
   BlockProdPlanHost plan;
   if (build_blockprod_plan(u.nC, u.nO, u.iidx, u.jidx, u.ptr.data(), seg, plan) != PSBA_OK)
-    return fail(h, PSBA_E_INVALID, "PSBA_CAMERA_FREE_KD: more than 2^31 products Y_a W_b^T");
-  TRY(upload(h, h->kd_blocks, plan.blocks));
-  TRY(upload(h, h->kd_segs, plan.segs));
-  TRY(upload(h, h->kd_prods, plan.prods));
-  if (!plan.multi.empty()) TRY(upload(h, h->kd_multi, plan.multi));
-  TRY(h->kd_tiles.alloc(h, (size_t)256 * (plan.ntiles ? plan.ntiles : 1)));
-  h->kd_nsegs = (int)plan.segs.size();
-  h->kd_nmulti = (int)plan.multi.size();
+    return fail(h, PSBA_E_INVALID, "%s: more than 2^31 products Y_a W_b^T", h->cnp == KD_CNP ? "PSBA_CAMERA_FREE_KD" : "PSBA_CAMERA_FREE_K");
+  TRY(upload(h, h->free_blocks, plan.blocks));
+  TRY(upload(h, h->free_segs, plan.segs));
+  TRY(upload(h, h->free_prods, plan.prods));
+  if (!plan.multi.empty()) TRY(upload(h, h->free_multi, plan.multi));
+  TRY(h->free_tiles.alloc(h, (size_t)h->cnp * h->cnp * (plan.ntiles ? plan.ntiles : 1)));
+  h->free_nsegs = (int)plan.segs.size();
+  h->free_nmulti = (int)plan.multi.size();
   return PSBA_OK;
 }
 
@@ -910,8 +910,7 @@ static int plan_schur(psba_ctx *h, const Upload &u) {
   TRY(plan_schur_ring(h, u));
   if (h->ring_nWg) return PSBA_OK;
 #endif
-  if (h->cnp == KD_CNP) return plan_schur_blockprod(h, u);
-  if (h->cnp != 6) return PSBA_OK;  // the 11-parameter route needs no schedule (global atomics straight into S)
+  if (h->cnp != 6) return plan_schur_blockprod(h, u);
   return plan_schur_lds(h, u);
 }
 
@@ -968,7 +967,7 @@ int psba_upload_problem(psba_handle h, int nCams, int n3Dpts, int n2Dprojs, cons
   drop_problem(h);  // from here on the handle holds no problem until this upload has succeeded
   set_dims(h, u);
   TRY(alloc_work_buffers(h));
-  if (h->cam_global || h->cnp == KD_CNP) TRY(upload_camera_index(h, u));
+  if (h->cam_global || h->cnp != 6) TRY(upload_camera_index(h, u));
   TRY(plan_schur(h, u));
   TRY(copy_inputs(h, u));
   // the blocking copies went through the null stream, which this handle's non-blocking stream does not wait for:

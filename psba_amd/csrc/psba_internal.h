@@ -142,7 +142,7 @@ struct SchurPlanHost {
   long long tasks = 0;
   long long pair_items = 0;  // rows layout: items that carry two products of one observation (SchurWg::itemD)
 };
-// ---- the 16-parameter camera block (PSBA_CAMERA_FREE_KD, kernels_freekd.hip): the products Y_a W_b^T, b <= a of one
+// ---- the camera blocks of 11 and 16 (free intrinsics, kernels_free.hip): the products Y_a W_b^T, b <= a of one
 // point, sorted by block (j_a, j_b) of the lower block triangle and inside a block by point; every block's list cut
 // into segments of at most seg_len products (one wave each).  blockprod_plan.cpp, host only
 struct BlockProdPlanHost {
@@ -150,7 +150,7 @@ struct BlockProdPlanHost {
   std::vector<int4> segs;    // (block, first product, end product, partial tile or -1: the block's only segment)
   std::vector<int2> prods;   // (a, b) observation indices
   std::vector<int4> multi;   // the blocks with several segments: (j, k, first partial tile, tiles)
-  int ntiles = 0;            // partial tiles (16 x 16 doubles each)
+  int ntiles = 0;            // partial tiles (a camera block squared each)
   int seg_len = 0;
 };
 constexpr int KD_UNIT = 64;        // observations of a camera unit on this route: one wave, one observation per lane
@@ -286,18 +286,19 @@ struct ProblemState {
   psba::DevBuf<psba::OwnerUnit> own_units;
   int own_nwaves = 0;
   long long own_products = 0;
-  // the 16-parameter camera block (PSBA_CAMERA_FREE_KD, kernels_freekd.hip): no floating-point atomics on this route
+  // the camera blocks of cnp = 11 and 16 (free intrinsics, kernels_free.hip): no floating-point atomics on this route
+  psba::DevBuf<int> free_cuptr;      // [nC+1] the units cam_units[free_cuptr[j] .. free_cuptr[j+1]) of camera j
+  psba::DevBuf<double> free_Be;      // [nO][8] B (2 x 3) | e of the linearization in flight (read by the per-point pass)
+  psba::DevBuf<double> free_upart;   // [nCamUnits][cnp^2 + cnp] per-unit sums A^T A (cnp x cnp) | A^T e
+  psba::DevBuf<double> free_Y;       // [nO][3 cnp] Y_a = W_a (V_i + mu I)^-1 of the try
+  psba::DevBuf<double> free_eapart;  // [nCamUnits][cnp] per-unit sums Y_a g_b,i
+  psba::DevBuf<int2> free_blocks, free_prods;  // BlockProdPlanHost on the device
+  psba::DevBuf<int4> free_segs, free_multi;
+  psba::DevBuf<double> free_tiles;   // [ntiles][cnp^2] partial tiles of the blocks with several segments
+  int free_nsegs = 0, free_nmulti = 0;
+  psba::DevBuf<double> free_red;     // [KD_RED] per-workgroup partial sums (cost; the try's four sums)
+  // blocks of 16 only (the setters refuse the others, which so keep every intrinsic free and no groups)
   unsigned kd_mask = 0x3FFu;       // psba_set_intrinsics_mask: bit k set = intrinsic k is optimised
-  psba::DevBuf<int> kd_cuptr;      // [nC+1] the units cam_units[kd_cuptr[j] .. kd_cuptr[j+1]) of camera j
-  psba::DevBuf<double> kd_Be;      // [nO][8] B (2 x 3) | e of the linearization in flight (read by the per-point pass)
-  psba::DevBuf<double> kd_upart;   // [nCamUnits][272] per-unit sums A^T A (16 x 16) | A^T e
-  psba::DevBuf<double> kd_Y;       // [nO][48] Y_a = W_a (V_i + mu I)^-1 of the try
-  psba::DevBuf<double> kd_eapart;  // [nCamUnits][16] per-unit sums Y_a g_b,i
-  psba::DevBuf<int2> kd_blocks, kd_prods;  // BlockProdPlanHost on the device
-  psba::DevBuf<int4> kd_segs, kd_multi;
-  psba::DevBuf<double> kd_tiles;   // [ntiles][256] partial tiles of the blocks with several segments
-  int kd_nsegs = 0, kd_nmulti = 0;
-  psba::DevBuf<double> kd_red;     // [KD_RED] per-workgroup partial sums (cost; the try's four sums)
   // shared intrinsics (psba_set_intrinsics_groups): empty / null = no grouping, the ungrouped launches
   std::vector<int> kd_rep_h;       // [nC] representative (lowest member) of each camera's group; empty: none
   int kd_ngroups = 0;              // groups in all (singletons included) while kd_rep_h is set
@@ -425,20 +426,14 @@ int launch_schur_expand(psba_ctx *h);
 // kernels_chol.hip
 int launch_chol_solve(psba_ctx *h);
 int mirror_refused(psba_ctx *h);  // the sba_func.h mirror (dumps, per-observation outputs) asked of a block wider than 6
-// kernels_freek.hip: the 11-parameter camera block (free intrinsics), one plain route
-int launch_linearize_fk(psba_ctx *h, bool ahead, bool publish);
-int launch_residual_fk(psba_ctx *h, int which);
-int launch_max_diag_fk(psba_ctx *h);
-int launch_schur_fk(psba_ctx *h, double mu);
-int launch_backsub_fk(psba_ctx *h, double mu);
-// kernels_freekd.hip: the 16-parameter camera block (free intrinsics and distortion), MFMA sums in fixed order
+// kernels_free.hip: the camera blocks of 11 and 16 (free intrinsics; with distortion), MFMA sums in fixed order
 int build_blockprod_plan(int nCams, int nObs, const int *iidx, const int *jidx, const int *ptr, int seg_len,
                          BlockProdPlanHost &out);  // blockprod_plan.cpp
-int launch_linearize_kd(psba_ctx *h, bool ahead, bool publish);
-int launch_residual_kd(psba_ctx *h, int which);
-int launch_max_diag_kd(psba_ctx *h);
-int launch_schur_kd(psba_ctx *h, double mu);
-int launch_backsub_kd(psba_ctx *h, double mu);
+int launch_linearize_free(psba_ctx *h, bool ahead, bool publish);
+int launch_residual_free(psba_ctx *h, int which);
+int launch_max_diag_free(psba_ctx *h);
+int launch_schur_free(psba_ctx *h, double mu);
+int launch_backsub_free(psba_ctx *h, double mu);
 // kernels_pcg.hip
 int launch_bsr_finalize(psba_ctx *h, double mu);
 int launch_pcg_solve(psba_ctx *h);

@@ -2,7 +2,8 @@
 back-substitution) with camera blocks of 11 (PSBA_CAMERA_FREE_K) and of 16 (PSBA_CAMERA_FREE_KD: all ten intrinsics
 free, and the mask of Bundle Adjustment in the Large), on 54camsvarK / 54pts and on the venice-shaped problem.  The
 variants are alternated within one process (one LM run of each per round), so that drift of the machine hits all of
-them alike.  --seg sweeps the segment length of the 16-block S assembly (PSBA_FKD_SEG, read at upload).
+them alike; both blocks run the kernels of kernels_free.hip.  --seg sweeps the segment length of the S assembly
+(PSBA_FKD_SEG, read at upload; the sweep opens handles of the 16-block only).
 Usage: python scripts/freekd_time.py [--rounds N] [--iters N] [--seg 16,64,256] [--problem p54|venice|both]"""
 import argparse
 import os

@@ -1,6 +1,6 @@
 """The inputs and judges of tests/test_gpu_free_entrywise.py on the host (no GPU): the fp64 twin against its own sums
 in extended precision on the new inputs, the closed-form 3 x 3 inverse against the L D L^T substitution where it
-matters (why kernels_freek.hip forms Y and dp_b by substitution), the dp_b / dp_a / try-scalar judges of
+matters (why kernels_free.hip forms Y and dp_b by substitution), the dp_b / dp_a / try-scalar judges of
 tests/free_ref.py applied to a plain fp64 evaluation, and injected faults each judge must catch."""
 import functools
 

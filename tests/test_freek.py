@@ -146,3 +146,23 @@ def test_freek_levmar_against_the_twin(cams, pts, max_pts):
     with pytest.raises(psba_amd.PsbaError):
         h.compute_S()
     h.close()
+
+
+@pytest.mark.gpu
+def test_freek_two_runs_are_bit_identical():
+    """Blocks of 11 sum in an order the upload fixes (no floating-point atomics): two psba_levmar runs from
+    psba_reset_params give the same log and the same final parameters, bit for bit."""
+    import psba_amd
+    p = _problem("7camsvarK.txt", "7pts.txt")
+    h = psba_amd.Psba(0)
+    h.set_camera_model(True)
+    h.upload_problem(p)
+    assert h.schur_path() == 5
+    runs = []
+    for _ in range(2):
+        h.reset_params()
+        _, log = h.levmar(max_iter=8, tr_handoff=False, log_cap=256)
+        cams, pts = h.get_params()
+        runs.append((log.tobytes(), cams.tobytes(), pts.tobytes()))
+    h.close()
+    assert runs[0] == runs[1] and len(runs[0][0]) > 0

@@ -15,7 +15,7 @@ none and an eighth of the points are seen once.  Dampings: mu = 1e-3 max diag an
   * C5  many_obs_problem (66 000 observations, 16 units per camera, blocks of several default-length segments):
         cost, gradient (16-block route), one assembly.
   * C6  psba_linearize(2, -2): S / 2 and e_a / -2 are the twin's at mu / 2; held diagonals are exactly 2 + mu.
-  * C7  two assemblies of the 16-block route are bit-identical beyond 64 cameras and with many segments.
+  * C7  two assemblies are bit-identical beyond 64 (93) cameras and with many segments, for both blocks.
 The module prints the worst ratio (found / allowed) per route, input and quantity; DESIGN 7d keeps the table."""
 import functools
 
@@ -31,7 +31,7 @@ from test_gpu_dense_solve import ETA_MAX
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not ar.LD_OK, reason="needs an 80-bit long double")]
 
 ROUTES = {"kd-all": (16, fr.ALL), "kd-bal": (16, BAL), "fk": (11, None)}
-SEG_LEN = 64   # the default segment length of the 16-block route's product lists
+SEG_LEN = 64   # the default segment length of the product lists
 WIDE = {16: {"wide-below": 64, "wide-above": 65}, 11: {"wide-below": 93, "wide-above": 94}}
 INPUTS = ["tiny", "P7", "P54", "wide-below", "wide-above"]
 WORST = {}  # (route, input, quantity) -> worst found / allowed
@@ -96,11 +96,10 @@ def handle(name, route):
         h.upload_problem(p)
         h.set_distortion(start_kc(p["nC"]))
         h.set_intrinsics_mask(free)
-        assert h.schur_path() == 5
     else:
         h.set_camera_model(psba_amd.CAMERA_FREE_K)
         h.upload_problem(p)
-    assert h.camera_block() == cnp
+    assert h.camera_block() == cnp and h.schur_path() == 5
     return h
 
 
@@ -282,16 +281,28 @@ def test_linearize_with_coefficients(route):
         h.close()
 
 
-@pytest.mark.parametrize("name", ["wide-above", "many"])
-def test_two_assemblies_are_bit_identical(name):
-    """C7: the 16-block route sums in an order the upload fixes (no floating-point atomics)."""
+def assembled_twice(name, route):
     bufs = []
     for _ in range(2):
-        h = handle(name, "kd-bal")
+        h = handle(name, route)
         try:
             h.linearize(1.0, 1.0)
             h.schur_assemble(1e-3 * h.max_diag())
             bufs.append(h.get_reduce_buffer().tobytes())
         finally:
             h.close()
+    return bufs
+
+
+@pytest.mark.parametrize("name", ["wide-above", "many"])
+def test_two_assemblies_are_bit_identical(name):
+    """C7: the 16-block route sums in an order the upload fixes (no floating-point atomics)."""
+    bufs = assembled_twice(name, "kd-bal")
+    assert bufs[0] == bufs[1]
+
+
+@pytest.mark.parametrize("name", ["wide-above", "many"])
+def test_two_assemblies_of_blocks_of_11_are_bit_identical(name):
+    """C7 for blocks of 11, which run the same kernels: 94 cameras, and blocks of several segments."""
+    bufs = assembled_twice(name, "fk")
     assert bufs[0] == bufs[1]

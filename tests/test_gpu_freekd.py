@@ -161,6 +161,69 @@ def test_two_runs_are_bit_identical():
     assert logs[0] == logs[1] and len(logs[0]) > 0
 
 
+def test_four_handles_of_three_camera_blocks_share_no_state():
+    """Handles of blocks 16, 11, 6 and 11 alive at once on 7camsvarK, the verbs of one damping try interleaved over
+    them: the two instantiations of kernels_free.hip and the six-parameter kernels keep no state outside their
+    handle.  The two 11-block handles agree bit for bit; the 16-block handle meets this module's tolerances against
+    the twin, the six-parameter one test_gpu_parity.py's against the oracle."""
+    import psba_amd
+    from oracle_lib import Oracle
+    p = prob("P7")
+    t, cost, N, g = twin_normal("P7", ALL)
+    o = Oracle(p)
+    lin = o.linearize()
+    hs = [handle(p, start_kc(p["nC"]), ALL)]
+    for model in (psba_amd.CAMERA_FREE_K, psba_amd.CAMERA_FIXED_K, psba_amd.CAMERA_FREE_K):
+        h = psba_amd.Psba(0)
+        h.set_camera_model(model)
+        h.upload_problem(p)
+        hs.append(h)
+    assert [h.camera_block() for h in hs] == [16, 11, 6, 11]
+    begun = [h.begin() for h in hs]
+    mus = [1e-3 * t.max_diag(N), 1e-3 * begun[1][1], 1e-3 * lin["maxdiag"], 1e-3 * begun[3][1]]
+    for h, mu in zip(hs, mus):
+        h.schur_assemble(mu)
+    reds = [h.get_reduce_buffer() for h in (hs[0], hs[1], hs[3])]
+    for h in hs:
+        h.schur_reduce()
+    for h in hs:
+        h.schur_solve()
+    scs = [h.backsub(mu) for h, mu in zip(hs, mus)]
+    dps = [h.get_dp() for h in hs]
+    for h in hs:
+        h.close()
+    assert all(sc.status == 0 for sc in scs)
+    # blocks of 11, twice
+    assert begun[1] == begun[3] and reds[1].tobytes() == reds[2].tobytes() and dps[1].tobytes() == dps[3].tobytes()
+    assert all(getattr(scs[1], f) == getattr(scs[3], f) for f, _ in scs[1]._fields_)
+    # blocks of 16 against the twin (one_try's measures)
+    nA, nT, mu = t.nA, t.nT, mus[0]
+    assert abs(begun[0][0] - cost) <= 1e-12 * cost and abs(begun[0][1] - t.max_diag(N)) <= 1e-11 * begun[0][1]
+    n32 = (nA + 31) // 32 * 32
+    M = reds[0].reshape(n32 + 1, n32)
+    S_want, ea_want = t.schur(N, g, mu)
+    eS, ee = scaled_errors(M[:nA, :nA], M[n32, :nA], S_want, ea_want, np.sqrt(np.diag(N)[:nA] + mu), np.sqrt(cost))
+    assert eS <= scaled_tol(p) and ee <= scaled_tol(p)
+    dp_want = np.linalg.solve(N + mu * np.eye(nT), g)
+    for sl in (slice(0, nA), slice(nA, nT)):
+        assert np.abs(dps[0][sl] - dp_want[sl]).max() <= 1e-6 * np.abs(dp_want[sl]).max()
+    new_cost = t.cost(t.cams + dp_want[:nA].reshape(-1, CNP), t.pts + dp_want[nA:].reshape(-1, 3))
+    assert abs(scs[0].new_cost - new_cost) <= 1e-7 * new_cost
+    assert abs(scs[0].dp_l2 - dp_want @ dp_want) <= 1e-6 * (dp_want @ dp_want)
+    assert abs(scs[0].gain_den - dp_want @ (mu * dp_want + g)) <= 1e-7 * abs(dp_want @ (mu * dp_want + g))
+    # blocks of 6 against the oracle (test_gpu_parity.py: dp 1e-9 of the largest entry, the try's scalars 1e-8)
+    mu = mus[2]
+    assert abs(begun[2][0] - lin["ex"] @ lin["ex"]) <= 1e-12 * begun[2][0]
+    assert abs(begun[2][1] - lin["maxdiag"]) <= 1e-12 * lin["maxdiag"]
+    _, dp6, _ = o.solve(lin, o.schur(lin, mu))
+    assert np.abs(dps[2] - dp6).max() <= 1e-9 * np.abs(dp6).max()
+    newp = np.r_[o.cams, o.pts] + dp6
+    ex_new = o.exQT(cams=newp[: o.nA], pts=newp[o.nA:])
+    for got, want in [(scs[2].dp_l2, dp6 @ dp6), (scs[2].gain_den, dp6 @ (mu * dp6 + lin["g"])),
+                      (scs[2].new_cost, ex_new @ ex_new), (scs[2].newp_l2, newp @ newp)]:
+        assert abs(got - want) <= 1e-8 * abs(want), (got, want)
+
+
 def test_against_the_eleven_block_route():
     """kc = 0 held, the five intrinsics free: the 11 x 11 sub-blocks are the FREE_K route's (twice the tolerance: the
     same again for that route's atomics)."""
