@@ -422,6 +422,16 @@ int psba_cholmod_lambda(psba_handle h, int reassemble, double *lambda, double *i
  * assembly and solve and psba_upload_problem invalidate it -- PSBA_E_STATE then, as before any psba_cholmod_lambda and
  * under PSBA_SOLVER_PCG (no factor exists: the estimate is a Gershgorin shift). */
 int psba_get_cholmod_factor(psba_handle h, double *L);
+/* ---- test hook: the per-observation blocks of the free-intrinsics linearization (PSBA_CAMERA_FREE_K /
+ * PSBA_CAMERA_FREE_KD), as the fused kernel itself stored them: W [n2Dprojs][cnp][3] row-major = coeff A^T B of
+ * observation a (cnp = psba_camera_block: 11 or 16; a masked intrinsic's row is zero), Be [n2Dprojs][8] = B (2 x 3
+ * row-major) | e (2).  Either pointer may be null.  A device-to-host copy, no kernel.  Valid after a psba_linearize
+ * (or psba_begin) at the current parameters until something overwrites the buffers or moves the parameters:
+ * psba_linearize_ahead (it reuses the B | e buffer), psba_accept of a proposal that was not linearized ahead,
+ * psba_set_params, psba_reset_params, psba_set_distortion, psba_set_intrinsics_mask, psba_set_intrinsics_groups,
+ * psba_upload_problem -- PSBA_E_STATE then, as before any linearization and for six-parameter camera blocks (whose
+ * blocks the sba_func.h mirror reads: psba_compute_jacobiQT, psba_compute_Wblks). */
+int psba_get_free_obs_blocks(psba_handle h, double *W, double *Be);
 
 typedef struct {
   int max_iter;     /* literal 50, shared with levmar() through itno (trust_region.cpp:112) */

@@ -137,6 +137,7 @@ SIGNATURES = [
     ("psba_set_step", C.c_int, [_h, _dp]),
     ("psba_cholmod_lambda", C.c_int, [_h, C.c_int, _dp, _dp]),
     ("psba_get_cholmod_factor", C.c_int, [_h, _dp]),
+    ("psba_get_free_obs_blocks", C.c_int, [_h, _dp, _dp]),
     ("psba_tr_default_options", None, [C.POINTER(TrOptions)]),
     ("psba_trust_region", C.c_int, [_h, C.POINTER(TrOptions), C.POINTER(TrResult), _dp]),
     ("psba_solve", C.c_int, [_h, C.c_int, C.c_int, C.POINTER(SolveResult)]),
@@ -818,6 +819,14 @@ class Psba:
     def cholmod_factor(self):
         """psba_get_cholmod_factor (test hook): L [nA, nA] of the last dense-mode cholmod_lambda."""
         return self._out(lib.psba_get_cholmod_factor, self.nA * self.nA)[1].reshape(self.nA, self.nA)
+
+    def free_obs_blocks(self):
+        """psba_get_free_obs_blocks (test hook): W [nO, cnp, 3], B [nO, 2, 3], e [nO, 2] of the last psba_linearize
+        with free intrinsics."""
+        W, Be = np.empty(3 * self.cnp * self.nO), np.empty(8 * self.nO)
+        self._ck(lib.psba_get_free_obs_blocks(self._h, _d(W), _d(Be)))
+        Be = Be.reshape(self.nO, 8)
+        return W.reshape(self.nO, self.cnp, 3), Be[:, :6].reshape(self.nO, 2, 3).copy(), Be[:, 6:].copy()
 
     def trust_region(self, max_iter=50, start_itno=0, verbose=False, log_cap=512, init_lambda=0.0):
         opts = TrOptions(max_iter, start_itno, int(verbose), log_cap, init_lambda)

@@ -16,11 +16,21 @@ namespace psba {
 
 #define PSBA_HD __host__ __device__ __forceinline__
 
+// Every function of the per-observation model pins how its a * b + c contract: within one expression, as written, and
+// never across statements (the compiler's default for device code fuses across statements wherever the inlined
+// context allows, so two kernels that inline the same text rounded it differently: k_jmul's A against the dumping
+// K1's on 54cams differed by 2.4e-12 |A| in an entry (v0 - y) / Pz that cancels, 2.7 times what the suites allow
+// between instantiations).  With the contraction pinned, every kernel that evaluates the model on the same inputs
+// gets the same bits: the blocks K3, k_cam_sums and k_jmul recompute are the ones K1 formed, and the robust weight
+// is the same everywhere (below).  First statement of the function body.
+#define PSBA_FP_PINNED _Pragma("clang fp contract(on)")
+
 struct Quat {
   double s, u0, u1, u2;
 };
 
 PSBA_HD Quat compose_quat(const double *q0, double v0, double v1, double v2, double &sl) {
+  PSBA_FP_PINNED;
   sl = sqrt(1.0 - v0 * v0 - v1 * v1 - v2 * v2);
   const double s0 = q0[0], a0 = q0[1], a1 = q0[2], a2 = q0[3];
   Quat q;
@@ -33,6 +43,7 @@ PSBA_HD Quat compose_quat(const double *q0, double v0, double v1, double v2, dou
 
 // R'(q), row-major
 PSBA_HD void quat_matrix(const Quat &q, double *R) {
+  PSBA_FP_PINNED;
   const double ss = q.s * q.s, x = q.u0, y = q.u1, z = q.u2;
   const double xx = x * x, yy = y * y, zz = z * z;
   R[0] = ss + xx - yy - zz;
@@ -50,6 +61,7 @@ PSBA_HD void quat_matrix(const Quat &q, double *R) {
 // residual only.  cam = (v0,v1,v2,t0,t1,t2)
 PSBA_HD void residual_obs(const double *K, const double *q0, const double *cam, const double *M,
                           double mx, double my, double &e0, double &e1) {
+  PSBA_FP_PINNED;
   double sl, R[9];
   const Quat q = compose_quat(q0, cam[0], cam[1], cam[2], sl);
   quat_matrix(q, R);
@@ -65,6 +77,7 @@ PSBA_HD void residual_obs(const double *K, const double *q0, const double *cam, 
 // xn: (optional) the normalised image coordinates (Px / Pz, Py / Pz): what d(x, y) / dK needs
 PSBA_HD void linearize_obs(const double *K, const double *q0, const double *cam, const double *M,
                            double mx, double my, double *e, double *A, double *B, double *xn = nullptr) {
+  PSBA_FP_PINNED;
   double sl, R[9];
   const Quat q = compose_quat(q0, cam[0], cam[1], cam[2], sl);
   quat_matrix(q, R);
@@ -139,6 +152,7 @@ PSBA_HD void linearize_obs(const double *K, const double *q0, const double *cam,
 constexpr int FK_CNP = 11;
 PSBA_HD void linearize_obs_freek(const double *p, const double *q0, const double *M, double mx, double my, double *e,
                                  double *A, double *B) {
+  PSBA_FP_PINNED;
   double A6[12], xn[2];
   linearize_obs(p, q0, p + 5, M, mx, my, e, A6, B, xn);
   A[0] = xn[0];
@@ -175,6 +189,7 @@ constexpr int LENS_WSTRIDE = 4;  // doubles per observation of the whitening fac
 
 // (xd, yd) and, when J is given, d(xd, yd) / d(x, y) row-major
 PSBA_HD void distort(const double *kc, double x, double y, double &xd, double &yd, double *J = nullptr) {
+  PSBA_FP_PINNED;
   const double r2 = x * x + y * y;
   const double radial = 1.0 + r2 * (kc[0] + r2 * (kc[1] + r2 * kc[4]));
   const double xy = x * y;
@@ -191,6 +206,7 @@ PSBA_HD void distort(const double *kc, double x, double y, double &xd, double &y
 
 PSBA_HD void residual_obs_dist(const double *K, const double *q0, const double *cam, const double *M, const double *kc,
                                double mx, double my, double &e0, double &e1) {
+  PSBA_FP_PINNED;
   double sl, R[9];
   const Quat q = compose_quat(q0, cam[0], cam[1], cam[2], sl);
   quat_matrix(q, R);
@@ -208,6 +224,7 @@ PSBA_HD void residual_obs_dist(const double *K, const double *q0, const double *
 // full 2 x 3 matrix (d10 != 0), so A[9] and the R[0..2] terms of B[3..5] are not the zeros of linearize_obs.
 PSBA_HD void linearize_obs_dist(const double *K, const double *q0, const double *cam, const double *M, const double *kc,
                                 double mx, double my, double *e, double *A, double *B) {
+  PSBA_FP_PINNED;
   double sl, R[9];
   const Quat q = compose_quat(q0, cam[0], cam[1], cam[2], sl);
   quat_matrix(q, R);
@@ -284,6 +301,7 @@ constexpr int KD_CNP = 16;
 constexpr unsigned KD_ALL_FREE = 0x3FFu;
 PSBA_HD void linearize_obs_freekd(const double *p, const double *q0, const double *M, double mx, double my, double *e,
                                   double *A, double *B, unsigned free_mask = KD_ALL_FREE) {
+  PSBA_FP_PINNED;
   double A6[12];
   linearize_obs_dist(p, q0, p + 10, M, p + 5, mx, my, e, A6, B);
   // the normalised point once more (three products: cheaper than widening linearize_obs_dist's interface)
@@ -331,6 +349,7 @@ PSBA_HD void linearize_obs_freekd(const double *p, const double *q0, const doubl
 
 // e <- L e, A <- L A, B <- L B with L = [l00 l01; 0 l11] (w = (l00, l01, l11))
 PSBA_HD void whiten2(const double *w, double &e0, double &e1) {
+  PSBA_FP_PINNED;
   const double t = w[0] * e0 + w[1] * e1;
   e1 = w[2] * e1;
   e0 = t;
@@ -373,6 +392,7 @@ inline RobustLoss make_robust_loss(int kind, double c) {
 // only where s <= c2 picks 1); soft-L1's rho is written as 2 s / (sqrt(1 + s / c2) + 1), the same value without the
 // cancellation of sqrt(1 + s / c2) - 1 at s << c2.
 PSBA_HD void robust_eval(const RobustLoss &rl, double s, double &rho, double &w) {
+  PSBA_FP_PINNED;
   switch (rl.kind) {
     case LOSS_HUBER: {
       const double r = sqrt(s);
@@ -401,6 +421,7 @@ PSBA_HD void robust_eval(const RobustLoss &rl, double s, double &rho, double &w)
 }
 // e <- w e, A <- w A, B <- w B with w of s = |e|^2 (e already whitened)
 PSBA_HD void robust_scale(const RobustLoss &rl, double *e, double *A, double *B) {
+  PSBA_FP_PINNED;
   double rho, w;
   robust_eval(rl, e[0] * e[0] + e[1] * e[1], rho, w);
   e[0] *= w;
@@ -502,6 +523,7 @@ PSBA_HD void lens_residual(const double *cc, const double *cam, const double *M,
 // bit, which also scales e <- w e (the residual the normal equations see) and stores s to *s_out when given
 template <int LM>
 PSBA_HD double lens_cost(const RobustLoss &rl, double &e0, double &e1, double *s_out = nullptr) {
+  PSBA_FP_PINNED;
   const double s = e0 * e0 + e1 * e1;
   if constexpr ((LM & LENS_ROBUST) != 0) {
     double rho, w;

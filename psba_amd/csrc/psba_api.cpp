@@ -231,6 +231,7 @@ static void lens_changed(psba_ctx *h) {
   h->ahead = false;
   h->lin_is_ahead = false;
   h->linearized = h->assembled = h->solved = false;
+  h->free_obs = false;
 }
 
 static int groups_split(psba_ctx *h, const char *who, const std::vector<int> &rep, const double *v, int stride, int ncols,
@@ -256,6 +257,7 @@ static int set_start_distortion(psba_ctx *h, const double *kc) {
   }
   h->ahead = h->lin_is_ahead = false;
   h->linearized = h->assembled = h->solved = h->backsubbed = false;
+  h->free_obs = false;
   return PSBA_OK;
 }
 
@@ -988,6 +990,7 @@ int psba_set_params(psba_handle h, const double *camsEx, const double *pts3D) {
   PSBA_HIP(h, hipStreamSynchronize(h->stream));
   h->linearized = h->assembled = h->solved = h->backsubbed = false;
   h->ahead = h->lin_is_ahead = h->backsub_pending = h->publish_deferred = h->publish_in_k1 = false;
+  h->free_obs = false;
   return PSBA_OK;
 }
 
@@ -1000,6 +1003,7 @@ int psba_reset_params(psba_handle h) {
                              hipMemcpyDeviceToDevice, h->stream));
   h->linearized = h->assembled = h->solved = h->backsubbed = false;
   h->ahead = h->lin_is_ahead = h->backsub_pending = h->publish_deferred = h->publish_in_k1 = false;
+  h->free_obs = false;
   return PSBA_OK;
 }
 
@@ -1051,6 +1055,7 @@ int psba_linearize(psba_handle h, double coeff, double coeff_g) {
     h->coeff = coeff;
     h->coeff_g = coeff_g;
     TRY(launch_linearize(h, false));
+    h->free_obs = h->cnp != 6;
   }
   h->lin_is_ahead = false;
   h->ahead = false;
@@ -1085,6 +1090,7 @@ int psba_begin(psba_handle h, double coeff, double coeff_g, double *cost, double
   h->coeff = coeff;
   h->coeff_g = coeff_g;
   TRY(launch_linearize(h, false));
+  h->free_obs = h->cnp != 6;
   h->linearized = true;
   h->assembled = h->solved = h->backsubbed = false;
   h->ahead = false;
@@ -1232,6 +1238,7 @@ int psba_linearize_ahead(psba_handle h) {
   NEED(h, h->backsub_pending || h->backsubbed, "psba_backsub_async / psba_backsub first");
   const bool carry = h->backsub_pending && h->publish_deferred;
   if (carry) h->pub_seq += 1.0;
+  h->free_obs = false;  // (free_Be is about to hold the blocks at the proposal, W those at the current parameters)
   TRY(launch_linearize(h, false, true, carry));
   if (carry) {
     h->publish_deferred = false;
@@ -1302,6 +1309,7 @@ int psba_accept(psba_handle h) {
   NEED(h, h->backsubbed, "psba_backsub first");
   h->cur = 1 - h->cur;
   h->linearized = h->assembled = h->solved = h->backsubbed = false;
+  h->free_obs = h->ahead && h->cnp != 6;  // W_alt and free_Be of the linearization queued ahead become the current pair
   if (h->ahead) {  // the linearization at the (now current) proposed parameters exists already
     std::swap(h->W, h->W_alt);
     std::swap(h->PV, h->PV_alt);
@@ -1598,6 +1606,18 @@ int psba_get_cholmod_factor(psba_handle h, double *L) {
                                hipMemcpyDeviceToHost, h->stream));
   PSBA_HIP(h, hipStreamSynchronize(h->stream));
   return PSBA_OK;
+}
+
+// test hook (psba_hip.h): W_a and B_a | e_a as k_free_linearize stored them
+int psba_get_free_obs_blocks(psba_handle h, double *W, double *Be) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp != 6, "free-intrinsics camera blocks only (six-parameter blocks: psba_compute_jacobiQT, psba_compute_Wblks)");
+  NEED(h, h->linearized && h->free_obs,
+       "psba_linearize first (psba_linearize_ahead, psba_accept and every verb that moves the parameters or the model "
+       "invalidate the blocks)");
+  TRY(d2h(h, W, h->W, sizeof(double) * 3 * (size_t)h->cnp * h->d.nO));
+  return d2h(h, Be, h->free_Be, sizeof(double) * 8 * (size_t)h->d.nO);
 }
 
 // ---- sba_func.h mirror ------------------------------------------------------------------

@@ -323,6 +323,9 @@ struct ProblemState {
   // ---- state ----
   bool uploaded = false, linearized = false, assembled = false, solved = false, backsubbed = false;
   bool backsub_pending = false;  // psba_backsub_async issued, psba_backsub_wait not yet
+  // free intrinsics: W and free_Be hold the blocks of one linearization at the current parameters
+  // (psba_get_free_obs_blocks); a linearization queued ahead writes W_alt but the same free_Be
+  bool free_obs = false;
   // the try's scalars travel to the host with the linearization queued ahead (its workgroup 0 copies
   // them and then writes a stamp the host polls) instead of through a kernel of their own between K3
   // and that linearization: publish_deferred = K3 queued, nothing published yet; publish_in_k1 = the
