@@ -165,6 +165,34 @@ int psba_intrinsics_mask(psba_handle h, unsigned char out10[10]);
 int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam);
 int psba_intrinsics_groups(psba_handle h, int *rep_of_cam, int *n_groups);
 
+/* ---- the damping rule of the free-intrinsics models (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD) --------
+ * A camera block with free intrinsics mixes scales: the diagonal of J^T J runs from about 1 (a focal length in
+ * pixels) to 1e7 (a rotation), and mu I with mu_0 = 1e-3 max diag freezes the small entries until mu has come down.
+ * PSBA_DAMPING_MARQUARDT damps with N + mu D instead, D_k = min(max(N_kk, dmin), dmax) (Marquardt's scaling, with the
+ * clamps production solvers use).  N_kk is the stored diagonal of the linearization: U_j[k][k] for cameras (scaled by
+ * coeff; the placeholder coeff of a coordinate held by psba_set_intrinsics_mask), the diagonal of V_i for points.
+ * dmin = 0 / dmax = 0 mean the defaults 1e-6 / 1e32; otherwise 0 < dmin <= dmax, both finite.  PSBA_E_INVALID for
+ * other clamps and for an unknown kind.
+ * What the fused verbs do with mu: in psba_schur_assemble(mu), psba_backsub(mu) and psba_backsub_async(mu) it
+ * multiplies D -- the point system is V_i + mu diag(D_i), the camera diagonal U_kk + mu D_k,
+ * gain_den = sum dp g + mu sum D dp^2, and psba_get_reduce_buffer returns that S.  psba_max_diag and psba_begin are
+ * unchanged.  With psba_set_intrinsics_groups mu D is added once, after the fold: D of a shared coordinate of a
+ * representative is the clamp of the sum of its members' U_kk in ascending camera order (the folded diagonal
+ * psba_max_diag takes its maximum over), D of a folded-away coordinate of a non-representative is clamp(coeff), as
+ * for a masked one, and the mu sum D dp^2 term counts a shared parameter once.  Mask, groups and damping compose in
+ * any order of calls.  psba_levmar under Marquardt starts from mu_0 = tau (see psba_lm_options.init_mu) and is
+ * otherwise the same loop.
+ * After psba_upload_problem (a new upload resets to PSBA_DAMPING_IDENTITY with the default clamps); PSBA_E_STATE
+ * before an upload, while a try is in flight and on six-parameter camera blocks (free-intrinsics models only: the
+ * fixed-K routes keep the reference's N + mu I); a refused call changes nothing; setting the rule discards a
+ * linearization queued ahead.  PSBA_DAMPING_IDENTITY is bit for bit the handle that never called this, also after a
+ * Marquardt run on the same handle.  No floating-point atomics: two runs stay bit-identical.  PARITY UNPINNED, like
+ * the models it belongs to. */
+#define PSBA_DAMPING_IDENTITY  0   /* N + mu I: the reference's rule, the default */
+#define PSBA_DAMPING_MARQUARDT 1   /* N + mu D, D_k = min(max(N_kk, dmin), dmax) */
+int psba_set_damping(psba_handle h, int kind, double dmin, double dmax);
+int psba_damping(psba_handle h, int *kind, double *dmin, double *dmax);
+
 /* ---- lens distortion and per-observation image covariances --------------------------
  * Model (the same in psba_amd/csrc/camera_model.h and DESIGN.md): P = R'(q) M + t, (x, y) = (Px, Py) / Pz,
  * r2 = x^2 + y^2, kc = (k1, k2, k3, k4, k5) in the Camera Calibration Toolbox order (the column order of the
@@ -361,7 +389,9 @@ typedef struct {
   int log_cap;      /* rows available in log (5 doubles each), 0 = none */
   int start_itno;   /* the reference shares itno between LM and TR (main.cpp:193-208) */
   double init_mu;   /* mu_0 = init_mu * max diag(U, V); 0 = the reference's PSBA_INIT_MU 1e-3 (psba.h:6,
-                       levmar.cpp:114-116), a compile-time constant there */
+                       levmar.cpp:114-116), a compile-time constant there.  Under PSBA_DAMPING_MARQUARDT
+                       (psba_set_damping) mu_0 = init_mu itself, 0 = 1e-3: D carries the scale, the largest diagonal
+                       entry does not enter; psba_lm_result.mu0 reports it */
   double stop_cost; /* the loop ends with PSBA_ITER_ERR_SMALL_ENOUGH once ||e||^2 <= stop_cost; 0 = the reference's
                        PSBA_STOP_THRESH 1e-12 (psba.h:7, levmar.cpp:247-248), an absolute figure in squared image
                        units that ends a noise-free problem before fp64 is used up; negative = no such test (the
@@ -432,6 +462,15 @@ int psba_get_cholmod_factor(psba_handle h, double *L);
  * psba_upload_problem -- PSBA_E_STATE then, as before any linearization and for six-parameter camera blocks (whose
  * blocks the sba_func.h mirror reads: psba_compute_jacobiQT, psba_compute_Wblks). */
 int psba_get_free_obs_blocks(psba_handle h, double *W, double *Be);
+/* ---- test hook: D[nT] = [cnp per camera ; 3 per point] of the current linearization under PSBA_DAMPING_MARQUARDT
+ * (psba_set_damping), as the kernel behind the linearization stored it.  A device-to-host copy, no kernel.  Valid
+ * after a psba_linearize or psba_begin under Marquardt -- and after the psba_accept of a proposal that was linearized
+ * ahead, whose D comes with it -- until the parameters or the model change: psba_accept of a proposal that was not
+ * linearized ahead, psba_set_params, psba_reset_params, psba_set_distortion, psba_set_intrinsics_mask,
+ * psba_set_intrinsics_groups, psba_set_damping, psba_upload_problem -- PSBA_E_STATE then, as under
+ * PSBA_DAMPING_IDENTITY and for six-parameter camera blocks.  (psba_linearize_ahead writes the second set: the
+ * diagonal of a rejected step's current parameters stays readable.) */
+int psba_get_damping_diag(psba_handle h, double *D);
 
 typedef struct {
   int max_iter;     /* literal 50, shared with levmar() through itno (trust_region.cpp:112) */

@@ -8,9 +8,11 @@ a handle raises if no GPU is present.
 from .capi import (Psba, PsbaError, Problem, lib, lib_path, read_problem, partition_points,  # noqa: F401
                    write_problem, convert_bal, read_problem_ex, convert_bal_kd,
                    LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY, LOSS_SOFT_L1,
-                   CAMERA_FIXED_K, CAMERA_FREE_K, CAMERA_FREE_KD, INTRINSICS_BAL)
+                   CAMERA_FIXED_K, CAMERA_FREE_K, CAMERA_FREE_KD, INTRINSICS_BAL,
+                   DAMPING_IDENTITY, DAMPING_MARQUARDT)
 
 __all__ = ["Psba", "PsbaError", "Problem", "lib", "lib_path", "read_problem", "partition_points",
            "write_problem", "convert_bal", "read_problem_ex", "convert_bal_kd",
            "LOSS_NONE", "LOSS_HUBER", "LOSS_CAUCHY", "LOSS_SOFT_L1",
-           "CAMERA_FIXED_K", "CAMERA_FREE_K", "CAMERA_FREE_KD", "INTRINSICS_BAL"]
+           "CAMERA_FIXED_K", "CAMERA_FREE_K", "CAMERA_FREE_KD", "INTRINSICS_BAL",
+           "DAMPING_IDENTITY", "DAMPING_MARQUARDT"]

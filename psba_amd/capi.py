@@ -19,6 +19,7 @@ PARAMS_CUR, PARAMS_NEW = 0, 1
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY, LOSS_SOFT_L1 = 0, 1, 2, 3
 CAMERA_FIXED_K, CAMERA_FREE_K, CAMERA_FREE_KD = 0, 1, 2
 INTRINSICS_BAL = (1, 0, 0, 0, 0, 1, 1, 0, 0, 0)  # the free intrinsics of Bundle Adjustment in the Large: f, k1, k2
+DAMPING_IDENTITY, DAMPING_MARQUARDT = 0, 1
 ITER_TURN_TO_LM, ITER_TURN_TO_TR, ITER_CONTINUE, ITER_ERR = 1, 2, 3, 4
 ITER_DP_NO_CHANGE, ITER_ERR_SMALL_ENOUGH, ITER_PASS = 5, 6, 7
 K_LINEARIZE, K_SCHUR, K_CHOLESKY, K_BACKSUB, K_RESIDUAL, K_ALLREDUCE, K_SCHUR_REDUCE = range(7)
@@ -182,6 +183,9 @@ SIGNATURES = [
     ("psba_intrinsics_mask", C.c_int, [_h, C.POINTER(C.c_ubyte)]),
     ("psba_set_intrinsics_groups", C.c_int, [_h, C.POINTER(C.c_int)]),
     ("psba_intrinsics_groups", C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("psba_set_damping", C.c_int, [_h, C.c_int, C.c_double, C.c_double]),
+    ("psba_damping", C.c_int, [_h, _ip, _dp, _dp]),
+    ("psba_get_damping_diag", C.c_int, [_h, _dp]),
     ("psba_blockprod_plan_create", C.c_void_p, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_int]),
     ("psba_blockprod_plan_info", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     ("psba_blockprod_plan_copy", C.c_int, [C.c_void_p, _ip, _ip, _ip]),
@@ -505,6 +509,23 @@ class Psba:
         if g.size != self.nC:
             raise PsbaError(-1, f"set_intrinsics_groups: {g.size} labels for {self.nC} cameras")
         self._ck(lib.psba_set_intrinsics_groups(self._h, g.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def set_damping(self, kind=DAMPING_IDENTITY, dmin=0.0, dmax=0.0):
+        """psba_set_damping: DAMPING_IDENTITY (N + mu I) or DAMPING_MARQUARDT (N + mu D, D = clamp(diag N, dmin, dmax));
+        0 for a clamp = its default (1e-6, 1e32).  Free-intrinsics camera models only."""
+        self._ck(lib.psba_set_damping(self._h, int(kind), float(dmin), float(dmax)))
+
+    def damping(self):
+        """psba_damping -> (kind, dmin, dmax)"""
+        k, lo, hi = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        self._ck(lib.psba_damping(self._h, C.byref(k), C.byref(lo), C.byref(hi)))
+        return k.value, lo.value, hi.value
+
+    def get_damping_diag(self):
+        """psba_get_damping_diag (test hook): D [nT] = [cnp per camera ; 3 per point] of the current linearization."""
+        D = np.empty(getattr(self, "nT", 0) or 1)  # (before an upload the library refuses, nothing is written)
+        self._ck(lib.psba_get_damping_diag(self._h, _d(D)))
+        return D
 
     def intrinsics_groups(self):
         """psba_intrinsics_groups -> (representative of each camera [nC], number of groups)"""

@@ -611,4 +611,16 @@ PSBA_HD void sym3_ldl_solve(const Sym3Ldl &f, double w0, double w1, double w2, d
   y0 = w0 * f.i0 - f.l10 * y1 - f.l20 * y2;
 }
 
+// Marquardt's scaling of the damping (psba_set_damping): D_k from the stored diagonal entry N_kk of the
+// linearization -- the one place the clamps are applied, for cameras, points, held and folded-away coordinates alike
+PSBA_HD double damp_diag(double nkk, double dmin, double dmax) { return fmin(fmax(nkk, dmin), dmax); }
+// V_i + mu diag(D_i) in place (v = sym6 packing), D_i formed from V_i's own diagonal in registers.  k_free_Y and
+// k_free_backsub_pts both come through here, with an explicit fma, so that the back-substitution solves against the
+// very bits Y was made with
+PSBA_HD void damp_point_block(double *v, double mu, double dmin, double dmax) {
+  v[0] = fma(mu, damp_diag(v[0], dmin, dmax), v[0]);
+  v[3] = fma(mu, damp_diag(v[3], dmin, dmax), v[3]);
+  v[5] = fma(mu, damp_diag(v[5], dmin, dmax), v[5]);
+}
+
 }  // namespace psba

@@ -249,13 +249,50 @@ __global__ __launch_bounds__(1024) void k_free_max_diag(const double *U, const d
   }
 }
 
+// the damping rule of a try (psba_set_damping).  D null: N + mu I, and the kernels below are what they were
+// -- the branch on D is uniform and its side loads nothing.  D set: N + mu D, D [nT] written by k_free_damp_diag for
+// the linearization the try reads; the point kernels form their three entries from PV in registers (damp_point_block)
+struct FreeDamp {
+  const double *D;
+  double dmin, dmax;
+};
+
+// one thread per parameter, behind k_free_finish_cams and k_free_point_sums: D_k = clamp(N_kk) of this linearization.
+// Cameras: U_j[k][k] (a held coordinate: its placeholder coeff).  With groups a shared coordinate of a representative
+// takes the sum over its members in ascending camera order (the folded diagonal of k_kd_max_diag_groups), a
+// folded-away one coeff, as a masked coordinate.  Points: the diagonal of V_i
+template <class T>
+__global__ __launch_bounds__(256) void k_free_damp_diag(const double *U, const double *PV, const int *rep, const int *gidx,
+                                                        const int *gptr, const int *gmem, unsigned mask, double coeff,
+                                                        int nA, int nT, double dmin, double dmax, double *D) {
+  constexpr int CNP = T::CNP;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nT) return;
+  double n;
+  if (t < nA) {
+    const int j = t / CNP, r = t % CNP;
+    n = U[(size_t)CNP * CNP * j + (CNP + 1) * r];
+    const int g = (rep && r < 10 && ((mask >> r) & 1u)) ? gidx[j] : -1;
+    if (g >= 0 && rep[j] == j) {
+      n = 0.0;
+      for (int q = gptr[g]; q < gptr[g + 1]; q++) n += U[(size_t)CNP * CNP * gmem[q] + (CNP + 1) * r];
+    } else if (g >= 0) {
+      n = coeff;
+    }
+  } else {
+    const int i = (t - nA) / 3, q = (t - nA) % 3;
+    n = PV[9 * (size_t)i + (q == 0 ? 0 : q == 1 ? 3 : 5)];
+  }
+  D[t] = damp_diag(n, dmin, dmax);
+}
+
 // per try, camera-major (one wave per unit): Y_a = W_a (V_i + mu I)^-1 stored once, and the unit's part of
 // sum_a Y_a g_b,i (the e_a term of camera j), reduced over the lanes by a shuffle tree.  Y by L D L^T and
 // substitution: the closed-form inverse loses the points seen once at a small mu
 template <class T>
 __global__ __launch_bounds__(64) void k_free_Y(const double *W, const double *PV, const int *iidx, const int *cam_obs,
-                                               const int4 *cam_units, double *Y, double *eapart, double mu, int *status,
-                                               int try_id) {
+                                               const int4 *cam_units, double *Y, double *eapart, double mu, FreeDamp dm,
+                                               int *status, int try_id) {
   constexpr int CNP = T::CNP;
   const int lane = threadIdx.x;
   const int4 u = cam_units[blockIdx.x];
@@ -268,9 +305,13 @@ __global__ __launch_bounds__(64) void k_free_Y(const double *W, const double *PV
     double v[6], vi[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) v[k] = pv[k];
-    v[0] += mu;
-    v[3] += mu;
-    v[5] += mu;
+    if (dm.D) {
+      damp_point_block(v, mu, dm.dmin, dm.dmax);
+    } else {
+      v[0] += mu;
+      v[3] += mu;
+      v[5] += mu;
+    }
     if (sym3_inverse(v, vi)) status[0] = try_id;  // (the singular flag as on the other routes; Y by substitution)
     const Sym3Ldl f = sym3_ldl(v);
     const double g0 = pv[6], g1 = pv[7], g2 = pv[8];
@@ -352,12 +393,12 @@ __global__ __launch_bounds__(256) void k_free_combine(const int4 *multi, const d
   S[(size_t)(CNP * m.x + e / CNP) * ld + CNP * m.y + e % CNP] = -s;
 }
 
-// S += blockdiag(U) + mu I on the lower block triangle, mirrored to the upper; e_a = g_a - the units' sums in unit
-// order; identity padding; the accumulators of the try's back-substitution zeroed, the try stamp set
+// S += blockdiag(U) + mu I (mu D with D set) on the lower block triangle, mirrored to the upper; e_a = g_a - the
+// units' sums in unit order; identity padding; the accumulators of the try's back-substitution zeroed, the try stamp set
 template <class T>
 __global__ __launch_bounds__(256) void k_free_finalize(double *S, double *ea, const double *U, const double *ga,
-                                                       const double *eapart, const int *cuptr, double mu, int nA, int n32,
-                                                       double *scal, int *status, int try_id) {
+                                                       const double *eapart, const int *cuptr, double mu, const double *D,
+                                                       int nA, int n32, double *scal, int *status, int try_id) {
   constexpr int CNP = T::CNP;
   if (blockIdx.x == 0 && threadIdx.x < 4 * SC_NPART) scal[SC_PART + threadIdx.x] = 0.0;
   if (blockIdx.x == 0 && threadIdx.x == 64) status[3] = try_id;
@@ -371,7 +412,7 @@ __global__ __launch_bounds__(256) void k_free_finalize(double *S, double *ea, co
       S[at] = S[(size_t)c * n32 + r];
     } else if (lb == kb) {
       double v = S[at] + U[(size_t)CNP * CNP * kb + CNP * (r - CNP * kb) + (c - CNP * lb)];
-      if (r == c) v += mu;
+      if (r == c) v += D ? mu * D[r] : mu;
       S[at] = v;
     }
   }
@@ -393,6 +434,7 @@ struct FreeBackArgs {
   double *dp, *newcams, *newpts, *scal, *red;
   const int *status;
   double mu;
+  FreeDamp dm;
   unsigned mask;
   int nA, nP;
 };
@@ -421,7 +463,8 @@ __global__ __launch_bounds__(256) void k_free_backsub_cams(FreeBackArgs p) {  //
     const double c = p.cams[t] + d;
     p.newcams[t] = c;
     v4[0] += d * d;
-    v4[1] += d * (p.mu * d + p.ga[t]);
+    const double mud = p.dm.D ? p.mu * p.dm.D[t] : p.mu;
+    v4[1] += d * (mud * d + p.ga[t]);
     v4[3] += c * c;
   }
   free_block_sums4(v4, sRed, p.red);
@@ -448,9 +491,17 @@ __global__ __launch_bounds__(256) void k_free_backsub_pts(FreeBackArgs p) {
     double v[6], d[3];
 #pragma unroll
     for (int k = 0; k < 6; k++) v[k] = pv[k];
-    v[0] += p.mu;
-    v[3] += p.mu;
-    v[5] += p.mu;
+    double mud[3] = {p.mu, p.mu, p.mu};
+    if (p.dm.D) {
+      mud[0] = p.mu * damp_diag(v[0], p.dm.dmin, p.dm.dmax);
+      mud[1] = p.mu * damp_diag(v[3], p.dm.dmin, p.dm.dmax);
+      mud[2] = p.mu * damp_diag(v[5], p.dm.dmin, p.dm.dmax);
+      damp_point_block(v, p.mu, p.dm.dmin, p.dm.dmax);
+    } else {
+      v[0] += p.mu;
+      v[3] += p.mu;
+      v[5] += p.mu;
+    }
     sym3_ldl_solve(sym3_ldl(v), e0, e1, e2, d[0], d[1], d[2]);
     double n3[3];
 #pragma unroll
@@ -459,7 +510,7 @@ __global__ __launch_bounds__(256) void k_free_backsub_pts(FreeBackArgs p) {
       p.dp[p.nA + 3 * (size_t)i + q] = d[q];
       p.newpts[3 * (size_t)i + q] = n3[q];
       v4[0] += d[q] * d[q];
-      v4[1] += d[q] * (p.mu * d[q] + pv[6 + q]);
+      v4[1] += d[q] * (mud[q] * d[q] + pv[6 + q]);
       v4[3] += n3[q] * n3[q];
     }
     for (int a = o0; a < o1; a++) {  // (newcams: written by k_free_backsub_cams, launched before this kernel)
@@ -557,18 +608,20 @@ __global__ __launch_bounds__(256) void k_kd_fold_cols(double *S, KdGroups G, int
 
 // behind the column pass: the folded-away coordinates cleared to what a masked coordinate is (zero row and column,
 // coeff + mu on the diagonal, e_a = 0), mu added once to the other diagonal entries, the upper triangle an exact
-// copy of the lower (the two passes sum a mirrored pair in different orders)
-__global__ __launch_bounds__(256) void k_kd_fold_finish(double *S, double *ea, KdGroups G, double coeff, double mu, int nA,
-                                                        int n32) {
+// copy of the lower (the two passes sum a mirrored pair in different orders).  D set: mu D_r in the place of mu (D of
+// a representative's shared coordinate is the clamp of the folded diagonal, that of a folded-away one clamp(coeff))
+__global__ __launch_bounds__(256) void k_kd_fold_finish(double *S, double *ea, KdGroups G, double coeff, double mu,
+                                                        const double *D, int nA, int n32) {
   const size_t n2 = (size_t)nA * nA;
   const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gsize = (size_t)gridDim.x * blockDim.x;
   for (size_t t = gtid; t < n2; t += gsize) {
     const int r = (int)(t / nA), c = (int)(t % nA);
     const size_t at = (size_t)r * n32 + c;
+    const double mud = (D && r == c) ? mu * D[r] : mu;
     if (kd_folded(G, r) || kd_folded(G, c))
-      S[at] = r == c ? coeff + mu : 0.0;
+      S[at] = r == c ? coeff + mud : 0.0;
     else if (r == c)
-      S[at] += mu;
+      S[at] += mud;
     else if (r < c)
       S[at] = S[(size_t)c * n32 + r];  // (below the diagonal a kept entry is not written by this kernel)
   }
@@ -627,8 +680,9 @@ __global__ __launch_bounds__(256) void k_kd_backsub_cams_groups(FreeBackArgs p, 
     const double c = p.cams[t] + d;
     p.newcams[t] = c;
     if (!copy) {
+      const double mud = p.dm.D ? p.mu * p.dm.D[t] : p.mu;
       v4[0] += d * d;
-      v4[1] += d * (p.mu * d + p.ga[t]);
+      v4[1] += d * (mud * d + p.ga[t]);
       v4[3] += c * c;
     } else {
       v4[1] += d * p.ga[t];
@@ -694,6 +748,11 @@ static int linearize_free(psba_ctx *h, bool ahead, bool publish) {
                      h->free_cuptr, d.nC, h->coeff, h->coeff_g, h->kd_mask, Uo, gao);
   hipLaunchKernelGGL(k_free_point_sums, dim3((unsigned)((d.nP + 255) / 256)), dim3(256), 0, h->stream, h->free_Be, h->ptr, d.nP,
                      h->coeff, h->coeff_g, PVo);
+  if (h->damp_kind == PSBA_DAMPING_MARQUARDT)  // D of this set, behind the two kernels whose sums it reads
+    hipLaunchKernelGGL(k_free_damp_diag<T>, dim3((unsigned)((d.nT + 255) / 256)), dim3(256), 0, h->stream, (const double *)Uo,
+                       (const double *)PVo, (const int *)h->kd_rep, (const int *)h->kd_gidx, (const int *)h->kd_gptr,
+                       (const int *)h->kd_gmem, h->kd_mask, h->coeff, d.nA, d.nT, h->damp_dmin, h->damp_dmax,
+                       (double *)(ahead ? h->damp_D_alt : h->damp_D));
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }
@@ -723,9 +782,19 @@ static int max_diag_free(psba_ctx *h) {
   return PSBA_OK;
 }
 
+// the rule of the tries on the current linearization
+static FreeDamp free_damp(psba_ctx *h) {
+  FreeDamp dm;
+  dm.D = h->damp_kind == PSBA_DAMPING_MARQUARDT ? (const double *)h->damp_D : nullptr;
+  dm.dmin = h->damp_dmin;
+  dm.dmax = h->damp_dmax;
+  return dm;
+}
+
 template <class T>
 static int schur_free(psba_ctx *h, double mu) {
   const Dims &d = h->d;
+  const FreeDamp dm = free_damp(h);
   h->try_id++;  // (the status words are generation stamps, as in launch_schur)
   h->diag_done = false;
   double *S = h->red, *ea = h->red + (size_t)h->n32 * h->n32;
@@ -733,7 +802,7 @@ static int schur_free(psba_ctx *h, double mu) {
   {
     ProfScope ps(h, PSBA_K_SCHUR);
     hipLaunchKernelGGL(k_free_Y<T>, dim3(h->nCamUnits), dim3(64), 0, h->stream, h->W, h->PV, h->iidx, h->cam_obs, h->cam_units,
-                       h->free_Y, h->free_eapart, mu, h->status, h->try_id);
+                       h->free_Y, h->free_eapart, mu, dm, h->status, h->try_id);
     hipLaunchKernelGGL(k_free_schur<T>, dim3((unsigned)((h->free_nsegs + 3) / 4)), dim3(256), 0, h->stream, h->free_Y, h->W,
                        h->free_prods, h->free_segs, h->free_blocks, h->free_nsegs, S, h->n32, h->free_tiles);
     if (h->free_nmulti)
@@ -748,10 +817,10 @@ static int schur_free(psba_ctx *h, double mu) {
                          h->free_cuptr, d.nA, h->n32, h->scal, h->status, h->try_id);
       hipLaunchKernelGGL(k_kd_fold_rows, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, h->stream, S, G, d.nA, h->n32);
       hipLaunchKernelGGL(k_kd_fold_cols, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, h->stream, S, G, d.nA, h->n32);
-      hipLaunchKernelGGL(k_kd_fold_finish, dim3(fgrid), dim3(256), 0, h->stream, S, ea, G, h->coeff, mu, d.nA, h->n32);
+      hipLaunchKernelGGL(k_kd_fold_finish, dim3(fgrid), dim3(256), 0, h->stream, S, ea, G, h->coeff, mu, dm.D, d.nA, h->n32);
     } else {
       hipLaunchKernelGGL(k_free_finalize<T>, dim3(fgrid), dim3(256), 0, h->stream, S, ea, h->U, h->ga, h->free_eapart,
-                         h->free_cuptr, mu, d.nA, h->n32, h->scal, h->status, h->try_id);
+                         h->free_cuptr, mu, dm.D, d.nA, h->n32, h->scal, h->status, h->try_id);
     }
   }
   h->packed_pending = false;
@@ -779,6 +848,7 @@ static int backsub_free(psba_ctx *h, double mu) {
   a.red = h->free_red;
   a.status = h->status;
   a.mu = mu;
+  a.dm = free_damp(h);
   a.mask = h->kd_mask;
   a.nA = d.nA;
   a.nP = d.nP;

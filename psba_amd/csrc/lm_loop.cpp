@@ -51,7 +51,9 @@ int psba_levmar(psba_handle h, const psba_lm_options *opts, psba_lm_result *res,
   for (; itno < opts->max_iter && flag == PSBA_ITER_CONTINUE; itno++) {  // :100
     LM_TRY(psba_linearize(h, 1.0, 1.0));                                  // :103-108
     if (first) {                                                          // :114-120
-      mu = tau * maxdiag0;
+      // Marquardt's scaling (psba_set_damping, free-intrinsics models): D carries the scale of every coordinate,
+      // so tau is the damping itself and not a fraction of the largest diagonal entry
+      mu = h->damp_kind == PSBA_DAMPING_MARQUARDT ? tau : tau * maxdiag0;
       res->mu0 = mu;
       first = false;
       p_L2 = 1e+3;

@@ -232,6 +232,7 @@ static void lens_changed(psba_ctx *h) {
   h->lin_is_ahead = false;
   h->linearized = h->assembled = h->solved = false;
   h->free_obs = false;
+  h->damp_ok = false;
 }
 
 static int groups_split(psba_ctx *h, const char *who, const std::vector<int> &rep, const double *v, int stride, int ncols,
@@ -258,6 +259,7 @@ static int set_start_distortion(psba_ctx *h, const double *kc) {
   h->ahead = h->lin_is_ahead = false;
   h->linearized = h->assembled = h->solved = h->backsubbed = false;
   h->free_obs = false;
+  h->damp_ok = false;
   return PSBA_OK;
 }
 
@@ -520,6 +522,54 @@ int psba_intrinsics_groups(psba_handle h, int *rep_of_cam, int *n_groups) {
 }
 
 static int d2h(psba_ctx *h, void *dst, const void *src, size_t bytes);
+
+// ---- the damping rule of the free-intrinsics route ----
+int psba_set_damping(psba_handle h, int kind, double dmin, double dmax) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp != 6, "psba_set_damping: free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD); "
+                       "six-parameter blocks keep the reference's N + mu I");
+  NEED(h, !h->backsub_pending, "psba_set_damping: a damping try is in flight (psba_backsub_wait first)");
+  if (kind != PSBA_DAMPING_IDENTITY && kind != PSBA_DAMPING_MARQUARDT)
+    return fail(h, PSBA_E_INVALID, "psba_set_damping: unknown kind %d", kind);
+  if (dmin == 0.0) dmin = 1e-6;
+  if (dmax == 0.0) dmax = 1e32;
+  if (!(std::isfinite(dmin) && std::isfinite(dmax) && dmin > 0.0 && dmin <= dmax))
+    return fail(h, PSBA_E_INVALID, "psba_set_damping: clamps (%g, %g): 0 < dmin <= dmax, both finite (0 = the default)", dmin,
+                dmax);
+  if (kind == PSBA_DAMPING_MARQUARDT && !h->damp_D) {  // both sets or none: a refused call changes nothing
+    DevBuf<double> D, D_alt;
+    TRY(D.alloc(h, (size_t)h->d.nT));
+    TRY(D_alt.alloc(h, (size_t)h->d.nT));
+    h->damp_D = std::move(D);
+    h->damp_D_alt = std::move(D_alt);
+  }
+  h->damp_kind = kind;
+  h->damp_dmin = dmin;
+  h->damp_dmax = dmax;
+  lens_changed(h);  // (a linearization queued ahead carries no D, or one of other clamps)
+  return PSBA_OK;
+}
+
+int psba_damping(psba_handle h, int *kind, double *dmin, double *dmax) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp != 6, "psba_damping: free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)");
+  if (kind) *kind = h->damp_kind;
+  if (dmin) *dmin = h->damp_dmin;
+  if (dmax) *dmax = h->damp_dmax;
+  return PSBA_OK;
+}
+
+// test hook (psba_hip.h): D as k_free_damp_diag stored it for the current linearization
+int psba_get_damping_diag(psba_handle h, double *D) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp != 6, "psba_get_damping_diag: free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)");
+  NEED(h, h->damp_kind == PSBA_DAMPING_MARQUARDT, "psba_set_damping(PSBA_DAMPING_MARQUARDT) first");
+  NEED(h, h->damp_ok, "psba_linearize first (every verb that moves the parameters or the model invalidates the diagonal)");
+  return d2h(h, D, h->damp_D, sizeof(double) * (size_t)h->d.nT);
+}
 
 int psba_obs_sq_residuals(psba_handle h, int which, double *s) {
   CHECK_H(h);
@@ -991,6 +1041,7 @@ int psba_set_params(psba_handle h, const double *camsEx, const double *pts3D) {
   h->linearized = h->assembled = h->solved = h->backsubbed = false;
   h->ahead = h->lin_is_ahead = h->backsub_pending = h->publish_deferred = h->publish_in_k1 = false;
   h->free_obs = false;
+  h->damp_ok = false;
   return PSBA_OK;
 }
 
@@ -1004,6 +1055,7 @@ int psba_reset_params(psba_handle h) {
   h->linearized = h->assembled = h->solved = h->backsubbed = false;
   h->ahead = h->lin_is_ahead = h->backsub_pending = h->publish_deferred = h->publish_in_k1 = false;
   h->free_obs = false;
+  h->damp_ok = false;
   return PSBA_OK;
 }
 
@@ -1056,6 +1108,7 @@ int psba_linearize(psba_handle h, double coeff, double coeff_g) {
     h->coeff_g = coeff_g;
     TRY(launch_linearize(h, false));
     h->free_obs = h->cnp != 6;
+    h->damp_ok = h->damp_kind == PSBA_DAMPING_MARQUARDT;
   }
   h->lin_is_ahead = false;
   h->ahead = false;
@@ -1091,6 +1144,7 @@ int psba_begin(psba_handle h, double coeff, double coeff_g, double *cost, double
   h->coeff_g = coeff_g;
   TRY(launch_linearize(h, false));
   h->free_obs = h->cnp != 6;
+  h->damp_ok = h->damp_kind == PSBA_DAMPING_MARQUARDT;
   h->linearized = true;
   h->assembled = h->solved = h->backsubbed = false;
   h->ahead = false;
@@ -1315,7 +1369,9 @@ int psba_accept(psba_handle h) {
     std::swap(h->PV, h->PV_alt);
     std::swap(h->U, h->U_alt);
     std::swap(h->ga, h->ga_alt);
+    std::swap(h->damp_D, h->damp_D_alt);
   }
+  h->damp_ok = h->ahead && h->damp_kind == PSBA_DAMPING_MARQUARDT;
   // only a linearization that was computed ahead for THIS proposal spares the next psba_linearize
   // (an earlier accept's flag must not survive: psba_set_step -> psba_accept -> psba_linearize)
   h->lin_is_ahead = h->ahead;

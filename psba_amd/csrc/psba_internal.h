@@ -307,6 +307,13 @@ struct ProblemState {
   psba::DevBuf<int> kd_gptr;       // [kd_nmg + 1] CSR over kd_gmem of the groups with several members
   psba::DevBuf<int> kd_gmem;       // their members in ascending camera order (the first is the representative)
   int kd_nmg = 0;
+  // the damping rule of this route (psba_set_damping): N + mu I, or N + mu D with Marquardt's
+  // D_k = min(max(N_kk, dmin), dmax).  damp_D [nT] belongs to the current linearization, damp_D_alt to the one queued
+  // ahead (psba_accept swaps them with the rest); both are allocated by the first switch to Marquardt
+  int damp_kind = PSBA_DAMPING_IDENTITY;
+  double damp_dmin = 1e-6, damp_dmax = 1e32;
+  psba::DevBuf<double> damp_D, damp_D_alt;
+  bool damp_ok = false;           // damp_D is that of the current parameters and model (psba_get_damping_diag)
   psba::DevBuf<double> dp;        // [nT] dpa | dpb                     (dp_buffer)
   psba::DevBuf<double> trv[2];    // [nT] each: vectors of the trust-region operators (allocated on first use)
   psba::DevBuf<double> jmul_out;  // [2 nO] J x of psba_compute_Jmultiply (allocated on first use)
