@@ -416,19 +416,27 @@ def rho_ext(s, kind=0, c=1.0):
     return r, mag
 
 
-def try_scalars(dp, newp, mu, g, nA, s_new, e_slack=None, envg=None, loss=(0, 1.0), r=1):
+def try_scalars(dp, newp, mu, g, nA, s_new, e_slack=None, envg=None, loss=(0, 1.0), r=1, extra=0):
     """The four sums of one damping try: {name: (exact, bound)}.  dp, newp: the GPU's step and proposal; g (double or
     exact) with its envelope; s_new [nO] the squared whitened residuals at the proposal as k_residual forms them
-    (e_slack [nO, 2]: K3 recomputes them); loss (kind, c); r the partial sets merged on the host."""
+    (e_slack [nO, 2]: K3 recomputes them); loss (kind, c); r the partial sets merged on the host.  mu: a scalar, or
+    the weights mu D [nT] of a diagonal damping in extended precision (free_ref), formed by the kernel with `extra`
+    roundings more per term of gain_den."""
     dpL = ld(dp)
     ad = np.abs(np.asarray(dp, dtype=np.float64))
     gx = ld(g)
     nT = ad.size
     out = {"dp_l2": (np.sum(dpL * dpL), float(gamma(nT + 1 + r) * np.sum(ad * ad)))}
-    den_env = float(gamma(2 * nA + (nT - nA) + 3 + r) * np.sum(ad * (abs(mu) * ad + np.abs(gx.astype(np.float64)))))
+    if np.ndim(mu) == 0:   # (the scalar rule: the expressions are what they always were)
+        den_env = float(gamma(2 * nA + (nT - nA) + 3 + r) * np.sum(ad * (abs(mu) * ad + np.abs(gx.astype(np.float64)))))
+        mu = LD(mu)
+    else:
+        mu = ld(mu)
+        den_env = float(gamma(2 * nA + (nT - nA) + 3 + extra + r)
+                        * np.sum(ad * (np.abs(mu.astype(np.float64)) * ad + np.abs(gx.astype(np.float64)))))
     if envg is not None:
         den_env += float(np.sum(ad * np.asarray(envg, dtype=np.float64)))
-    out["gain_den"] = (np.sum(dpL * (LD(mu) * dpL + gx)), den_env)
+    out["gain_den"] = (np.sum(dpL * (mu * dpL + gx)), den_env)
     npL = ld(newp)
     out["newp_l2"] = (np.sum(npL * npL), float(gamma(nT + 1 + r) * np.sum(np.abs(np.asarray(newp, dtype=np.float64)) ** 2)))
     sd = np.asarray(s_new, dtype=np.float64).reshape(-1)

@@ -45,7 +45,28 @@ applies (DESIGN 7d records the worst ratios found).
 The four try scalars (C4) are assembly_ref.try_scalars' (it takes nA, not a block size): dp_l2, gain_den and newp_l2
 from the device's own dp and proposal summed in extended precision, gain_den with env(g) above; new_cost against the
 twin's residuals at the device's proposal, per observation gamma(2) s (+ gamma(8) s for the loss slot, the identity
-here) and the residual slack rule."""
+here) and the residual slack rule.
+
+Marquardt's damping (psba_set_damping): every judge takes a Rule (kind, dmin, dmax; identity is the default
+and leaves each result bit for bit what it was).  N + mu D in the place of N + mu I, D_k = min(max(N_kk, dmin), dmax).
+  * The reference D (damp_ref) is the clamp of the diagonal of the sums above in extended precision -- the placeholder
+    coeff at a held coordinate -- rounded once.  The kernels clamp THEIR stored diagonal entry, a K1 sum of squares:
+    it differs from the exact one by env(N_kk) = |c| gamma(n + 2) sum J_k^2 + the Jacobian slack (2 |J_k| s + s^2
+    summed), and the clamp is 1-Lipschitz, so |D_device - D_ref| <= env(N_kk) + u D_ref (the reference's own
+    rounding); 0 at a held coordinate.  envD is that envelope, and mu envD goes wherever mu D enters below.
+  * C1: schur_blocks restates TwinKD.schur_blocks on the route's own columns with U_kk + mu D_k and
+    V_i + mu diag(D_i); the scaled measure keeps its form with d_r = sqrt(N_rr + mu D_r) and tol = scaled_tol(p).
+  * C3: V* = V_i + mu diag(D_i).  camera_model.h's damp_point_block forms each diagonal entry as
+    fma(mu, clamp(v_rr), v_rr): ONE rounding per diagonal entry (the clamp is exact), the count the identity rule has
+    for its add, so the diagonal of env(V*) is u |V*_rr| + mu envD_r + env(V)_rr.  k_free_Y and k_free_backsub_pts
+    both come through that function with the same stored V_i, so the solve is against the V* Y was made with and the
+    L D L^T term is unchanged.
+  * C4: gain_den = sum dp g + sum (mu D) dp^2 with the DEVICE's D (psba_get_damping_diag; D itself is judged on its
+    own, check_damp_diag) as weights.  kernels_free.hip forms mud = mu * D[t] (k_free_backsub_cams,
+    k_kd_backsub_cams_groups) or mu * clamp(v_rr) (k_free_backsub_pts) and then d * (mud * d + g): one multiply more
+    than under mu I, so the count of roundings before the sum goes from three to four (try_scalars' `extra`)."""
+import collections
+
 import numpy as np
 
 import assembly_ref as ar
@@ -58,6 +79,32 @@ K_ONLY = (1, 1, 1, 1, 1, 0, 0, 0, 0, 0)
 SEL11 = np.r_[0:5, 10:16]
 GROUPS = {16: (slice(0, 5), slice(5, 10), slice(10, 13), slice(13, 16)), 11: (slice(0, 5), slice(5, 8), slice(8, 11))}
 LDL_K = 16
+IDENTITY, MARQUARDT = 0, 1   # PSBA_DAMPING_IDENTITY, PSBA_DAMPING_MARQUARDT
+DMIN, DMAX = 1e-6, 1e32      # the defaults of psba_set_damping
+
+
+class Rule(collections.namedtuple("Rule", "kind dmin dmax")):
+    """the damping rule of a try: N + mu I (identity, the default) or N + mu D, D = clamp(diag N, dmin, dmax)"""
+    __slots__ = ()
+
+    def __new__(cls, kind=IDENTITY, dmin=DMIN, dmax=DMAX):
+        return super().__new__(cls, int(kind), float(dmin), float(dmax))
+
+    @property
+    def marquardt(self):
+        return self.kind == MARQUARDT
+
+    def clamp(self, x):
+        return np.minimum(np.maximum(x, self.dmin), self.dmax)
+
+    def halved(self):
+        return Rule(self.kind, self.dmin / 2.0, self.dmax / 2.0)
+
+    def __str__(self):
+        return "identity" if not self.marquardt else f"marquardt({self.dmin:g}, {self.dmax:g})"
+
+
+NO_RULE = Rule()
 
 
 class Route:
@@ -149,18 +196,146 @@ def sums(rt, coeff=1.0, coeff_g=1.0):
     diagU = coeff * diagU.reshape(-1)
     diagU[rt.held] = coeff
     diagV, _ = ar._segsum((B * B).sum(axis=1), i, nP)
+    # the same diagonal in extended precision with its K1 envelope (what damp_ref clamps)
+    dUx, _ = ar._segsum((AL * AL).sum(axis=1), j, nC)
+    dUa, _ = ar._segsum((aA * aA).sum(axis=1), j, nC)
+    dUs, _ = ar._segsum((sA * (2 * aA + sA)).sum(axis=1), j, nC)
+    diagUx = LD(coeff) * dUx.reshape(-1)
+    envdU = c * (ar.gamma(n_j + 2)[:, None] * dUa + dUs).reshape(-1)
+    diagUx[rt.held] = LD(coeff)
+    envdU[rt.held] = 0.0
+    k3 = np.arange(3)
     return dict(W=W, envW=envW, V=LD(coeff) * Vx, envV=envV, g=g, envg=envg, n_i=n_i, n_j=n_j, diagU=diagU,
-                diagV=coeff * diagV.reshape(-1), cost=float(np.sum(eL * eL)), A=A, B=B, e=e)
+                diagV=coeff * diagV.reshape(-1), cost=float(np.sum(eL * eL)), A=A, B=B, e=e, diagUx=diagUx, envdU=envdU,
+                diagVx=(LD(coeff) * Vx)[:, k3, k3].reshape(-1), envdV=envV[:, k3, k3].reshape(-1), coeff=float(coeff))
 
 
-def dpb_residual(rt, sm, dp, mu):
+def damp_ref(rt, sm, rule=NO_RULE):
+    """(D [nT], envD [nT]) of the module docstring: the clamp of the extended-precision diagonal rounded once, and the
+    envelope |D_device - D| must stay inside.  Identity: (ones, zeros), so that mu D is mu exactly."""
+    if not rule.marquardt:
+        return np.ones(rt.nT), np.zeros(rt.nT)
+    D = rule.clamp(np.concatenate([sm["diagUx"], sm["diagVx"]])).astype(np.float64)
+    env = np.concatenate([sm["envdU"], sm["envdV"]])
+    free = np.ones(rt.nT, dtype=bool)
+    free[rt.held] = False
+    return D, np.where(free, env + ar.U * D, 0.0)
+
+
+def check_damp_diag(D, sm_diag, envN, rule, held, coeff=1.0):
+    """The device's D [n] against the clamp of the extended-precision diagonal sm_diag [n] (envelope envN [n], held:
+    indices whose entry is the placeholder coeff).  Returns the worst |D - D_ref| / (envN + u D_ref) over the entries
+    that have an envelope; asserts the exact parts: the clamp itself where the reference lies beyond it by more than
+    its envelope, clamp(coeff) at held coordinates.  Also returns the counts (at dmin, at dmax) of such entries."""
+    D = np.asarray(D, dtype=np.float64)
+    want = rule.clamp(sm_diag).astype(np.float64)
+    x = sm_diag.astype(np.float64)
+    low, high = x + envN < rule.dmin * (1.0 - ar.U), x - envN > rule.dmax * (1.0 + ar.U)
+    assert np.all(D[low] == rule.dmin), "an entry below dmin by more than its envelope is not dmin itself"
+    assert np.all(D[high] == rule.dmax), "an entry above dmax by more than its envelope is not dmax itself"
+    assert np.all(D[held] == min(max(coeff, rule.dmin), rule.dmax)), "D of a held coordinate is not clamp(coeff)"
+    assert np.all((D >= rule.dmin) & (D <= rule.dmax))
+    bound = envN + ar.U * want
+    bound[held] = 0.0
+    ratio, k = ar.excess(D, ar.ld(want), bound)
+    return ratio, k, int(low.sum()), int(high.sum())
+
+
+def schur_blocks(rt, mu, D, camera=True, dtype=np.longdouble):
+    """TwinKD.schur_blocks restated on the route's own columns for N + mu diag(D): S [nA, nA] and e_a with every sum in
+    `dtype` (80-bit), U_kk + mu D_k (camera=False: the camera diagonal is left undamped, for the fold of shared_ref)
+    and V_i + mu diag(D_i); the placeholder 1 at held coordinates."""
+    e, A, B, _ = rt.blocks()
+    e, A, B = e.astype(dtype), A.astype(dtype), B.astype(dtype)
+    nC, nP, cnp, nA = rt.nC, rt.nP, rt.cnp, rt.nA
+    D = np.asarray(D, dtype=np.float64).astype(dtype)
+    mu = dtype(mu)
+    U = np.zeros((nC, cnp, cnp), dtype)
+    ga = np.zeros((nC, cnp), dtype)
+    np.add.at(U, rt.j, np.einsum("nri,nrk->nik", A, A))
+    np.add.at(ga, rt.j, np.einsum("nri,nr->ni", A, e))
+    V = np.zeros((nP, 3, 3), dtype)
+    gb = np.zeros((nP, 3), dtype)
+    np.add.at(V, rt.i, np.einsum("nri,nrk->nik", B, B))
+    np.add.at(gb, rt.i, np.einsum("nri,nr->ni", B, e))
+    W = np.einsum("nri,nrk->nik", A, B)
+    S = np.zeros((nA, nA), dtype)
+    for j in range(nC):
+        S[cnp * j:cnp * j + cnp, cnp * j:cnp * j + cnp] = U[j]
+    S[rt.held, rt.held] = 1
+    if camera:
+        S[np.arange(nA), np.arange(nA)] += mu * D[:nA]
+    ea = ga.reshape(-1).copy()
+    order = np.argsort(rt.i, kind="stable")
+    ptr = np.searchsorted(rt.i[order], np.arange(nP + 1))
+    for i in range(nP):
+        obs = order[ptr[i]:ptr[i + 1]]
+        if obs.size == 0:
+            continue
+        v = V[i] + np.diag(mu * D[nA + 3 * i:nA + 3 * i + 3])
+        l10, l20 = v[0, 1] / v[0, 0], v[0, 2] / v[0, 0]
+        d1 = v[1, 1] - l10 * v[0, 1]
+        l21 = (v[1, 2] - l20 * v[0, 1]) / d1
+        d2 = v[2, 2] - l20 * v[0, 2] - l21 * l21 * d1
+        Wi = W[obs].reshape(-1, 3)
+        z1 = Wi[:, 1] - l10 * Wi[:, 0]
+        z2 = Wi[:, 2] - l20 * Wi[:, 0] - l21 * z1
+        y2 = z2 / d2
+        y1 = z1 / d1 - l21 * y2
+        Yi = np.stack([Wi[:, 0] / v[0, 0] - l10 * y1 - l20 * y2, y1, y2], 1)
+        rows = (cnp * rt.j[obs][:, None] + np.arange(cnp)[None, :]).reshape(-1)
+        S[np.ix_(rows, rows)] -= Yi @ Wi.T
+        ea[rows] -= Yi @ gb[i]
+    return S, ea
+
+
+def schur_ref(rt, sm, mu, rule=NO_RULE):
+    """S and e_a of the route in 80-bit, rounded once to double (identity: TwinKD.schur_blocks, as it always was)"""
+    if not rule.marquardt:
+        S, ea = rt.pick(*rt.twin.schur_blocks(mu))
+    else:
+        S, ea = schur_blocks(rt, mu, damp_ref(rt, sm, rule)[0])
+    return S.astype(np.float64), ea.astype(np.float64)
+
+
+def scale_diag(rt, sm, mu, rule=NO_RULE):
+    """d [nA] of the scaled measure: sqrt(N_rr + mu D_r) (identity: sqrt(N_rr + mu))"""
+    return np.sqrt(sm["diagU"] + mu * damp_ref(rt, sm, rule)[0][:rt.nA])
+
+
+def check_exact_parts(rt, S, ea, mu, rule=NO_RULE, coeff=1.0):
+    """C1's exact checks: a held coordinate has a zero row, e_a = 0 and coeff + mu clamp(coeff) on the diagonal; the
+    block of a camera without observations is fl(mu dmin) on its free coordinates (mu under the identity rule), that
+    placeholder on held ones, zero elsewhere, and its off-diagonal blocks and e_a are zero."""
+    cnp, nC, held = rt.cnp, rt.nC, rt.held
+    dh = mu * float(rule.clamp(coeff)) if rule.marquardt else mu
+    off = S[held].copy()
+    off[np.arange(held.size), held] = 0.0
+    assert np.all(off == 0.0) and np.all(ea[held] == 0.0), "a held row is not clear"
+    assert np.all(S[held, held] == coeff + dh), "the diagonal of a held coordinate"
+    empty = np.flatnonzero(np.bincount(rt.j, minlength=nC) == 0)
+    for j in empty:
+        rows = np.arange(cnp * j, cnp * j + cnp)
+        want = (mu * rule.dmin if rule.marquardt else mu) * np.eye(cnp)
+        hj = held[(held >= rows[0]) & (held <= rows[-1])] - rows[0]
+        want[hj, hj] = coeff + dh
+        assert np.array_equal(S[np.ix_(rows, rows)], want), f"the block of camera {j}, which has no observation"
+        assert np.all(np.delete(S[rows], rows, axis=1) == 0.0) and np.all(ea[rows] == 0.0)
+    return empty
+
+
+def dpb_residual(rt, sm, dp, mu, rule=NO_RULE):
     """(r [nB], bound [nB]) of the module docstring from the step dp [nT] (cameras then points) being judged"""
     cnp, nA = rt.cnp, rt.nA
     dpa = np.asarray(dp[:nA], dtype=np.float64).reshape(-1, cnp)
     dpb = np.asarray(dp[nA:], dtype=np.float64).reshape(-1, 3)
     Vs = sm["V"].copy()
     k = np.arange(3)
-    Vs[:, k, k] += LD(mu)
+    if rule.marquardt:
+        D, envD = damp_ref(rt, sm, rule)
+        Vs[:, k, k] += LD(mu) * ar.ld(D[nA:].reshape(-1, 3))
+    else:
+        Vs[:, k, k] += LD(mu)
     dL, ad = ar.ld(dpa)[rt.j], np.abs(dpa)[rt.j]
     t, n_i = ar._segsum(np.einsum("akc,ak->ac", sm["W"], dL), rt.i, rt.nP)
     gb = sm["g"][nA:].reshape(-1, 3)
@@ -172,6 +347,8 @@ def dpb_residual(rt, sm, dp, mu):
     dg = np.sqrt(Vd[:, k, k])
     envV = sm["envV"].copy()
     envV[:, k, k] += ar.U * Vd[:, k, k]
+    if rule.marquardt:
+        envV[:, k, k] += abs(mu) * envD[nA:].reshape(-1, 3)
     ab = np.abs(dpb)
     bound = (ar.gamma(LDL_K) * dg * (dg * ab).sum(axis=1)[:, None] + np.einsum("irc,ic->ir", envV, ab)
              + sm["envg"][nA:].reshape(-1, 3) + ar.gamma(cnp * n_i + 2)[:, None] * (np.abs(gb.astype(np.float64)) + wd)
@@ -179,12 +356,16 @@ def dpb_residual(rt, sm, dp, mu):
     return r.reshape(-1), bound.reshape(-1)
 
 
-def scalars(rt, sm, dp, newcams, newpts, mu):
-    """assembly_ref.try_scalars for this route: {name: (exact, bound)} from the step and proposal being judged"""
+def scalars(rt, sm, dp, newcams, newpts, mu, D=None):
+    """assembly_ref.try_scalars for this route: {name: (exact, bound)} from the step and proposal being judged.
+    D [nT]: the weights of Marquardt's rule, gain_den = sum dp g + sum (mu D) dp^2 (the device's own D)"""
     e_new, proj = rt.residuals(newcams, newpts)
     newp = np.concatenate([np.asarray(newcams).reshape(-1), np.asarray(newpts).reshape(-1)])
-    return ar.try_scalars(dp, newp, mu, sm["g"], rt.nA, (e_new * e_new).sum(axis=1),
-                          e_slack=ar.residual_slack(rt.twin.t.m, proj), envg=sm["envg"])
+    if D is None:
+        return ar.try_scalars(dp, newp, mu, sm["g"], rt.nA, (e_new * e_new).sum(axis=1),
+                              e_slack=ar.residual_slack(rt.twin.t.m, proj), envg=sm["envg"])
+    return ar.try_scalars(dp, newp, LD(mu) * ar.ld(D), sm["g"], rt.nA, (e_new * e_new).sum(axis=1),
+                          e_slack=ar.residual_slack(rt.twin.t.m, proj), envg=sm["envg"], extra=1)
 
 
 def solve_judge(S, ea, dpa):
@@ -231,8 +412,23 @@ def closed_form_solve(v, w):
     return w @ X
 
 
-def plain_schur(rt, mu, point_solve=ldl_solve):
+def plain_damp_diag(rt, U, V, rule, fault=None):
+    """k_free_damp_diag in fp64 numpy: D [nT] from the stored diagonals of U [nC, cnp, cnp] (placeholder 1 at held
+    coordinates) and V [nP, 3, 3].  Faults for test_free_entrywise_ref.py: "no-low-clamp" (D = min(N_kk, dmax)),
+    "cam-mod-64" (camera j reads the entries of camera j mod 64)."""
+    k, k3 = np.arange(rt.cnp), np.arange(3)
+    n = np.concatenate([U[:, k, k].reshape(-1), V[:, k3, k3].reshape(-1)])
+    n[rt.held] = 1.0
+    D = np.minimum(n, rule.dmax) if fault == "no-low-clamp" else rule.clamp(n)
+    if fault == "cam-mod-64":
+        D[:rt.nA] = D[:rt.nA].reshape(-1, rt.cnp)[np.arange(rt.nC) % 64].reshape(-1)
+    return D
+
+
+def plain_schur(rt, mu, point_solve=ldl_solve, rule=NO_RULE, fault=None):
     """S [nA, nA], e_a, and the pieces (V*, W, g) in fp64 from the twin's blocks, Y = W V*^-1 by `point_solve`"""
+    if rule.marquardt:
+        return plain_schur_damped(rt, mu, rule, fault)
     e, A, B, _ = rt.blocks()
     nC, nP, cnp, nA = rt.nC, rt.nP, rt.cnp, rt.nA
     U = np.zeros((nC, cnp, cnp))
@@ -264,9 +460,53 @@ def plain_schur(rt, mu, point_solve=ldl_solve):
     return S, ea, dict(Vs=Vs, W=W, g=np.concatenate([ga.reshape(-1), gb.reshape(-1)]))
 
 
-def plain_try(rt, mu):
+def plain_schur_damped(rt, mu, rule, fault=None, camera=True):
+    """plain_schur under Marquardt's rule: U_kk + mu D_k (camera=False: left undamped, for shared_ref's fold),
+    V_i + mu diag(D_i), D by plain_damp_diag; pieces as plain_schur's, D and the stored diagonal dU of U (placeholder
+    1 at held coordinates).  numpy rounds the product mu D_r and the sum where damp_point_block has one fma."""
+    e, A, B, _ = rt.blocks()
+    nC, nP, cnp, nA = rt.nC, rt.nP, rt.cnp, rt.nA
+    U = np.zeros((nC, cnp, cnp))
+    np.add.at(U, rt.j, np.einsum("ari,ark->aik", A, A))
+    ga = np.zeros((nC, cnp))
+    np.add.at(ga, rt.j, np.einsum("ari,ar->ai", A, e))
+    V = np.zeros((nP, 3, 3))
+    np.add.at(V, rt.i, np.einsum("ari,ark->aik", B, B))
+    gb = np.zeros((nP, 3))
+    np.add.at(gb, rt.i, np.einsum("ari,ar->ai", B, e))
+    W = np.einsum("ark,arc->akc", A, B)
+    D = plain_damp_diag(rt, U, V, rule, fault)
+    k3 = np.arange(3)
+    Vs = V.copy()
+    Vs[:, k3, k3] += mu * D[nA:].reshape(-1, 3)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        Y = ldl_solve(Vs[rt.i], W)
+    S = np.zeros((nA, nA))
+    for j in range(nC):
+        S[cnp * j:cnp * j + cnp, cnp * j:cnp * j + cnp] = U[j]
+    S[rt.held, rt.held] = 1.0
+    dU = np.diag(S).copy()
+    if camera:
+        S[np.arange(nA), np.arange(nA)] += mu * D[:nA]
+    ea = ga.reshape(-1).copy()
+    order = np.argsort(rt.i, kind="stable")
+    ptr = np.searchsorted(rt.i[order], np.arange(nP + 1))
+    for i in range(nP):
+        obs = order[ptr[i]:ptr[i + 1]]
+        if obs.size == 0:
+            continue
+        rows = (cnp * rt.j[obs][:, None] + np.arange(cnp)[None, :]).reshape(-1)
+        S[np.ix_(rows, rows)] -= Y[obs].reshape(-1, 3) @ W[obs].reshape(-1, 3).T
+        ea[rows] -= Y[obs].reshape(-1, 3) @ gb[i]
+    return S, ea, dict(Vs=Vs, V=V, W=W, g=np.concatenate([ga.reshape(-1), gb.reshape(-1)]), D=D, dU=dU)
+
+
+def plain_try(rt, mu, rule=NO_RULE, fault=None):
     """One damping try in plain fp64: dp [nT] (dp_a by a Cholesky of the scaled S, dp_b by L D L^T), the proposal and
-    the four sums"""
+    the four sums.  Under Marquardt's rule also D; fault "backsub-identity": dp_b solved with V + mu I while Y was
+    made with V + mu D (the others are plain_damp_diag's)."""
+    if rule.marquardt:
+        return plain_try_damped(rt, mu, rule, fault)
     S, ea, pc = plain_schur(rt, mu)
     d = 1.0 / np.sqrt(np.diag(S))
     L = np.linalg.cholesky(d[:, None] * S * d[None, :])
@@ -283,3 +523,24 @@ def plain_try(rt, mu):
     sc = dict(dp_l2=float(dp @ dp), gain_den=float(dp @ (mu * dp + pc["g"])), newp_l2=float(newp @ newp),
               new_cost=float((e_new * e_new).sum()))
     return dict(S=S, ea=ea, dp=dp, newcams=newcams, newpts=newpts, sc=sc)
+
+
+def plain_try_damped(rt, mu, rule, fault=None):
+    S, ea, pc = plain_schur_damped(rt, mu, rule, fault)
+    D = pc["D"]
+    d = 1.0 / np.sqrt(np.diag(S))
+    L = np.linalg.cholesky(d[:, None] * S * d[None, :])
+    dpa = d * np.linalg.solve(L.T, np.linalg.solve(L, d * ea))
+    dpa[rt.held] = 0.0
+    eb = pc["g"][rt.nA:].reshape(-1, 3).copy()
+    np.subtract.at(eb, rt.i, np.einsum("akc,ak->ac", pc["W"], dpa.reshape(-1, rt.cnp)[rt.j]))
+    Vs = pc["V"] + mu * np.eye(3)[None] if fault == "backsub-identity" else pc["Vs"]
+    dpb = ldl_solve(Vs, eb[:, None, :])[:, 0, :]
+    dp = np.concatenate([dpa, dpb.reshape(-1)])
+    cams = rt.twin.cams[:, np.arange(CNP) if rt.cnp == 16 else SEL11]
+    newcams, newpts = cams + dpa.reshape(-1, rt.cnp), rt.twin.pts + dpb
+    e_new, _ = rt.residuals(newcams, newpts)
+    newp = np.concatenate([newcams.reshape(-1), newpts.reshape(-1)])
+    sc = dict(dp_l2=float(dp @ dp), gain_den=float(dp @ ((mu * D) * dp + pc["g"])), newp_l2=float(newp @ newp),
+              new_cost=float((e_new * e_new).sum()))
+    return dict(S=S, ea=ea, dp=dp, newcams=newcams, newpts=newpts, sc=sc, D=D)

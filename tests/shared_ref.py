@@ -29,6 +29,10 @@ entries (n - 1 additions) and add mu once on the diagonal (one more); the unfold
 its diagonal, so the host's term d_m - mu differs from t_m by at most u |d_m|.  Together:
 |found - exact| <= gamma(n_r n_c + 2) sum |terms|, the terms being the source entries as the buffer holds them and,
 on the diagonal, mu once per source entry.
+
+Under Marquardt's damping (psba_set_damping; free_ref.Rule) the section "Marquardt's damping with groups"
+below gives D of the embedded system, its envelope, the 80-bit S and e_a with mu D added once after the fold, and the
+plain fp64 evaluation with its injected fault.
 """
 import numpy as np
 
@@ -211,13 +215,98 @@ def reduce_sums(rt, sm):
     return np.concatenate([g, sm["g"][nA:]])[rt.keep], np.concatenate([env, sm["envg"][nA:]])[rt.keep]
 
 
-def scalars(rt, sm, dp, newcams, newpts, mu):
-    """free_ref.scalars on the reduced vectors: {name: (exact, bound)}"""
+def scalars(rt, sm, dp, newcams, newpts, mu, D=None):
+    """free_ref.scalars on the reduced vectors: {name: (exact, bound)}.  D [nT] (embedded): Marquardt's weights; a
+    folded-away coordinate contributes nothing, a shared one once with the D of its representative"""
     e_new, proj = rt.residuals(newcams, newpts)
     newp = np.concatenate([np.asarray(newcams).reshape(-1), np.asarray(newpts).reshape(-1)])
     g, envg = reduce_sums(rt, sm)
-    return ar.try_scalars(np.asarray(dp)[rt.keep], newp[rt.keep], mu, g, int((~rt.away).sum()),
-                          (e_new * e_new).sum(axis=1), e_slack=ar.residual_slack(rt.twin.t.m, proj), envg=envg)
+    if D is None:
+        return ar.try_scalars(np.asarray(dp)[rt.keep], newp[rt.keep], mu, g, int((~rt.away).sum()),
+                              (e_new * e_new).sum(axis=1), e_slack=ar.residual_slack(rt.twin.t.m, proj), envg=envg)
+    return ar.try_scalars(np.asarray(dp)[rt.keep], newp[rt.keep], LD(mu) * ar.ld(np.asarray(D)[rt.keep]), g,
+                          int((~rt.away).sum()), (e_new * e_new).sum(axis=1),
+                          e_slack=ar.residual_slack(rt.twin.t.m, proj), envg=envg, extra=1)
+
+
+# ---- Marquardt's damping with groups (psba_set_damping, DESIGN 7g) ------------------------------------------------------
+# D of the embedded system: at a representative's shared coordinate the clamp of the sum of its members' diagonal
+# entries (k_free_damp_diag sums them in ascending camera order), clamp(coeff) at a folded-away or held coordinate,
+# the points as without groups.  The envelope of the sum is the members' K1 envelopes added (free_ref.damp_ref: the
+# rule of shared_tol, every observation of the group once) plus gamma(n_g - 1) of the sum for the n_g - 1 additions
+# of the member sum.  mu D is added once, after the fold (k_kd_fold_finish).
+
+def folded_damp_diag(rt, sm):
+    """(the folded diagonal [nT] in extended precision with the placeholder 1 at held and folded-away coordinates,
+    its envelope [nT], the indices whose entry is a placeholder)"""
+    nA = rt.nA
+    x = sm["diagUx"].copy()
+    x[rt.held] = 0
+    f = np.zeros(nA, dtype=LD)
+    np.add.at(f, rt.phi, x)
+    cnt = np.bincount(rt.phi, minlength=nA)
+    env = (np.bincount(rt.phi, weights=sm["envdU"], minlength=nA)
+           + ar.gamma(np.maximum(cnt - 1, 0)) * np.abs(f.astype(np.float64)))
+    fixed = np.union1d(rt.held, np.flatnonzero(rt.away))
+    f[fixed] = 1
+    env[fixed] = 0.0
+    return np.concatenate([f, sm["diagVx"]]), np.concatenate([env, sm["envdV"]]), fixed
+
+
+def damp_ref(rt, sm, rule=fr.NO_RULE):
+    """free_ref.damp_ref of the embedded system: (D [nT], envD [nT])"""
+    if not rule.marquardt:
+        return np.ones(rt.nT), np.zeros(rt.nT)
+    x, env, fixed = folded_damp_diag(rt, sm)
+    D = rule.clamp(x).astype(np.float64)
+    env = env + ar.U * D
+    env[fixed] = 0.0
+    return D, env
+
+
+def schur_ref(rt, sm, mu, rule):
+    """S and e_a of the embedded system under Marquardt's rule in 80-bit, rounded once: the point blocks damped with
+    mu D_i, the fold of the undamped camera part, then mu D once on the diagonal (1 + mu clamp(1) where folded away)"""
+    D = damp_ref(rt, sm, rule)[0]
+    S, ea = fold(*fr.schur_blocks(rt, mu, D, camera=False), rt.rep, rt.free, 0.0)
+    k = np.arange(rt.nA)
+    S[k, k] += LD(mu) * ar.ld(D[:rt.nA])
+    return S.astype(np.float64), ea.astype(np.float64)
+
+
+def plain_try_damped(rt, mu, rule, fault=None):
+    """plain_try under Marquardt's rule.  fault "rep-own-diag": D of a representative from its own U_kk instead of
+    the members' sum"""
+    S1, ea1, pc = fr.plain_schur_damped(rt, mu, rule, camera=False)
+    S, ea = plain_fold(S1, ea1, rt.rep, rt.free, 0.0)
+    nA = rt.nA
+    dU = pc["dU"].copy()
+    own = dU.copy()
+    dU[rt.held] = 0.0
+    f = np.bincount(rt.phi, weights=dU, minlength=nA)
+    if fault == "rep-own-diag":
+        f = own
+    fixed = np.union1d(rt.held, np.flatnonzero(rt.away))
+    f[fixed] = 1.0
+    D = np.concatenate([rule.clamp(f), pc["D"][nA:]])
+    S[np.arange(nA), np.arange(nA)] += mu * D[:nA]
+    d = 1.0 / np.sqrt(np.diag(S))
+    Lc = np.linalg.cholesky(d[:, None] * S * d[None, :])
+    dpe = d * np.linalg.solve(Lc.T, np.linalg.solve(Lc, d * ea))
+    dpe[rt.held] = 0.0
+    dpe[rt.away] = 0.0
+    dpa = rt.expand(dpe)
+    eb = pc["g"][nA:].reshape(-1, 3).copy()
+    np.subtract.at(eb, rt.i, np.einsum("akc,ak->ac", pc["W"], dpa.reshape(-1, CNP)[rt.j]))
+    dpb = fr.ldl_solve(pc["Vs"], eb[:, None, :])[:, 0, :]
+    dp = np.concatenate([dpa, dpb.reshape(-1)])
+    newcams, newpts = rt.twin.cams + dpa.reshape(-1, CNP), rt.twin.pts + dpb
+    e_new, _ = rt.residuals(newcams, newpts)
+    newp = np.concatenate([newcams.reshape(-1), newpts.reshape(-1)])
+    dr_, nr_ = dp[rt.keep], newp[rt.keep]
+    sc = dict(dp_l2=float(dr_ @ dr_), gain_den=float(dp @ pc["g"] + dr_ @ ((mu * D[rt.keep]) * dr_)),
+              newp_l2=float(nr_ @ nr_), new_cost=float((e_new * e_new).sum()))
+    return dict(S=S, ea=ea, dp=dp, dp_embedded=dpe, newcams=newcams, newpts=newpts, sc=sc, D=D)
 
 
 # ---- a plain fp64 evaluation (what the kernels compute, in numpy) ----------------------------------------------------

@@ -14,7 +14,10 @@ under the BAL mask.  Masks: all free and {fu, k1, k2}.  Dampings: 1e-3 max diag 
         dp_b by dpb_residual, the four try scalars on the reduced vectors.
   * G4  psba_max_diag / psba_begin against the folded maximum, relative 1e-11.
   * G5  all-singleton labels and NULL are bit-identical to a handle that never set groups; grouped runs repeat.
-  * G6  psba_levmar against the shared twin's LM.   G7  recovery of the shared ring scene.   G8  the interface."""
+  * G6  psba_levmar against the shared twin's LM.   G7  recovery of the shared ring scene.   G8  the interface.
+  * G1 and G3 again under Marquardt's damping (psba_set_damping) on wide-above and one-group, BAL mask, at
+    mu = 1e-3 and 1e-6: D of the embedded system, mu D added once after the fold, gain_den with a shared parameter
+    counted once.  The module prints the worst ratios of those cases per input and quantity."""
 import functools
 
 import numpy as np
@@ -386,3 +389,107 @@ def test_interface():
     h.upload_problem(p)
     assert h.intrinsics_groups()[1] == nC and np.array_equal(h.intrinsics_groups()[0], np.arange(nC))
     h.close()
+
+
+# ---- groups under Marquardt's damping (psba_set_damping) ---------------------------------------------------
+MQ_RULE = fr.Rule(fr.MARQUARDT)
+MQ_MUS = {"big": 1e-3, "small": 1e-6}   # Marquardt's mu is relative (test_gpu_damping.py)
+WORST_MQ = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report_marquardt():
+    yield
+    if WORST_MQ:
+        print("\ngroups under Marquardt, worst ratio found / allowed per input and quantity:")
+        for name in sorted({n for n, _ in WORST_MQ}):
+            print(f"  {name}: " + ", ".join(f"{q} {v:.2e}" for (n, q), v in WORST_MQ.items() if n == name))
+
+
+def note_mq(name, what, ratio):
+    WORST_MQ[(name, what)] = max(WORST_MQ.get((name, what), 0.0), float(ratio))
+    print(f"{name} marquardt {what}: {float(ratio):.3e}")
+
+
+@functools.lru_cache(maxsize=None)
+def schur_ref_marquardt(name, mask, mu):
+    rt, sm, _, _ = ref(name, mask)
+    S, ea = sr.schur_ref(rt, sm, mu, MQ_RULE)
+    S.setflags(write=False)
+    ea.setflags(write=False)
+    return S, ea
+
+
+@pytest.mark.parametrize("which_mu", ["big", "small"])
+@pytest.mark.parametrize("name", ["wide-above", "one-group"])
+def test_one_damping_try_entrywise_marquardt(name, which_mu):
+    """G1, G3 under PSBA_DAMPING_MARQUARDT, BAL mask: wide_labels on 65 cameras and all 65 cameras one group (a member
+    sum of 65 terms in k_free_damp_diag).  D of the embedded system is the clamp of the members' sum at a
+    representative's shared coordinate and clamp(coeff) at a folded-away one; mu D is added once, after the fold;
+    gain_den counts a shared parameter once (shared_ref.scalars with the device's D)."""
+    import psba_amd
+    rt, sm, mus, fdiag = ref(name, "bal")
+    nA, mu, cost = rt.nA, MQ_MUS[which_mu], sm["cost"]
+    label = f"{name} bal {which_mu} marquardt"
+    h = handle(rt)
+    try:
+        h.set_damping(psba_amd.DAMPING_MARQUARDT, MQ_RULE.dmin, MQ_RULE.dmax)
+        assert h.damping() == tuple(MQ_RULE) and h.intrinsics_groups()[1] == np.unique(rt.rep).size
+        h.linearize(1.0, 1.0)
+        assert abs(h.max_diag() - 1e3 * mus["big"]) <= 1e-11 * 1e3 * mus["big"]
+        # ---- D of the embedded system
+        D = h.get_damping_diag()
+        x, env, fixed = sr.folded_damp_diag(rt, sm)
+        ratio, k, nlow, nhigh = fr.check_damp_diag(D, x, env, MQ_RULE, fixed)
+        note_mq(name, "D", ratio)
+        assert ratio <= 1.0, f"{label}: D[{k}] = {D[k]!r} outside its envelope"
+        assert nlow >= 3 and np.all(D[np.flatnonzero(rt.away)] == 1.0)
+        # ---- G1
+        h.schur_assemble(mu)
+        S, ea, M = read_system(h, nA)
+        D_ref = sr.damp_ref(rt, sm, MQ_RULE)[0]
+        d = np.sqrt(fdiag[:nA] + mu * D_ref[:nA])
+        eS, ee = sr.scaled_errors(S, ea, *schur_ref_marquardt(name, "bal", mu), d, cost)
+        note_mq(name, "S", eS / rt.tol)
+        note_mq(name, "e_a", ee / rt.tol)
+        assert eS <= rt.tol and ee <= rt.tol, f"{label}: scaled S {eS:.3e}, e_a {ee:.3e}, tol {rt.tol:.3e}"
+        check_padding(M, nA)
+        sr.check_mirror(S)
+        sr.check_embedded(S, ea, rt.away, 1.0 + mu)
+        held = rt.held
+        off = S[held].copy()
+        off[np.arange(held.size), held] = 0.0
+        assert np.all(off == 0.0) and np.all(S[held, held] == 1.0 + mu) and np.all(ea[held] == 0.0)
+        # ---- G3
+        h.schur_reduce()
+        h.schur_solve()
+        sc = h.backsub(mu)
+        assert sc.status == 0
+        dp = h.get_dp()
+        newcams, newpts = h.get_params(1)
+        dpa = dp[:nA].reshape(-1, CNP)
+        assert np.array_equal(dpa[:, :10], dpa[rt.rep][:, :10])
+        assert np.array_equal(newcams[:, :10], newcams[rt.rep][:, :10])
+        assert np.all(dp[:nA][held] == 0.0)
+        emb = dp[:nA].copy()
+        emb[rt.away] = 0.0
+        eta, fe, kappa = fr.solve_judge(S, ea, emb)
+        note_mq(name, "dp_a eta", eta / ETA_MAX)
+        note_mq(name, "dp_a forward", fe / (2 * kappa * 1e-14))
+        assert eta <= ETA_MAX, f"{label}: backward error {eta:.3e} of the scaled system"
+        assert fe <= 2 * kappa * 1e-14, f"{label}: forward error {fe:.3e} (cond {kappa:.2e})"
+        r, bound = fr.dpb_residual(rt, sm, dp, mu, MQ_RULE)
+        ratio, k = ar.excess(r, np.zeros(r.shape, ar.LD), bound)
+        note_mq(name, "dp_b", ratio)
+        assert ratio <= 1.0, f"{label}: point {k // 3} entry {k % 3}: residual {float(r[k]):.3e} > {bound[k]:.3e}"
+        assert np.all(dp[nA + 3 * (rt.nP - 1):] == 0.0)      # the point without observations
+        got = dict(dp_l2=sc.dp_l2, gain_den=sc.gain_den, newp_l2=sc.newp_l2, new_cost=sc.new_cost)
+        bad = []
+        for what, (x, b) in sr.scalars(rt, sm, dp, newcams, newpts, mu, D=D).items():
+            ratio = float(abs(ar.LD(got[what]) - x) / b)
+            note_mq(name, what, ratio)
+            if not ratio <= 1.0:
+                bad.append(f"{what} = {got[what]!r}, exact {float(x)!r}, bound {b:.3e}")
+        assert not bad, f"{label}: " + "; ".join(bad)
+    finally:
+        h.close()
