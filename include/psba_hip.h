@@ -286,6 +286,51 @@ int psba_obs_sq_residuals(psba_handle h, int which, double *s);
  * numpy twin, the oracle's own sums on masked blocks, finite differences and a dense solve of the reduced system. */
 int psba_set_fixed(psba_handle h, const unsigned char *fixed_cams, const unsigned char *fixed_pts);
 int psba_fixed_counts(psba_handle h, int *n_fixed_cams, int *n_fixed_pts);
+
+/* ---- covariance of the refined cameras and points (fixed-K dense route) ------------------------
+ * Definition (the same text in psba_amd/csrc/kernels_cov.hip and DESIGN.md).  The covariance is taken at the current
+ * parameters and uses the linearization of psba_linearize(h, 1, 1): whitened, loss-weighted and masked by
+ * psba_set_fixed, i.e. exactly what the normal equations see.  N = J^T J on the free blocks.  For mu >= 0 and
+ * scale > 0,
+ *   C = scale (N + mu I)^-1 on the free entries, zero on rows and columns of fixed blocks
+ * (not the inverse of the placeholder).  Through the Schur complement:
+ *   cameras   C_aa = scale S(mu)^-1; rows and columns of fixed cameras are removed and returned as zeros
+ *   point i   C_bb,i = scale V*_i^-1 + sum_{j,k in cams(i)} Y_ij^T C_jk Y_ik,  Y_ij = W_ij V*_i^-1,  V*_i = V_i + mu I
+ *             (ordered pairs of the point's free cameras, j == k included); a fixed point gives zeros, a point whose
+ *             cameras are all fixed gives scale V*_i^-1; with every camera fixed no S is assembled and C_aa = 0
+ * The cross blocks C_ab are not returned.  mu = 0 is the true covariance and needs the gauge fixed (two fixed cameras;
+ * DESIGN 7c shows S is positive definite then); mu > 0 gives a regularised inverse, which is NOT a covariance.
+ * scale is the variance factor (1: unit-weight residuals; the reduced chi-square psba_residual / (2 n2Dprojs - free
+ * parameters) is the usual a-posteriori choice).
+ * psba_covariance_compute: with reassemble != 0 it linearizes at the current parameters with coefficients (1, 1)
+ * unless that linearization is current, runs psba_schur_assemble(mu) and psba_schur_reduce, copies S out of the reduce
+ * buffer into a workspace of its own and inverts the copy there (a blocked Cholesky of its own on 16 x 16 MFMA tiles;
+ * the Cholesky chain of psba_schur_solve and its factor are not touched).  The handle is left exactly as after
+ * psba_schur_reduce: psba_get_reduce_buffer then returns the S that was inverted.  reassemble = 0 inverts what the
+ * reduce buffer holds (psba_schur_assemble or psba_set_reduce_buffer before it, as for psba_cholmod_lambda: the hook
+ * the tests use to invert a chosen matrix); only the camera part exists afterwards and psba_get_point_covariance
+ * returns PSBA_E_STATE.  Returns PSBA_OK, PSBA_NOT_SPD or PSBA_SINGULAR_V (bit-or; the outputs are invalid then) and
+ * synchronises.  PSBA_E_INVALID for mu < 0, scale <= 0 or non-finite values; PSBA_E_STATE, with a text that names the
+ * reason, before an upload, while a try is in flight, on 11- or 16-parameter camera blocks, under PSBA_SOLVER_PCG and
+ * under a rank layout or communicator; a refused call changes nothing.
+ * The getters return PSBA_E_STATE until a compute has returned PSBA_OK and again after anything that moves the
+ * parameters or the model (psba_accept, psba_set_params, psba_reset_params, psba_set_distortion,
+ * psba_set_obs_covariance, psba_set_robust_loss, psba_set_fixed, psba_upload_problem), PSBA_E_INVALID for a camera
+ * index out of range.  Workspaces (two n32 x n32 squares, 18 doubles per observation, 9 per point) are allocated on
+ * first use and released by the next upload and by psba_destroy.  No floating-point atomics: two computes on the
+ * same state return bit-identical arrays; C_aa and every point block are bit-symmetric.  PARITY UNPINNED: the
+ * reference's SPDinv inverse is an intermediate of its solve and is never returned -- checked against an
+ * extended-precision inverse of the device's own S, per-entry long-double sums of the point formula and the dense
+ * inverse of a numpy twin's reduced normal matrix. */
+int psba_covariance_compute(psba_handle h, double mu, double scale, int reassemble);
+/* pairs[2 n_pairs] = (j, k) in any order, out[36 n_pairs] row-major = C_jk; pairs NULL: n_pairs must be nCams, the
+ * diagonal blocks */
+int psba_get_camera_covariance(psba_handle h, int n_pairs, const int *pairs, double *out);
+int psba_get_covariance_matrix(psba_handle h, double *Caa /* (6 nCams)^2 row-major, symmetric */);
+int psba_get_point_covariance(psba_handle h, double *out /* n3Dpts*9, full symmetric 3x3 */);
+/* measurement: HIP-event milliseconds of the last psba_covariance_compute that returned PSBA_OK -- factor (with the
+ * compaction), inverse (with the mirror), points.  Linearization and assembly are timed by psba_profile_get. */
+int psba_covariance_times(psba_handle h, double ms3[3]);
 /* which S-assembly route the uploaded problem takes: 0 = LDS-resident partitions of the block
  * triangle with the static schedule (fewer than 2048 cameras, up to 8 GB of partial-sum slabs on
  * this rank), 1 = the owner route for larger problems (one thread per block segment,

@@ -190,6 +190,11 @@ SIGNATURES = [
     ("psba_blockprod_plan_info", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     ("psba_blockprod_plan_copy", C.c_int, [C.c_void_p, _ip, _ip, _ip]),
     ("psba_blockprod_plan_destroy", None, [C.c_void_p]),
+    ("psba_covariance_compute", C.c_int, [_h, C.c_double, C.c_double, C.c_int]),
+    ("psba_get_camera_covariance", C.c_int, [_h, C.c_int, _ip, _dp]),
+    ("psba_get_covariance_matrix", C.c_int, [_h, _dp]),
+    ("psba_get_point_covariance", C.c_int, [_h, _dp]),
+    ("psba_covariance_times", C.c_int, [_h, _dp]),
 ]
 # only in a library built with PSBA_BUILD_EXPERIMENTS=1 (round 3's rejected ring route and its test hooks)
 EXPERIMENT_SIGNATURES = [
@@ -848,6 +853,45 @@ class Psba:
         self._ck(lib.psba_get_free_obs_blocks(self._h, _d(W), _d(Be)))
         Be = Be.reshape(self.nO, 8)
         return W.reshape(self.nO, self.cnp, 3), Be[:, :6].reshape(self.nO, 2, 3).copy(), Be[:, 6:].copy()
+
+    # ---- covariance of the estimate (fixed-K dense route) ----
+    def covariance(self, mu=0.0, scale=1.0, reassemble=True):
+        """psba_covariance_compute: C = scale (J^T J + mu I)^-1 on the free blocks at the current parameters (mu = 0, the
+        true covariance, needs the gauge fixed by set_fixed).  scale="reduced_chi2": residual(PARAMS_CUR) /
+        (2 nO - number of free parameters).  Returns PSBA_OK, PSBA_NOT_SPD or PSBA_SINGULAR_V (the getters refuse
+        then); raises on errors."""
+        if isinstance(scale, str):
+            if scale != "reduced_chi2":
+                raise PsbaError(-1, f"covariance: unknown scale {scale!r}")
+            fc, fp = self.fixed_counts()
+            dof = 2 * self.nO - (self.nT - self.cnp * fc - 3 * fp)
+            if dof <= 0:
+                raise PsbaError(-1, f"covariance: reduced_chi2 needs more residuals than free parameters (dof = {dof})")
+            scale = self.residual(PARAMS_CUR) / dof
+        return self._ck(lib.psba_covariance_compute(self._h, float(mu), float(scale), int(bool(reassemble))))
+
+    def camera_covariance(self, pairs=None):
+        """psba_get_camera_covariance: [n, 6, 6] blocks C_jk of the pairs [(j, k), ...]; None: the nC diagonal blocks."""
+        if pairs is None:
+            out = np.empty((self.nC, 6, 6))
+            self._ck(lib.psba_get_camera_covariance(self._h, self.nC, None, _d(out)))
+            return out
+        p = _c(pairs, np.int32).reshape(-1, 2)
+        out = np.empty((p.shape[0], 6, 6))
+        self._ck(lib.psba_get_camera_covariance(self._h, p.shape[0], _i(p), _d(out)))
+        return out
+
+    def covariance_matrix(self):
+        """psba_get_covariance_matrix: C_aa [nA, nA], symmetric, zero rows and columns for fixed cameras."""
+        return self._out(lib.psba_get_covariance_matrix, self.nA * self.nA)[1].reshape(self.nA, self.nA)
+
+    def point_covariance(self):
+        """psba_get_point_covariance: C_bb,i [nP, 3, 3] (not after covariance(reassemble=False))."""
+        return self._out(lib.psba_get_point_covariance, 9 * self.nP)[1].reshape(self.nP, 3, 3)
+
+    def covariance_times(self):
+        """psba_covariance_times: HIP-event ms (factor, inverse, points) of the last covariance()."""
+        return self._out(lib.psba_covariance_times, 3)[1]
 
     def trust_region(self, max_iter=50, start_itno=0, verbose=False, log_cap=512, init_lambda=0.0):
         opts = TrOptions(max_iter, start_itno, int(verbose), log_cap, init_lambda)

@@ -233,6 +233,7 @@ static void lens_changed(psba_ctx *h) {
   h->linearized = h->assembled = h->solved = false;
   h->free_obs = false;
   h->damp_ok = false;
+  h->cov_ok = h->cov_pts_ok = false;
 }
 
 static int groups_split(psba_ctx *h, const char *who, const std::vector<int> &rep, const double *v, int stride, int ncols,
@@ -260,6 +261,7 @@ static int set_start_distortion(psba_ctx *h, const double *kc) {
   h->linearized = h->assembled = h->solved = h->backsubbed = false;
   h->free_obs = false;
   h->damp_ok = false;
+  h->cov_ok = h->cov_pts_ok = false;
   return PSBA_OK;
 }
 
@@ -1042,6 +1044,7 @@ int psba_set_params(psba_handle h, const double *camsEx, const double *pts3D) {
   h->ahead = h->lin_is_ahead = h->backsub_pending = h->publish_deferred = h->publish_in_k1 = false;
   h->free_obs = false;
   h->damp_ok = false;
+  h->cov_ok = h->cov_pts_ok = false;
   return PSBA_OK;
 }
 
@@ -1056,6 +1059,7 @@ int psba_reset_params(psba_handle h) {
   h->ahead = h->lin_is_ahead = h->backsub_pending = h->publish_deferred = h->publish_in_k1 = false;
   h->free_obs = false;
   h->damp_ok = false;
+  h->cov_ok = h->cov_pts_ok = false;
   return PSBA_OK;
 }
 
@@ -1363,6 +1367,7 @@ int psba_accept(psba_handle h) {
   NEED(h, h->backsubbed, "psba_backsub first");
   h->cur = 1 - h->cur;
   h->linearized = h->assembled = h->solved = h->backsubbed = false;
+  h->cov_ok = h->cov_pts_ok = false;  // the covariance belonged to the parameters that were current
   h->free_obs = h->ahead && h->cnp != 6;  // W_alt and free_Be of the linearization queued ahead become the current pair
   if (h->ahead) {  // the linearization at the (now current) proposed parameters exists already
     std::swap(h->W, h->W_alt);
@@ -1674,6 +1679,130 @@ int psba_get_free_obs_blocks(psba_handle h, double *W, double *Be) {
        "invalidate the blocks)");
   TRY(d2h(h, W, h->W, sizeof(double) * 3 * (size_t)h->cnp * h->d.nO));
   return d2h(h, Be, h->free_Be, sizeof(double) * 8 * (size_t)h->d.nO);
+}
+
+// ---- covariance of the estimate (kernels_cov.hip) ------------------------------------
+
+namespace {
+struct CovEvents {  // the four stamps of one compute: before the factor, before the inverse, before the points, the end
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~CovEvents() {
+    for (hipEvent_t v : e)
+      if (v) (void)hipEventDestroy(v);
+  }
+};
+}  // namespace
+
+int psba_covariance_compute(psba_handle h, double mu, double scale, int reassemble) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, !h->backsub_pending, "a damping try is in flight (psba_backsub_wait first)");
+  if (h->cnp != 6)
+    return fail(h, PSBA_E_STATE, "%s: six-parameter camera blocks only (not %s)", __func__,
+                h->cnp == KD_CNP ? "PSBA_CAMERA_FREE_KD" : "PSBA_CAMERA_FREE_K");
+  NEED(h, h->solver != PSBA_SOLVER_PCG, "the dense solver only: PSBA_SOLVER_PCG assembles no dense S to invert");
+  NEED(h, !h->comm && h->nranks == 1, "single rank only: not under a rank layout or a communicator");
+  if (!(std::isfinite(mu) && mu >= 0.0)) return fail(h, PSBA_E_INVALID, "%s: mu must be finite and >= 0 (got %.17g)", __func__, mu);
+  if (!(std::isfinite(scale) && scale > 0.0))
+    return fail(h, PSBA_E_INVALID, "%s: scale must be finite and > 0 (got %.17g)", __func__, scale);
+  if (!reassemble) {
+    NEED(h, h->assembled, "reassemble = 0 inverts what the reduce buffer holds (psba_schur_assemble first)");
+    NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S to invert");
+  }
+  h->cov_ok = h->cov_pts_ok = false;
+  if (reassemble) {
+    if (!(h->linearized && h->coeff == 1.0 && h->coeff_g == 1.0)) TRY(psba_linearize(h, 1.0, 1.0));
+    TRY(psba_schur_assemble(h, mu));
+    TRY(psba_schur_reduce(h));
+  }
+  const bool with_S = !h->try_shortcut;  // structure-only: nothing was assembled, C_aa = 0
+  CovEvents ev;
+  for (hipEvent_t &e : ev.e) PSBA_HIP(h, hipEventCreate(&e));
+  if (!h->cov_status) TRY(h->cov_status.alloc(h, 2));
+  PSBA_HIP(h, hipMemsetAsync(h->cov_status, 0, 2 * sizeof(int), h->stream));
+  if (with_S) {
+    TRY(launch_cov_cameras(h, scale, ev.e));
+  } else {
+    const size_t nn = (size_t)h->n32 * h->n32;
+    if (!h->cov_C) TRY(h->cov_C.alloc(h, nn));
+    for (int k = 0; k < 3; k++) PSBA_HIP(h, hipEventRecord(ev.e[k], h->stream));
+    PSBA_HIP(h, hipMemsetAsync(h->cov_C, 0, sizeof(double) * nn, h->stream));
+  }
+  if (reassemble) TRY(launch_cov_points(h, mu, scale, with_S));
+  PSBA_HIP(h, hipEventRecord(ev.e[3], h->stream));
+  int st[2] = {0, 0};
+  TRY(d2h(h, st, h->cov_status, sizeof st));
+  for (int k = 0; k < 3; k++) {
+    float ms = 0.f;
+    PSBA_HIP(h, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+    h->cov_ms[k] = ms;
+  }
+  if (st[0] || st[1]) {
+    h->err = std::string(__func__) + (st[0] ? ": S is not positive definite (a pivot of its Cholesky factor is not positive and finite)"
+                                            : ": some V_i + mu I is singular");
+    return (st[0] ? PSBA_NOT_SPD : 0) | (st[1] ? PSBA_SINGULAR_V : 0);
+  }
+  h->cov_ok = true;
+  h->cov_pts_ok = reassemble != 0;
+  return PSBA_OK;
+}
+
+#define NEED_COV(h)                                                                                                  \
+  do {                                                                                                               \
+    NEED(h, (h)->uploaded, "no problem uploaded");                                                                   \
+    NEED(h, (h)->cov_ok,                                                                                             \
+         "psba_covariance_compute first (whatever moves the parameters or the model invalidates the covariance)"); \
+  } while (0)
+
+int psba_get_camera_covariance(psba_handle h, int n_pairs, const int *pairs, double *out) {
+  CHECK_H(h);
+  NEED_COV(h);
+  const int nC = h->d.nC;
+  if (!out) return fail(h, PSBA_E_INVALID, "%s: null output", __func__);
+  if (n_pairs < 0 || (!pairs && n_pairs != nC))
+    return fail(h, PSBA_E_INVALID, "%s: n_pairs = %d (without a pair list it must be the number of cameras, %d)", __func__, n_pairs, nC);
+  std::vector<int2> jk((size_t)n_pairs);
+  for (int q = 0; q < n_pairs; q++) {
+    jk[q] = pairs ? make_int2(pairs[2 * q], pairs[2 * q + 1]) : make_int2(q, q);
+    if (jk[q].x < 0 || jk[q].x >= nC || jk[q].y < 0 || jk[q].y >= nC)
+      return fail(h, PSBA_E_INVALID, "%s: pair %d = (%d, %d) names a camera out of range (%d cameras)", __func__, q, jk[q].x, jk[q].y, nC);
+  }
+  if (n_pairs == 0) return PSBA_OK;
+  DevBuf<int2> jk_dev;
+  DevBuf<double> out_dev;
+  TRY(jk_dev.alloc(h, jk.size()));
+  TRY(out_dev.alloc(h, 36 * jk.size()));
+  PSBA_HIP(h, hipMemcpyAsync(jk_dev, jk.data(), sizeof(int2) * jk.size(), hipMemcpyHostToDevice, h->stream));
+  int rc = launch_cov_gather(h, jk_dev, n_pairs, out_dev);
+  if (rc == PSBA_OK) rc = d2h(h, out, out_dev, sizeof(double) * 36 * jk.size());
+  (void)hipStreamSynchronize(h->stream);  // (before the two buffers go)
+  return rc;
+}
+
+int psba_get_covariance_matrix(psba_handle h, double *Caa) {
+  CHECK_H(h);
+  NEED_COV(h);
+  if (!Caa) return fail(h, PSBA_E_INVALID, "%s: null output", __func__);
+  PSBA_HIP(h, hipMemcpy2DAsync(Caa, sizeof(double) * h->d.nA, h->cov_C, sizeof(double) * h->n32, sizeof(double) * h->d.nA,
+                               h->d.nA, hipMemcpyDeviceToHost, h->stream));
+  PSBA_HIP(h, hipStreamSynchronize(h->stream));
+  return PSBA_OK;
+}
+
+int psba_get_point_covariance(psba_handle h, double *out) {
+  CHECK_H(h);
+  NEED_COV(h);
+  NEED(h, h->cov_pts_ok, "only the camera part exists after psba_covariance_compute with reassemble = 0");
+  if (!out) return fail(h, PSBA_E_INVALID, "%s: null output", __func__);
+  return d2h(h, out, h->cov_pts, sizeof(double) * 9 * (size_t)h->d.nP);
+}
+
+int psba_covariance_times(psba_handle h, double ms3[3]) {
+  CHECK_H(h);
+  NEED_COV(h);
+  if (!ms3) return fail(h, PSBA_E_INVALID, "%s: null output", __func__);
+  for (int k = 0; k < 3; k++) ms3[k] = h->cov_ms[k];
+  return PSBA_OK;
 }
 
 // ---- sba_func.h mirror ------------------------------------------------------------------

@@ -324,6 +324,17 @@ struct ProblemState {
   psba::DevBuf<double> chol_L;    // [(2 n32+16)][n32] panel chain: the Cholesky factor | forward-solved e_a row | L^-T
   psba::DevBuf<double> dist_buf;  // sharded factorization: packed column blocks of one super-panel (allocated on first use)
   psba::DevBuf<double> chol_ws;   // [ceil(nA/32)][32*32] inverses of the diagonal blocks of L (diagBlkAux_buffer)
+  // covariance of the estimate (psba_covariance_compute; kernels_cov.hip): workspaces of its own, allocated
+  // on first use -- the private copy of S that becomes its factor, the inverse, the inverses of the factor's diagonal
+  // tiles, Y_ij of the points, the 3 x 3 point blocks and the two status words (not SPD, singular V)
+  psba::DevBuf<double> cov_L, cov_C;  // [n32][n32] each
+  psba::DevBuf<double> cov_dinv;      // [n32 / 16][256]
+  psba::DevBuf<double> cov_Y;         // [nO][18]
+  psba::DevBuf<double> cov_pts;       // [nP][9]
+  psba::DevBuf<int> cov_status;       // [2]
+  bool cov_ok = false;                // cov_C is the camera covariance of the current parameters and model
+  bool cov_pts_ok = false;            // ... and cov_pts the point blocks (not after reassemble = 0)
+  double cov_ms[3] = {0.0, 0.0, 0.0}; // factor, inverse, points of the last compute (psba_covariance_times)
   // debug dumps for the sba_func.h mirror (allocated on first use)
   psba::DevBuf<double> dbg_ex, dbg_JA, dbg_JB, dbg_Y, dbg_Vinv, dbg_eb;
 
@@ -461,6 +472,10 @@ int chol_dist_finish(psba_ctx *h);
 int launch_backsub(psba_ctx *h, double mu, bool dump);
 int launch_publish_scal(psba_ctx *h, hipStream_t s);
 int launch_struct_only_try(psba_ctx *h, double mu);
+// kernels_cov.hip
+int launch_cov_cameras(psba_ctx *h, double scale, hipEvent_t *ev);
+int launch_cov_points(psba_ctx *h, double mu, double scale, bool with_C);
+int launch_cov_gather(psba_ctx *h, const int2 *pairs_dev, int n_pairs, double *out_dev);
 // kernels_tr.hip
 int launch_jmul(psba_ctx *h, const double *x1_dev, const double *x2_dev, double *out1_dev, double *dots_dev);
 int launch_pack_g(psba_ctx *h, double *g_dev);
