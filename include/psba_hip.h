@@ -193,6 +193,35 @@ int psba_intrinsics_groups(psba_handle h, int *rep_of_cam, int *n_groups);
 int psba_set_damping(psba_handle h, int kind, double dmin, double dmax);
 int psba_damping(psba_handle h, int *kind, double *dmin, double *dmax);
 
+/* ---- held poses and points of the free-intrinsics models (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD) ----
+ * Without held blocks S is singular at mu = 0 on these models (the gauge is free): no Gauss-Newton step, no
+ * reference frame, no control points.  held_poses[j] != 0 holds the POSE of camera j -- the six pose coordinates, the
+ * last six of its block (indices NI .. CNP-1, NI = 5 / 10) -- and held_pts[i] != 0 the three coordinates of point i.
+ * The camera's intrinsics stay under psba_set_intrinsics_mask and psba_set_intrinsics_groups: one physical camera
+ * whose first two poses fix the gauge is the common case, which holding whole blocks would forbid.  psba_set_fixed
+ * keeps refusing both models, and so does psba_covariance_compute.
+ * Model.  The problem solved is the reduced one (the held columns of J deleted, the held values constants of the
+ * residual), stored embedded in the full-size system; per held coordinate exactly what a coordinate held by
+ * psba_set_intrinsics_mask is: the column of A is zero for a held pose coordinate and B is zero for a held point, applied
+ * before W = coeff A^T B, so the W rows (the whole W of a held point) are exactly 0; the stored diagonal entry of U_j
+ * or V_i is the placeholder coeff and the off-diagonal entries of a held V_i are 0; g and dp are exactly 0; the
+ * proposed and the accepted values are bit-identical to the current ones; psba_max_diag / psba_begin take the maximum
+ * over the free entries; row and column of S are zero off the diagonal with coeff + mu on it (coeff + mu clamp(coeff)
+ * under PSBA_DAMPING_MARQUARDT: D is the clamp of the stored diagonal); e_a is 0.  The cost is untouched: every
+ * observation counts, and a held point's observations enter new_cost at the moved cameras.  psba_set_params may still
+ * move a held block.  Held blocks, mask, groups and damping compose in any order of calls (the fold of the groups
+ * touches intrinsic coordinates only).
+ * NULL = none of that kind, two NULLs clear the masks; a mask without a non-zero entry is no mask: the handle then
+ * runs the kernels of one that never called this and produces the same bits.  After psba_upload_problem (a new upload
+ * resets to none); PSBA_E_STATE before an upload, while a try is in flight and on six-parameter camera blocks (those
+ * are held as a whole by psba_set_fixed); PSBA_E_INVALID if every pose and every point would be held (a resection of
+ * the intrinsics alone is not supported); a refused call changes nothing; setting the masks discards a linearization
+ * queued ahead and invalidates psba_get_free_obs_blocks and psba_get_damping_diag.  No floating-point atomics: two
+ * runs stay bit-identical.  PARITY UNPINNED, like the models it belongs to.  psba_held_counts: the numbers of held
+ * poses and points (either pointer may be NULL). */
+int psba_set_held(psba_handle h, const unsigned char *held_poses /* nCams */, const unsigned char *held_pts /* n3Dpts */);
+int psba_held_counts(psba_handle h, int *n_held_poses, int *n_held_pts);
+
 /* ---- lens distortion and per-observation image covariances --------------------------
  * Model (the same in psba_amd/csrc/camera_model.h and DESIGN.md): P = R'(q) M + t, (x, y) = (Px, Py) / Pz,
  * r2 = x^2 + y^2, kc = (k1, k2, k3, k4, k5) in the Camera Calibration Toolbox order (the column order of the

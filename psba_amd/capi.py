@@ -161,6 +161,8 @@ SIGNATURES = [
     ("psba_obs_sq_residuals", C.c_int, [_h, C.c_int, _dp]),
     ("psba_set_fixed", C.c_int, [_h, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
     ("psba_fixed_counts", C.c_int, [_h, _ip, _ip]),
+    ("psba_set_held", C.c_int, [_h, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    ("psba_held_counts", C.c_int, [_h, _ip, _ip]),
     ("psba_read_problem_ex", C.c_int, [C.c_char_p, C.c_char_p, _dp, C.POINTER(CProblemEx)]),
     ("psba_free_problem_ex", None, [C.POINTER(CProblemEx)]),
     ("psba_convert_bal_kd", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
@@ -591,6 +593,28 @@ class Psba:
         """psba_fixed_counts -> (fixed cameras, fixed points)"""
         c, p = C.c_int(), C.c_int()
         self._ck(lib.psba_fixed_counts(self._h, C.byref(c), C.byref(p)))
+        return c.value, p.value
+
+    def set_held(self, poses=None, pts=None):
+        """psba_set_held (free-intrinsics models): poses [nC], pts [nP] boolean or integer arrays, non-zero = the
+        camera's six pose coordinates / the point are held constant (the intrinsics stay under the mask and the
+        groups); None = none of that kind, two Nones clear the masks."""
+        def mask(a, n, what):
+            if a is None:
+                return None
+            m = (np.asarray(a).reshape(-1) != 0).astype(np.uint8)
+            if n and m.size != n:  # (before an upload n is 0: the library refuses, nothing is read)
+                raise PsbaError(-1, f"set_held: {m.size} flags for {n} {what}")
+            return np.ascontiguousarray(m)
+        c, p = mask(poses, self.nC, "poses"), mask(pts, self.nP, "points")
+        ub = C.POINTER(C.c_ubyte)
+        self._ck(lib.psba_set_held(self._h, None if c is None else c.ctypes.data_as(ub),
+                                   None if p is None else p.ctypes.data_as(ub)))
+
+    def held_counts(self):
+        """psba_held_counts -> (held poses, held points)"""
+        c, p = C.c_int(), C.c_int()
+        self._ck(lib.psba_held_counts(self._h, C.byref(c), C.byref(p)))
         return c.value, p.value
 
     def obs_sq_residuals(self, which=PARAMS_CUR):

@@ -51,6 +51,16 @@ struct FreeKD {
 // per observation: W (or Y) is CNP x 3 row-major; per unit: the partial A^T A (CNP x CNP) | A^T e (CNP); the LDS row
 // of a staged observation is A (2 x CNP) | e | pad (an odd stride: 25 and 35)
 
+// ---- held poses and points (psba_set_held) ----
+// A held pose is the six pose coordinates NI .. CNP-1 of a camera (its intrinsics stay under the mask and the groups),
+// a held point its three coordinates.  Each held coordinate is what a coordinate held by psba_set_intrinsics_mask is:
+// its column of A (B for a point) is zeroed behind T::linearize, before W, Be and the LDS rows are written, so W, the
+// sums and g are exactly 0 there and k_free_Y, k_free_schur, the combine, finalize and fold kernels run unchanged on
+// the zeros; the stored diagonal entry is the placeholder coeff (k_free_damp_diag clamps it as it stands); the
+// maximum of the diagonal skips it; dp is exactly 0 and the proposal takes the current bits.  The cost is untouched.
+// The kernels that read the two byte masks are templated on HELD; a handle without a non-zero entry in either mask
+// runs the false instantiations, which are the code as it was (no load of a mask).  With HELD both masks are
+// allocated ([nC] and [nP]), so no kernel tests a pointer.
 struct FreeArgs {
   const double *camconst, *cams, *pts, *impts;
   const int *iidx, *jidx, *ptr, *cam_obs;
@@ -62,6 +72,7 @@ struct FreeArgs {
   const double *pub_src;  // the look-ahead linearization carries the try's scalar block to the host (see k_linearize)
   double *pub_dst;
   double pub_stamp;
+  const unsigned char *held_pose, *held_pt;  // read by the HELD instantiations only (last: the other offsets stay)
 };
 
 template <class T>
@@ -87,7 +98,7 @@ __device__ __forceinline__ double free_wave_sum(double v) {
 
 // camera-major: one wave per unit = up to 64 observations of one camera, one per lane.  e, A (masked), B; W_a and
 // (B | e) to global memory, the Jacobian rows to LDS, then U and g_a of the unit by MFMA
-template <class T>
+template <class T, bool HELD>
 __global__ __launch_bounds__(64) void k_free_linearize(FreeArgs p) {
   constexpr int CNP = T::CNP, ROW = 2 * CNP + 3;
   __shared__ double sJ[KD_UNIT][ROW];
@@ -107,6 +118,16 @@ __global__ __launch_bounds__(64) void k_free_linearize(FreeArgs p) {
     double2 m;
     free_load<T>(p, a, i, j, cam, q0, M, m);
     T::linearize(cam, q0, M, m.x, m.y, e, A, B, p.mask);
+    if (HELD) {  // (selects on registers, before anything is stored)
+      const bool hp = p.held_pose[j] != 0, hq = p.held_pt[i] != 0;
+#pragma unroll
+      for (int k = T::NI; k < CNP; k++) {
+        A[k] = hp ? 0.0 : A[k];
+        A[CNP + k] = hp ? 0.0 : A[CNP + k];
+      }
+#pragma unroll
+      for (int k = 0; k < 6; k++) B[k] = hq ? 0.0 : B[k];
+    }
     double *w = p.W + 3 * CNP * (size_t)a;
 #pragma unroll
     for (int r = 0; r < CNP; r++)
@@ -150,10 +171,12 @@ __global__ __launch_bounds__(64) void k_free_linearize(FreeArgs p) {
 }
 
 // the units of one camera in unit order: U_j (full CNP x CNP, scaled by coeff, the placeholder coeff on the diagonal
-// of a masked intrinsic) and g_a,j (scaled by coeff_g).  A camera without observations has zero sums
-template <class T>
+// of a masked intrinsic and of a held pose coordinate) and g_a,j (scaled by coeff_g).  A camera without observations
+// has zero sums
+template <class T, bool HELD>
 __global__ __launch_bounds__(256) void k_free_finish_cams(const double *upart, const int *cuptr, int nC, double coeff,
-                                                          double coeff_g, unsigned mask, double *U, double *ga) {
+                                                          double coeff_g, unsigned mask, const unsigned char *held_pose,
+                                                          double *U, double *ga) {
   constexpr int CNP = T::CNP, UP = CNP * CNP + CNP;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)nC * UP) return;
@@ -162,16 +185,19 @@ __global__ __launch_bounds__(256) void k_free_finish_cams(const double *upart, c
   for (int u = cuptr[j]; u < cuptr[j + 1]; u++) s += upart[UP * (size_t)u + e];
   if (e < CNP * CNP) {
     const int r = e / CNP, c = e % CNP;
-    const bool held = r == c && r < T::NI && !((mask >> r) & 1u);
+    bool held = r == c && r < T::NI && !((mask >> r) & 1u);
+    if (HELD) held = held || (r == c && r >= T::NI && held_pose[j]);
     U[(size_t)CNP * CNP * j + e] = held ? coeff : coeff * s;
   } else {
     ga[(size_t)CNP * j + (e - CNP * CNP)] = coeff_g * s;
   }
 }
 
-// V_i and g_b,i: thread per point over its contiguous observations, in observation order
+// V_i and g_b,i: thread per point over its contiguous observations, in observation order.  A held point: its B is
+// zero, so the sums are; the diagonal takes the placeholder (V_i = coeff I, g_b,i = 0)
+template <bool HELD>
 __global__ __launch_bounds__(256) void k_free_point_sums(const double *Be, const int *ptr, int nP, double coeff,
-                                                         double coeff_g, double *PV) {
+                                                         double coeff_g, const unsigned char *held_pt, double *PV) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nP) return;
   double v[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
@@ -194,6 +220,11 @@ __global__ __launch_bounds__(256) void k_free_point_sums(const double *Be, const
   for (int k = 0; k < 6; k++) pv[k] = coeff * v[k];
 #pragma unroll
   for (int k = 0; k < 3; k++) pv[6 + k] = coeff_g * g[k];
+  if (HELD && held_pt[i]) {
+    pv[0] = pv[3] = pv[5] = coeff;
+    pv[1] = pv[2] = pv[4] = 0.0;
+    pv[6] = pv[7] = pv[8] = 0.0;
+  }
 }
 
 // cost: per-workgroup partial sums; k_free_sum_columns adds them in workgroup order
@@ -225,17 +256,20 @@ __global__ __launch_bounds__(64) void k_free_sum_columns(const double *head, con
 }
 
 // the largest diagonal entry of U and V over the free parameters (a maximum does not depend on the order)
-template <class T>
+template <class T, bool HELD>
 __global__ __launch_bounds__(1024) void k_free_max_diag(const double *U, const double *PV, int nC, int nP, unsigned mask,
+                                                        const unsigned char *held_pose, const unsigned char *held_pt,
                                                         double *out) {
   constexpr int CNP = T::CNP;
   __shared__ double sRed[16];
   double m = 0.0;
   for (int t = threadIdx.x; t < CNP * nC; t += blockDim.x) {
     const int r = t % CNP;
+    if (HELD && r >= T::NI && held_pose[t / CNP]) continue;
     if (r >= T::NI || ((mask >> r) & 1u)) m = fmax(m, U[(size_t)CNP * CNP * (t / CNP) + (CNP + 1) * r]);
   }
   for (int i = threadIdx.x; i < nP; i += blockDim.x) {
+    if (HELD && held_pt[i]) continue;
     const double *v = PV + 9 * (size_t)i;
     m = fmax(m, fmax(v[0], fmax(v[3], v[5])));
   }
@@ -437,6 +471,7 @@ struct FreeBackArgs {
   FreeDamp dm;
   unsigned mask;
   int nA, nP;
+  const unsigned char *held_pose, *held_pt;  // read by the HELD instantiations only
 };
 __device__ __forceinline__ void free_block_sums4(double *v4, double (*sRed)[4], double *dst) {
 #pragma unroll
@@ -447,7 +482,7 @@ __device__ __forceinline__ void free_block_sums4(double *v4, double (*sRed)[4], 
   __syncthreads();
   if (threadIdx.x < 4) dst[threadIdx.x] = ((sRed[threadIdx.x][0] + sRed[threadIdx.x][1]) + sRed[threadIdx.x][2]) + sRed[threadIdx.x][3];
 }
-template <class T>
+template <class T, bool HELD>
 __global__ __launch_bounds__(256) void k_free_backsub_cams(FreeBackArgs p) {  // one workgroup, launched first: proposal cams
   __shared__ double sRed[4][4];
   double v4[4] = {0.0, 0.0, 0.0, 0.0};  // dp_l2, gain_den, (new cost: the point kernel's), newp_l2
@@ -457,10 +492,11 @@ __global__ __launch_bounds__(256) void k_free_backsub_cams(FreeBackArgs p) {  //
   }
   for (int t = threadIdx.x; t < p.nA; t += blockDim.x) {
     const int r = t % T::CNP;
-    const bool held = r < T::NI && !((p.mask >> r) & 1u);
+    const bool hp = HELD && r >= T::NI && p.held_pose[t / T::CNP];
+    const bool held = hp || (r < T::NI && !((p.mask >> r) & 1u));
     double d = p.dp[t];
     if (held) p.dp[t] = d = 0.0;  // (already zero to rounding: S decouples the entry; exactly zero by definition)
-    const double c = p.cams[t] + d;
+    const double c = hp ? p.cams[t] : p.cams[t] + d;  // (a held pose keeps its bits: -0.0 + 0.0 would be +0.0)
     p.newcams[t] = c;
     v4[0] += d * d;
     const double mud = p.dm.D ? p.mu * p.dm.D[t] : p.mu;
@@ -469,7 +505,7 @@ __global__ __launch_bounds__(256) void k_free_backsub_cams(FreeBackArgs p) {  //
   }
   free_block_sums4(v4, sRed, p.red);
 }
-template <class T>
+template <class T, bool HELD>
 __global__ __launch_bounds__(256) void k_free_backsub_pts(FreeBackArgs p) {
   constexpr int CNP = T::CNP;
   __shared__ double sRed[4][4];
@@ -503,10 +539,13 @@ __global__ __launch_bounds__(256) void k_free_backsub_pts(FreeBackArgs p) {
       v[5] += p.mu;
     }
     sym3_ldl_solve(sym3_ldl(v), e0, e1, e2, d[0], d[1], d[2]);
+    const bool hq = HELD && p.held_pt[i];  // a held point: dp exactly 0, the proposal takes the current bits
     double n3[3];
 #pragma unroll
     for (int q = 0; q < 3; q++) {
-      n3[q] = p.pts[3 * (size_t)i + q] + d[q];
+      const double cur = p.pts[3 * (size_t)i + q];
+      if (hq) d[q] = 0.0;
+      n3[q] = hq ? cur : cur + d[q];
       p.dp[p.nA + 3 * (size_t)i + q] = d[q];
       p.newpts[3 * (size_t)i + q] = n3[q];
       v4[0] += d[q] * d[q];
@@ -630,13 +669,16 @@ __global__ __launch_bounds__(256) void k_kd_fold_finish(double *S, double *ea, K
 }
 
 // k_free_max_diag over the folded diagonal of U: a shared free coordinate counts once, with the sum over its group
+template <bool HELD>
 __global__ __launch_bounds__(1024) void k_kd_max_diag_groups(const double *U, const double *PV, int nC, int nP, KdGroups G,
+                                                             const unsigned char *held_pose, const unsigned char *held_pt,
                                                              double *out) {
   __shared__ double sRed[16];
   double m = 0.0;
   for (int t = threadIdx.x; t < KD_CNP * nC; t += blockDim.x) {
     const int j = t / KD_CNP, r = t % KD_CNP;
     if (r < 10 && !((G.mask >> r) & 1u)) continue;
+    if (HELD && r >= 10 && held_pose[j]) continue;
     const int g = r < 10 ? G.gidx[j] : -1;
     if (g < 0) {
       m = fmax(m, U[(size_t)KD_CNP * KD_CNP * j + (KD_CNP + 1) * r]);
@@ -647,6 +689,7 @@ __global__ __launch_bounds__(1024) void k_kd_max_diag_groups(const double *U, co
     }
   }
   for (int i = threadIdx.x; i < nP; i += blockDim.x) {
+    if (HELD && held_pt[i]) continue;
     const double *v = PV + 9 * (size_t)i;
     m = fmax(m, fmax(v[0], fmax(v[3], v[5])));
   }
@@ -663,6 +706,7 @@ __global__ __launch_bounds__(1024) void k_kd_max_diag_groups(const double *U, co
 // k_free_backsub_cams with the step expanded: a folded-away entry reads its representative's dp (which the
 // representative's own thread leaves as solved) and writes only its own; dp_l2, mu dp^2 and newp_l2 count a shared
 // parameter once, dp g goes over every entry (sum_all dp g = dp_shared P^T g)
+template <bool HELD>
 __global__ __launch_bounds__(256) void k_kd_backsub_cams_groups(FreeBackArgs p, const int *rep) {
   __shared__ double sRed[4][4];
   double v4[4] = {0.0, 0.0, 0.0, 0.0};
@@ -672,12 +716,13 @@ __global__ __launch_bounds__(256) void k_kd_backsub_cams_groups(FreeBackArgs p, 
   }
   for (int t = threadIdx.x; t < p.nA; t += blockDim.x) {
     const int j = t / KD_CNP, r = t % KD_CNP;
-    const bool held = r < 10 && !((p.mask >> r) & 1u);
+    const bool hp = HELD && r >= 10 && p.held_pose[j];
+    const bool held = hp || (r < 10 && !((p.mask >> r) & 1u));
     const bool copy = r < 10 && !held && rep[j] != j;
     double d = copy ? p.dp[KD_CNP * (size_t)rep[j] + r] : p.dp[t];
     if (held) d = 0.0;
     if (held || copy) p.dp[t] = d;
-    const double c = p.cams[t] + d;
+    const double c = hp ? p.cams[t] : p.cams[t] + d;  // (a held pose keeps its bits, as in k_free_backsub_cams)
     p.newcams[t] = c;
     if (!copy) {
       const double mud = p.dm.D ? p.mu * p.dm.D[t] : p.mu;
@@ -714,6 +759,8 @@ static FreeArgs free_args(psba_ctx *h, int set) {
   a.ptr = h->ptr;
   a.cam_obs = h->cam_obs;
   a.cam_units = h->cam_units;
+  a.held_pose = h->held_poses;
+  a.held_pt = h->held_pts;
   a.W = nullptr;
   a.Be = h->free_Be;
   a.upart = h->free_upart;
@@ -730,7 +777,7 @@ static int free_grid(long long n, int cap) {
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-template <class T>
+template <class T, bool HELD>
 static int linearize_free(psba_ctx *h, bool ahead, bool publish) {
   const Dims &d = h->d;
   const int set = ahead ? 1 - h->cur : h->cur;
@@ -742,12 +789,12 @@ static int linearize_free(psba_ctx *h, bool ahead, bool publish) {
   h->coeff_w = h->coeff;
   double *Uo = ahead ? h->U_alt : h->U, *gao = ahead ? h->ga_alt : h->ga;
   ProfScope ps(h, PSBA_K_LINEARIZE);
-  hipLaunchKernelGGL(k_free_linearize<T>, dim3(h->nCamUnits), dim3(64), 0, h->stream, a);
+  hipLaunchKernelGGL((k_free_linearize<T, HELD>), dim3(h->nCamUnits), dim3(64), 0, h->stream, a);
   const long long nfin = (long long)d.nC * (T::CNP * T::CNP + T::CNP);
-  hipLaunchKernelGGL(k_free_finish_cams<T>, dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, h->stream, h->free_upart,
-                     h->free_cuptr, d.nC, h->coeff, h->coeff_g, h->kd_mask, Uo, gao);
-  hipLaunchKernelGGL(k_free_point_sums, dim3((unsigned)((d.nP + 255) / 256)), dim3(256), 0, h->stream, h->free_Be, h->ptr, d.nP,
-                     h->coeff, h->coeff_g, PVo);
+  hipLaunchKernelGGL((k_free_finish_cams<T, HELD>), dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, h->stream,
+                     h->free_upart, h->free_cuptr, d.nC, h->coeff, h->coeff_g, h->kd_mask, a.held_pose, Uo, gao);
+  hipLaunchKernelGGL(k_free_point_sums<HELD>, dim3((unsigned)((d.nP + 255) / 256)), dim3(256), 0, h->stream, h->free_Be, h->ptr,
+                     d.nP, h->coeff, h->coeff_g, a.held_pt, PVo);
   if (h->damp_kind == PSBA_DAMPING_MARQUARDT)  // D of this set, behind the two kernels whose sums it reads
     hipLaunchKernelGGL(k_free_damp_diag<T>, dim3((unsigned)((d.nT + 255) / 256)), dim3(256), 0, h->stream, (const double *)Uo,
                        (const double *)PVo, (const int *)h->kd_rep, (const int *)h->kd_gidx, (const int *)h->kd_gptr,
@@ -770,14 +817,15 @@ static int residual_free(psba_ctx *h, int which) {
   return PSBA_OK;
 }
 
-template <class T>
+template <class T, bool HELD>
 static int max_diag_free(psba_ctx *h) {
+  const unsigned char *hp = h->held_poses, *hq = h->held_pts;
   if (T::CNP == KD_CNP && h->kd_rep)
-    hipLaunchKernelGGL(k_kd_max_diag_groups, dim3(1), dim3(1024), 0, h->stream, h->U, h->PV, h->d.nC, h->d.nP, kd_groups(h),
-                       h->scal + SC_MAXDIAG);
+    hipLaunchKernelGGL(k_kd_max_diag_groups<HELD>, dim3(1), dim3(1024), 0, h->stream, h->U, h->PV, h->d.nC, h->d.nP,
+                       kd_groups(h), hp, hq, h->scal + SC_MAXDIAG);
   else
-    hipLaunchKernelGGL(k_free_max_diag<T>, dim3(1), dim3(1024), 0, h->stream, h->U, h->PV, h->d.nC, h->d.nP, h->kd_mask,
-                       h->scal + SC_MAXDIAG);
+    hipLaunchKernelGGL((k_free_max_diag<T, HELD>), dim3(1), dim3(1024), 0, h->stream, h->U, h->PV, h->d.nC, h->d.nP,
+                       h->kd_mask, hp, hq, h->scal + SC_MAXDIAG);
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }
@@ -828,7 +876,7 @@ static int schur_free(psba_ctx *h, double mu) {
   return PSBA_OK;
 }
 
-template <class T>
+template <class T, bool HELD>
 static int backsub_free(psba_ctx *h, double mu) {
   const Dims &d = h->d;
   FreeBackArgs a;
@@ -841,6 +889,8 @@ static int backsub_free(psba_ctx *h, double mu) {
   a.ga = h->ga;
   a.jidx = h->jidx;
   a.ptr = h->ptr;
+  a.held_pose = h->held_poses;
+  a.held_pt = h->held_pts;
   a.dp = h->dp;
   a.newcams = h->cams[1 - h->cur];
   a.newpts = h->pts[1 - h->cur];
@@ -855,10 +905,10 @@ static int backsub_free(psba_ctx *h, double mu) {
   const int grid = free_grid(d.nP, KD_RED / 4 - 8);
   ProfScope ps(h, PSBA_K_BACKSUB);
   if (T::CNP == KD_CNP && h->kd_rep)
-    hipLaunchKernelGGL(k_kd_backsub_cams_groups, dim3(1), dim3(256), 0, h->stream, a, (const int *)h->kd_rep);
+    hipLaunchKernelGGL(k_kd_backsub_cams_groups<HELD>, dim3(1), dim3(256), 0, h->stream, a, (const int *)h->kd_rep);
   else
-    hipLaunchKernelGGL(k_free_backsub_cams<T>, dim3(1), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(k_free_backsub_pts<T>, dim3(grid), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL((k_free_backsub_cams<T, HELD>), dim3(1), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL((k_free_backsub_pts<T, HELD>), dim3(grid), dim3(256), 0, h->stream, a);
   // set 0 of the SC_NPART partial sets carries the whole sums (k_free_finalize zeroed the others)
   hipLaunchKernelGGL(k_free_sum_columns, dim3(1), dim3(64), 0, h->stream, (const double *)h->free_red,
                      (const double *)h->free_red + 4, grid, 4, h->scal + SC_PART);
@@ -866,12 +916,15 @@ static int backsub_free(psba_ctx *h, double mu) {
   return PSBA_OK;
 }
 
-// one dispatch on the camera block per launcher
+// one dispatch on the camera block per launcher; the launchers whose kernels read the held masks also on has_held
 #define FREE_DISPATCH(fn, ...) (h->cnp == KD_CNP ? fn<FreeKD>(__VA_ARGS__) : fn<FreeK>(__VA_ARGS__))
-int launch_linearize_free(psba_ctx *h, bool ahead, bool publish) { return FREE_DISPATCH(linearize_free, h, ahead, publish); }
+#define FREE_DISPATCH_HELD(fn, ...)                                                                        \
+  (h->cnp == KD_CNP ? (h->has_held ? fn<FreeKD, true>(__VA_ARGS__) : fn<FreeKD, false>(__VA_ARGS__)) \
+                    : (h->has_held ? fn<FreeK, true>(__VA_ARGS__) : fn<FreeK, false>(__VA_ARGS__)))
+int launch_linearize_free(psba_ctx *h, bool ahead, bool publish) { return FREE_DISPATCH_HELD(linearize_free, h, ahead, publish); }
 int launch_residual_free(psba_ctx *h, int which) { return FREE_DISPATCH(residual_free, h, which); }
-int launch_max_diag_free(psba_ctx *h) { return FREE_DISPATCH(max_diag_free, h); }
+int launch_max_diag_free(psba_ctx *h) { return FREE_DISPATCH_HELD(max_diag_free, h); }
 int launch_schur_free(psba_ctx *h, double mu) { return FREE_DISPATCH(schur_free, h, mu); }
-int launch_backsub_free(psba_ctx *h, double mu) { return FREE_DISPATCH(backsub_free, h, mu); }
+int launch_backsub_free(psba_ctx *h, double mu) { return FREE_DISPATCH_HELD(backsub_free, h, mu); }
 
 }  // namespace psba

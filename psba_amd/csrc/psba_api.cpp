@@ -523,6 +523,57 @@ int psba_intrinsics_groups(psba_handle h, int *rep_of_cam, int *n_groups) {
   return PSBA_OK;
 }
 
+// ---- held poses and points of the free-intrinsics route ----
+int psba_set_held(psba_handle h, const unsigned char *held_poses, const unsigned char *held_pts) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp != 6, "free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD); six-parameter blocks "
+                       "are held as a whole by psba_set_fixed");
+  NEED(h, !h->backsub_pending, "a damping try is in flight (psba_backsub_wait first)");
+  const int nC = h->d.nC, nP = h->d.nP;
+  int nhc = 0, nhp = 0;
+  for (int j = 0; held_poses && j < nC; j++) nhc += held_poses[j] ? 1 : 0;
+  for (int i = 0; held_pts && i < nP; i++) nhp += held_pts[i] ? 1 : 0;
+  if (nhc == nC && nhp == nP)
+    return fail(h, PSBA_E_INVALID, "%s: every pose and every point is held (a resection of the intrinsics alone is not supported)",
+                __func__);
+  // a mask without a non-zero entry is no mask.  With one, both masks are staged (the kernels test no pointer) in
+  // buffers of their own and swapped in only when both are on the device, as psba_set_fixed does
+  DevBuf<unsigned char> new_c, new_p;
+  if (nhc || nhp) {
+    std::vector<unsigned char> hc((size_t)nC, 0), hp((size_t)nP, 0);
+    for (int j = 0; held_poses && j < nC; j++) hc[j] = held_poses[j] ? 1 : 0;
+    for (int i = 0; held_pts && i < nP; i++) hp[i] = held_pts[i] ? 1 : 0;
+    auto stage = [&]() -> int {
+      TRY(new_c.alloc(h, (size_t)nC));
+      TRY(new_p.alloc(h, (size_t)nP));
+      PSBA_HIP(h, hipMemcpyAsync(new_c, hc.data(), hc.size(), hipMemcpyHostToDevice, h->stream));
+      PSBA_HIP(h, hipMemcpyAsync(new_p, hp.data(), hp.size(), hipMemcpyHostToDevice, h->stream));
+      return PSBA_OK;
+    };
+    const int rc = stage();
+    const hipError_t e = hipStreamSynchronize(h->stream);  // (the host vectors and a staged buffer outlive the copies)
+    if (rc != PSBA_OK) return rc;
+    PSBA_HIP(h, e);
+  } else {
+    PSBA_HIP(h, hipStreamSynchronize(h->stream));  // nothing queued still reads the old masks
+  }
+  h->held_poses = std::move(new_c);
+  h->held_pts = std::move(new_p);
+  h->n_held_poses = nhc;
+  h->n_held_pts = nhp;
+  h->has_held = nhc > 0 || nhp > 0;
+  lens_changed(h);
+  return PSBA_OK;
+}
+
+int psba_held_counts(psba_handle h, int *n_held_poses, int *n_held_pts) {
+  CHECK_H(h);
+  if (n_held_poses) *n_held_poses = h->n_held_poses;
+  if (n_held_pts) *n_held_pts = h->n_held_pts;
+  return PSBA_OK;
+}
+
 static int d2h(psba_ctx *h, void *dst, const void *src, size_t bytes);
 
 // ---- the damping rule of the free-intrinsics route ----

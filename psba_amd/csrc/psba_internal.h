@@ -307,6 +307,11 @@ struct ProblemState {
   psba::DevBuf<int> kd_gptr;       // [kd_nmg + 1] CSR over kd_gmem of the groups with several members
   psba::DevBuf<int> kd_gmem;       // their members in ascending camera order (the first is the representative)
   int kd_nmg = 0;
+  // held poses and points of this route (psba_set_held): byte masks on the device, both allocated while
+  // either has a non-zero entry (has_held: the HELD kernel instantiations), none otherwise; an upload resets to none
+  psba::DevBuf<unsigned char> held_poses, held_pts;  // [nC], [nP]
+  int n_held_poses = 0, n_held_pts = 0;
+  bool has_held = false;
   // the damping rule of this route (psba_set_damping): N + mu I, or N + mu D with Marquardt's
   // D_k = min(max(N_kk, dmin), dmax).  damp_D [nT] belongs to the current linearization, damp_D_alt to the one queued
   // ahead (psba_accept swaps them with the rest); both are allocated by the first switch to Marquardt

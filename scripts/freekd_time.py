@@ -3,8 +3,9 @@ back-substitution) with camera blocks of 11 (PSBA_CAMERA_FREE_K) and of 16 (PSBA
 free, and the mask of Bundle Adjustment in the Large), on 54camsvarK / 54pts and on the venice-shaped problem.  The
 variants are alternated within one process (one LM run of each per round), so that drift of the machine hits all of
 them alike; both blocks run the kernels of kernels_free.hip.  --seg sweeps the segment length of the S assembly
-(PSBA_FKD_SEG, read at upload; the sweep opens handles of the 16-block only).
-Usage: python scripts/freekd_time.py [--rounds N] [--iters N] [--seg 16,64,256] [--problem p54|venice|both]"""
+(PSBA_FKD_SEG, read at upload; the sweep opens handles of the 16-block only).  --held adds every variant once more
+with the poses of cameras 0 and 1 held (psba_set_held, DESIGN 7i: the same launches and the same products).
+Usage: python scripts/freekd_time.py [--rounds N] [--iters N] [--seg 16,64,256] [--problem p54|venice|both] [--held]"""
 import argparse
 import os
 import sys
@@ -19,7 +20,7 @@ from psba_amd import synth  # noqa: E402
 CLASSES = [("linearize", 0), ("S assembly", 1), ("Cholesky", 2), ("back-subst.", 3)]
 
 
-def open_handle(prob, model, free, seg):
+def open_handle(prob, model, free, seg, held=False):
     if seg:
         os.environ["PSBA_FKD_SEG"] = str(seg)
     else:
@@ -29,6 +30,10 @@ def open_handle(prob, model, free, seg):
     h.upload_problem(prob)
     if model == psba_amd.CAMERA_FREE_KD:
         h.set_intrinsics_mask(free)
+    if held:
+        poses = np.zeros(prob["nC"], dtype=np.uint8)
+        poses[:2] = 1
+        h.set_held(poses, None)
     return h
 
 
@@ -38,6 +43,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--seg", default="")
     ap.add_argument("--problem", default="both")
+    ap.add_argument("--held", action="store_true")
     args = ap.parse_args()
     data = os.path.join(ROOT, "tests", "golden", "data")
     probs = []
@@ -54,7 +60,10 @@ def main():
             tag = f" L={s}" if s else ""
             variants.append((f"FREE_KD all free{tag}", psba_amd.CAMERA_FREE_KD, None, s))
             variants.append((f"FREE_KD f,k1,k2{tag}", psba_amd.CAMERA_FREE_KD, psba_amd.INTRINSICS_BAL, s))
-        handles = [(name, open_handle(prob, model, free, s)) for name, model, free, s in variants]
+        variants = [v + (False,) for v in variants]
+        if args.held:
+            variants = [w for v in variants for w in (v, (v[0] + " held", v[1], v[2], v[3], True))]
+        handles = [(name, open_handle(prob, model, free, s, held)) for name, model, free, s, held in variants]
         ms = {name: [] for name, _ in handles}
         for rnd in range(args.rounds + 1):
             for name, h in handles:
