@@ -222,6 +222,49 @@ int psba_damping(psba_handle h, int *kind, double *dmin, double *dmax);
 int psba_set_held(psba_handle h, const unsigned char *held_poses /* nCams */, const unsigned char *held_pts /* n3Dpts */);
 int psba_held_counts(psba_handle h, int *n_held_poses, int *n_held_pts);
 
+/* ---- Gaussian priors on cameras and points of the free-intrinsics models ----
+ * Between leaving a parameter free and freezing it: a focal length known to a few percent, a principal point near the
+ * image centre, k3..k5 pulled towards zero, a GPS position per camera, surveyed control points with a deviation.
+ * Model.  A camera j may carry a mean m_j [cnp], in the order of the camera block as psba_get_params returns it, and
+ * a symmetric positive semi-definite information matrix L_j [cnp x cnp] (the inverse covariance); a point i n_i [3]
+ * and G_i [3 x 3].  A diagonal L = diag(1 / sigma^2) is the common case; full blocks allow correlated knowledge.  With
+ * d = m - p, the sign convention of e = measured - projected, the cost is
+ *     F = sum_a |e_a|^2 + sum_j d_j^T L_j d_j + sum_i d_i^T G_i d_i
+ * The priors are extra residual rows: psba_residual, psba_begin, new_cost of the try scalars and the costs of
+ * psba_levmar's log and result are all F, and stop_cost tests F.  The rotation coordinates of a block are the local
+ * rotation about the uploaded initrot: a prior with mean 0 on them says "stay near the starting rotation".
+ * Normal equations, with coeff and coeff_g those of psba_linearize and s the sums over the observations:
+ *     U_j[r][c] = coeff (s_rc + L_j[r][c])      g_a,j[r] = coeff_g (s_r + sum_c L_j[r][c] d_j[c])
+ * the inner sum in ascending c, d at the parameter set being linearized (the proposal for psba_linearize_ahead);
+ * points the same with G_i: the six stored entries of V_i, and g_b,i.  psba_max_diag / psba_begin, Marquardt's D, Y, S,
+ * e_a, the back-substitution and gain_den run on the stored U, V, g, prior included.  Under
+ * psba_set_intrinsics_groups the fold sums the members' rows and columns: a shared intrinsic gets the sum of its
+ * members' priors, and psba_get_gradient keeps returning the per-camera g.
+ * Held coordinates (mask, psba_set_held, folded away by the groups): the held column is deleted from the prior rows
+ * too -- row and column of L (G) are dropped from U (V) before the placeholder coeff goes on the diagonal, g, e_a and
+ * dp stay exactly 0 there -- while the gradient of a free coordinate uses the full d, (L d)_free, and the cost always
+ * counts the full quadratic form.  Every exact guarantee of the mask, the groups, the damping and the holds keeps
+ * holding with priors set.
+ * cam_mean [nCams cnp], cam_info [nCams cnp cnp] row-major; pt_mean [n3Dpts 3], pt_info [n3Dpts 9].  The mean and the
+ * information of a kind are both NULL or both given (PSBA_E_INVALID otherwise); four NULLs clear the priors.  A block
+ * whose information is all zero has no prior; psba_prior_counts counts the others (either pointer may be NULL).  If
+ * no block has a prior the handle runs the kernels of one that never called this and produces the same bits.
+ * After psba_upload_problem (a new upload resets to none); PSBA_E_STATE before an upload, while a try is in flight and
+ * on six-parameter camera blocks; PSBA_E_INVALID, naming the first offending camera or point and entry, for a
+ * non-finite entry, a negative diagonal entry and a block that is not symmetric to 1e-12 relative to its largest
+ * entry (the rule of psba_set_obs_covariance; the two halves are averaged).  Positive semi-definiteness beyond that is
+ * the caller's contract: an indefinite block may surface as PSBA_NOT_SPD.  A refused call changes nothing.  Setting
+ * priors discards a linearization queued ahead and invalidates psba_get_damping_diag and psba_get_free_obs_blocks.
+ * psba_set_params / psba_reset_params move the parameters, not the means.  Priors, mask, groups, damping and holds
+ * compose in any order of calls.  No floating-point atomics: every new sum has an order the upload fixes, two runs are
+ * bit-identical.  PARITY UNPINNED, like the models it belongs to.
+ * psba_prior_cost: the two prior sums of F at PSBA_PARAMS_CUR / PSBA_PARAMS_NEW (either pointer may be NULL);
+ * synchronises; PSBA_E_STATE while a try is in flight (it shares the try's reduction scratch). */
+int psba_set_priors(psba_handle h, const double *cam_mean, const double *cam_info, const double *pt_mean,
+                    const double *pt_info);
+int psba_prior_counts(psba_handle h, int *n_cam_priors, int *n_pt_priors);
+int psba_prior_cost(psba_handle h, int which, double *cams_part, double *pts_part);
+
 /* ---- lens distortion and per-observation image covariances --------------------------
  * Model (the same in psba_amd/csrc/camera_model.h and DESIGN.md): P = R'(q) M + t, (x, y) = (Px, Py) / Pz,
  * r2 = x^2 + y^2, kc = (k1, k2, k3, k4, k5) in the Camera Calibration Toolbox order (the column order of the

@@ -163,6 +163,9 @@ SIGNATURES = [
     ("psba_fixed_counts", C.c_int, [_h, _ip, _ip]),
     ("psba_set_held", C.c_int, [_h, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
     ("psba_held_counts", C.c_int, [_h, _ip, _ip]),
+    ("psba_set_priors", C.c_int, [_h, _dp, _dp, _dp, _dp]),
+    ("psba_prior_counts", C.c_int, [_h, _ip, _ip]),
+    ("psba_prior_cost", C.c_int, [_h, C.c_int, _dp, _dp]),
     ("psba_read_problem_ex", C.c_int, [C.c_char_p, C.c_char_p, _dp, C.POINTER(CProblemEx)]),
     ("psba_free_problem_ex", None, [C.POINTER(CProblemEx)]),
     ("psba_convert_bal_kd", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
@@ -615,6 +618,45 @@ class Psba:
         """psba_held_counts -> (held poses, held points)"""
         c, p = C.c_int(), C.c_int()
         self._ck(lib.psba_held_counts(self._h, C.byref(c), C.byref(p)))
+        return c.value, p.value
+
+    def set_priors(self, cam_mean=None, cam_info=None, pt_mean=None, pt_info=None):
+        """psba_set_priors (free-intrinsics models): Gaussian priors, cost += d^T info d with d = mean - parameters.
+        cam_mean [nC, cnp], cam_info [nC, cnp, cnp]; pt_mean [nP, 3], pt_info [nP, 3, 3].  An info array of shape
+        [n, k] is taken as diagonals (1 / sigma^2) and expanded here.  A block whose information is all zero has no
+        prior; the mean and the information of a kind are both None or both given, four Nones clear the priors."""
+        def kind(mean, info, n, k, what):
+            if mean is None and info is None:
+                return None, None
+            if mean is None or info is None:   # (the library's refusal and its text)
+                z = np.zeros(1)
+                return (None, z) if mean is None else (z, None)
+            m = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).reshape(-1))
+            L = np.asarray(info, dtype=np.float64)
+            if n and L.ndim == 2 and L.shape == (n, k):
+                full = np.zeros((n, k, k))
+                full[:, np.arange(k), np.arange(k)] = L
+                L = full
+            L = np.ascontiguousarray(L.reshape(-1))
+            if n and (m.size != n * k or L.size != n * k * k):  # (before an upload n is 0: the library refuses)
+                raise PsbaError(-1, f"set_priors: {m.size} means and {L.size} information entries for {n} {what} of {k}")
+            return m, L
+        cnp = self.camera_block()
+        cm, ci = kind(cam_mean, cam_info, self.nC, cnp, "cameras")
+        pm, pi = kind(pt_mean, pt_info, self.nP, 3, "points")
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_dp)  # noqa: E731
+        self._ck(lib.psba_set_priors(self._h, ptr(cm), ptr(ci), ptr(pm), ptr(pi)))
+
+    def prior_counts(self):
+        """psba_prior_counts -> (cameras with a prior, points with a prior)"""
+        c, p = C.c_int(), C.c_int()
+        self._ck(lib.psba_prior_counts(self._h, C.byref(c), C.byref(p)))
+        return c.value, p.value
+
+    def prior_cost(self, which=PARAMS_CUR):
+        """psba_prior_cost -> (camera priors' part, point priors' part) of the cost at PARAMS_CUR / PARAMS_NEW"""
+        c, p = C.c_double(), C.c_double()
+        self._ck(lib.psba_prior_cost(self._h, which, C.byref(c), C.byref(p)))
         return c.value, p.value
 
     def obs_sq_residuals(self, which=PARAMS_CUR):

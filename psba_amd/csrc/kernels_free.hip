@@ -75,6 +75,43 @@ struct FreeArgs {
   const unsigned char *held_pose, *held_pt;  // read by the HELD instantiations only (last: the other offsets stay)
 };
 
+// ---- Gaussian priors on cameras and points (psba_set_priors) ----
+// A camera j may carry a mean m_j [CNP] (the order of the camera block) and a symmetric positive semi-definite
+// information matrix L_j [CNP x CNP]; a point i n_i [3] and G_i [3 x 3].  With d = m - p (the sign of e = measured -
+// projected) the cost is F = sum |e_a|^2 + sum_j d_j^T L_j d_j + sum_i d_i^T G_i d_i: the priors are extra residual
+// rows, so psba_residual, psba_begin, the try's new cost and psba_levmar all see F.  With s the sums of the kernels:
+//   U_j[r][c] = coeff (s_rc + L_j[r][c])            g_a,j[r] = coeff_g (s_r + sum_c L_j[r][c] d_j[c])
+// the inner sum from zero in ascending c, one add into s; d at the parameter set being linearized (current, or the
+// proposal for the look-ahead set).  Points the same with G_i on the six stored entries of V_i and on g_b,i.  A held
+// coordinate (mask, psba_set_held) has its column deleted from the prior rows too: row and column of L (G) are not
+// added to U (V), g stays exactly 0 there, and the gradient of a free coordinate still takes the whole d, the held
+// deviations included.  A coordinate folded away by the groups is not held here: U carries L and the fold sums the
+// members' rows and columns, so a shared intrinsic gets the sum of its members' priors.  The cost counts the whole
+// quadratic form, q = sum_r d_r (sum_c L[r][c] d[c]), r and c ascending.  Everything behind U, V and g (the maximum of
+// the diagonal, Marquardt's D, Y, S, e_a, the back-substitution, gain_den) reads the stored values and is unchanged.
+// Storage is compacted: an index per block (-1: no prior) into records mean | information of the blocks that have
+// one, and the list of those blocks for the cost kernels.  The kernels that read them are templated on PRIOR; a
+// handle on which no block has a prior runs the false instantiations, which are the code as it was.  With PRIOR all
+// tables are allocated, so no kernel tests a pointer.
+struct FreePriors {
+  const int *cidx, *pidx;      // [nC], [nP] record of the block, -1: none
+  const double *crec, *prec;   // [n][CNP + CNP^2], [n][12]
+};
+template <int N>
+__device__ __forceinline__ double prior_row(const double *rec, const double *x, int r) {  // sum_c L[r][c] (m[c] - x[c])
+  double t = 0.0;
+#pragma unroll
+  for (int c = 0; c < N; c++) t += rec[N + N * r + c] * (rec[c] - x[c]);
+  return t;
+}
+template <int N>
+__device__ __forceinline__ double prior_quad(const double *rec, const double *x) {  // d^T L d, rows ascending
+  double q = 0.0;
+#pragma unroll
+  for (int r = 0; r < N; r++) q += (rec[r] - x[r]) * prior_row<N>(rec, x, r);
+  return q;
+}
+
 template <class T>
 __device__ __forceinline__ void free_load(const FreeArgs &p, int a, int &i, int &j, double *cam, double *q0, double *M,
                                           double2 &m) {
@@ -173,16 +210,26 @@ __global__ __launch_bounds__(64) void k_free_linearize(FreeArgs p) {
 // the units of one camera in unit order: U_j (full CNP x CNP, scaled by coeff, the placeholder coeff on the diagonal
 // of a masked intrinsic and of a held pose coordinate) and g_a,j (scaled by coeff_g).  A camera without observations
 // has zero sums
-template <class T, bool HELD>
+template <class T, bool HELD, bool PRIOR>
 __global__ __launch_bounds__(256) void k_free_finish_cams(const double *upart, const int *cuptr, int nC, double coeff,
                                                           double coeff_g, unsigned mask, const unsigned char *held_pose,
-                                                          double *U, double *ga) {
+                                                          double *U, double *ga, FreePriors pr, const double *cams) {
   constexpr int CNP = T::CNP, UP = CNP * CNP + CNP;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)nC * UP) return;
   const int j = (int)(t / UP), e = (int)(t % UP);
   double s = 0.0;
   for (int u = cuptr[j]; u < cuptr[j + 1]; u++) s += upart[UP * (size_t)u + e];
+  if (PRIOR) {  // (a held row or column of the information matrix is dropped; the gradient takes the whole d)
+    const int k = pr.cidx[j];
+    if (k >= 0) {
+      const double *rec = pr.crec + (size_t)(CNP + CNP * CNP) * k;
+      const bool hp = HELD && held_pose[j];
+      const int r = e < CNP * CNP ? e / CNP : e - CNP * CNP, c = e < CNP * CNP ? e % CNP : r;
+      const bool hr = r < T::NI ? !((mask >> r) & 1u) : hp, hc = c < T::NI ? !((mask >> c) & 1u) : hp;
+      if (!hr && !hc) s += e < CNP * CNP ? rec[CNP + e] : prior_row<CNP>(rec, cams + (size_t)CNP * j, r);
+    }
+  }
   if (e < CNP * CNP) {
     const int r = e / CNP, c = e % CNP;
     bool held = r == c && r < T::NI && !((mask >> r) & 1u);
@@ -195,9 +242,10 @@ __global__ __launch_bounds__(256) void k_free_finish_cams(const double *upart, c
 
 // V_i and g_b,i: thread per point over its contiguous observations, in observation order.  A held point: its B is
 // zero, so the sums are; the diagonal takes the placeholder (V_i = coeff I, g_b,i = 0)
-template <bool HELD>
+template <bool HELD, bool PRIOR>
 __global__ __launch_bounds__(256) void k_free_point_sums(const double *Be, const int *ptr, int nP, double coeff,
-                                                         double coeff_g, const unsigned char *held_pt, double *PV) {
+                                                         double coeff_g, const unsigned char *held_pt, double *PV,
+                                                         FreePriors pr, const double *pts) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nP) return;
   double v[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
@@ -214,6 +262,19 @@ __global__ __launch_bounds__(256) void k_free_point_sums(const double *Be, const
       for (int c = r; c < 3; c++) v[q++] += B[r] * B[c] + B[3 + r] * B[3 + c];
 #pragma unroll
     for (int r = 0; r < 3; r++) g[r] += B[r] * e0 + B[3 + r] * e1;
+  }
+  if (PRIOR) {  // (a held point: the placeholder below overwrites the sums)
+    const int k = pr.pidx[i];
+    if (k >= 0) {
+      const double *rec = pr.prec + 12 * (size_t)k;
+      int q = 0;
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = r; c < 3; c++) v[q++] += rec[3 + 3 * r + c];
+#pragma unroll
+      for (int r = 0; r < 3; r++) g[r] += prior_row<3>(rec, pts + 3 * (size_t)i, r);
+    }
   }
   double *pv = PV + 9 * (size_t)i;
 #pragma unroll
@@ -253,6 +314,24 @@ __global__ __launch_bounds__(64) void k_free_sum_columns(const double *head, con
   double v = head ? head[q] : 0.0;
   for (int r = 0; r < n; r++) v += part[(size_t)ncol * r + q];
   dst[q] = v;
+}
+
+// the prior part of the cost: thread per block that has a prior (list [n], its record rec[idx[list]], its parameters
+// x[N list]), d^T L d per block, per-workgroup partial sums as k_free_residual's (k_free_sum_columns adds them in
+// workgroup order, behind the observations' partials)
+template <int N>
+__global__ __launch_bounds__(256) void k_free_prior_cost(const int *list, const int *idx, const double *rec, const double *x,
+                                                         int n, double *part) {
+  __shared__ double sRed[4];
+  double sum = 0.0;
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
+    const int b = list[t];
+    sum += prior_quad<N>(rec + (size_t)(N + N * N) * idx[b], x + (size_t)N * b);
+  }
+  sum = free_wave_sum(sum);
+  if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((sRed[0] + sRed[1]) + sRed[2]) + sRed[3];
 }
 
 // the largest diagonal entry of U and V over the free parameters (a maximum does not depend on the order)
@@ -472,7 +551,23 @@ struct FreeBackArgs {
   unsigned mask;
   int nA, nP;
   const unsigned char *held_pose, *held_pt;  // read by the HELD instantiations only
+  FreePriors pr;                             // read by the PRIOR instantiations only
 };
+// the camera priors' cost at the proposal, from the newcams this workgroup has just written (behind a barrier): the
+// try's `new cost` slot, thread per coordinate r: d_r (sum_c L[r][c] d[c])
+template <int CNP>
+__device__ __forceinline__ double free_prior_newcost(const FreeBackArgs &p) {
+  __threadfence_block();
+  __syncthreads();
+  double v = 0.0;
+  for (int t = threadIdx.x; t < p.nA; t += blockDim.x) {
+    const int j = t / CNP, r = t % CNP, k = p.pr.cidx[j];
+    if (k < 0) continue;
+    const double *rec = p.pr.crec + (size_t)(CNP + CNP * CNP) * k;
+    v += (rec[r] - p.newcams[t]) * prior_row<CNP>(rec, p.newcams + (size_t)CNP * j, r);
+  }
+  return v;
+}
 __device__ __forceinline__ void free_block_sums4(double *v4, double (*sRed)[4], double *dst) {
 #pragma unroll
   for (int q = 0; q < 4; q++) {
@@ -482,7 +577,7 @@ __device__ __forceinline__ void free_block_sums4(double *v4, double (*sRed)[4], 
   __syncthreads();
   if (threadIdx.x < 4) dst[threadIdx.x] = ((sRed[threadIdx.x][0] + sRed[threadIdx.x][1]) + sRed[threadIdx.x][2]) + sRed[threadIdx.x][3];
 }
-template <class T, bool HELD>
+template <class T, bool HELD, bool PRIOR>
 __global__ __launch_bounds__(256) void k_free_backsub_cams(FreeBackArgs p) {  // one workgroup, launched first: proposal cams
   __shared__ double sRed[4][4];
   double v4[4] = {0.0, 0.0, 0.0, 0.0};  // dp_l2, gain_den, (new cost: the point kernel's), newp_l2
@@ -503,9 +598,10 @@ __global__ __launch_bounds__(256) void k_free_backsub_cams(FreeBackArgs p) {  //
     v4[1] += d * (mud * d + p.ga[t]);
     v4[3] += c * c;
   }
+  if (PRIOR) v4[2] = free_prior_newcost<T::CNP>(p);
   free_block_sums4(v4, sRed, p.red);
 }
-template <class T, bool HELD>
+template <class T, bool HELD, bool PRIOR>
 __global__ __launch_bounds__(256) void k_free_backsub_pts(FreeBackArgs p) {
   constexpr int CNP = T::CNP;
   __shared__ double sRed[4][4];
@@ -562,6 +658,10 @@ __global__ __launch_bounds__(256) void k_free_backsub_pts(FreeBackArgs p) {
       const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
       T::residual(cam, q0, n3, m.x, m.y, r0, r1);
       v4[2] += r0 * r0 + r1 * r1;
+    }
+    if (PRIOR) {  // the point's prior at its proposal, behind its observations
+      const int k = p.pr.pidx[i];
+      if (k >= 0) v4[2] += prior_quad<3>(p.pr.prec + 12 * (size_t)k, n3);
     }
   }
   free_block_sums4(v4, sRed, p.red + 4 * (size_t)(1 + blockIdx.x));
@@ -706,7 +806,7 @@ __global__ __launch_bounds__(1024) void k_kd_max_diag_groups(const double *U, co
 // k_free_backsub_cams with the step expanded: a folded-away entry reads its representative's dp (which the
 // representative's own thread leaves as solved) and writes only its own; dp_l2, mu dp^2 and newp_l2 count a shared
 // parameter once, dp g goes over every entry (sum_all dp g = dp_shared P^T g)
-template <bool HELD>
+template <bool HELD, bool PRIOR>
 __global__ __launch_bounds__(256) void k_kd_backsub_cams_groups(FreeBackArgs p, const int *rep) {
   __shared__ double sRed[4][4];
   double v4[4] = {0.0, 0.0, 0.0, 0.0};
@@ -733,6 +833,7 @@ __global__ __launch_bounds__(256) void k_kd_backsub_cams_groups(FreeBackArgs p, 
       v4[1] += d * p.ga[t];
     }
   }
+  if (PRIOR) v4[2] = free_prior_newcost<KD_CNP>(p);  // (per camera: every member's own prior at the expanded proposal)
   free_block_sums4(v4, sRed, p.red);
 }
 
@@ -772,12 +873,20 @@ static FreeArgs free_args(psba_ctx *h, int set) {
   a.pub_stamp = 0.0;
   return a;
 }
+static FreePriors free_priors(psba_ctx *h) {
+  FreePriors pr;
+  pr.cidx = h->prior_cidx;
+  pr.pidx = h->prior_pidx;
+  pr.crec = h->prior_crec;
+  pr.prec = h->prior_prec;
+  return pr;
+}
 static int free_grid(long long n, int cap) {
   const long long g = (n + 255) / 256;
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-template <class T, bool HELD>
+template <class T, bool HELD, bool PRIOR>
 static int linearize_free(psba_ctx *h, bool ahead, bool publish) {
   const Dims &d = h->d;
   const int set = ahead ? 1 - h->cur : h->cur;
@@ -791,15 +900,45 @@ static int linearize_free(psba_ctx *h, bool ahead, bool publish) {
   ProfScope ps(h, PSBA_K_LINEARIZE);
   hipLaunchKernelGGL((k_free_linearize<T, HELD>), dim3(h->nCamUnits), dim3(64), 0, h->stream, a);
   const long long nfin = (long long)d.nC * (T::CNP * T::CNP + T::CNP);
-  hipLaunchKernelGGL((k_free_finish_cams<T, HELD>), dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, h->stream,
-                     h->free_upart, h->free_cuptr, d.nC, h->coeff, h->coeff_g, h->kd_mask, a.held_pose, Uo, gao);
-  hipLaunchKernelGGL(k_free_point_sums<HELD>, dim3((unsigned)((d.nP + 255) / 256)), dim3(256), 0, h->stream, h->free_Be, h->ptr,
-                     d.nP, h->coeff, h->coeff_g, a.held_pt, PVo);
+  const FreePriors pr = free_priors(h);
+  hipLaunchKernelGGL((k_free_finish_cams<T, HELD, PRIOR>), dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, h->stream,
+                     h->free_upart, h->free_cuptr, d.nC, h->coeff, h->coeff_g, h->kd_mask, a.held_pose, Uo, gao, pr, a.cams);
+  hipLaunchKernelGGL((k_free_point_sums<HELD, PRIOR>), dim3((unsigned)((d.nP + 255) / 256)), dim3(256), 0, h->stream,
+                     h->free_Be, h->ptr, d.nP, h->coeff, h->coeff_g, a.held_pt, PVo, pr, a.pts);
   if (h->damp_kind == PSBA_DAMPING_MARQUARDT)  // D of this set, behind the two kernels whose sums it reads
     hipLaunchKernelGGL(k_free_damp_diag<T>, dim3((unsigned)((d.nT + 255) / 256)), dim3(256), 0, h->stream, (const double *)Uo,
                        (const double *)PVo, (const int *)h->kd_rep, (const int *)h->kd_gidx, (const int *)h->kd_gptr,
                        (const int *)h->kd_gmem, h->kd_mask, h->coeff, d.nA, d.nT, h->damp_dmin, h->damp_dmax,
                        (double *)(ahead ? h->damp_D_alt : h->damp_D));
+  PSBA_HIP(h, hipGetLastError());
+  return PSBA_OK;
+}
+
+// the priors' per-workgroup partial sums at (cams, pts): cameras then points, written to part; returns how many (at
+// most 512), ncam: those of the cameras
+template <class T>
+static int prior_cost_parts(psba_ctx *h, const double *cams, const double *pts, double *part, int *ncam) {
+  const int gc = h->n_cam_priors ? free_grid(h->n_cam_priors, 256) : 0, gp = h->n_pt_priors ? free_grid(h->n_pt_priors, 256) : 0;
+  if (gc)
+    hipLaunchKernelGGL(k_free_prior_cost<T::CNP>, dim3(gc), dim3(256), 0, h->stream, (const int *)h->prior_clist,
+                       (const int *)h->prior_cidx, (const double *)h->prior_crec, cams, h->n_cam_priors, part);
+  if (gp)
+    hipLaunchKernelGGL(k_free_prior_cost<3>, dim3(gp), dim3(256), 0, h->stream, (const int *)h->prior_plist,
+                       (const int *)h->prior_pidx, (const double *)h->prior_prec, pts, h->n_pt_priors, part + gc);
+  if (ncam) *ncam = gc;
+  return gc + gp;
+}
+
+// psba_prior_cost: the two prior sums on their own, out2 (device) = (cameras, points)
+template <class T>
+static int prior_cost_free(psba_ctx *h, int which, double *out2) {
+  const int set = which == PSBA_PARAMS_NEW ? 1 - h->cur : h->cur;
+  int gc = 0;
+  const int rows = prior_cost_parts<T>(h, h->cams[set], h->pts[set], h->free_red, &gc);
+  hipLaunchKernelGGL(k_free_sum_columns, dim3(1), dim3(64), 0, h->stream, (const double *)nullptr, (const double *)h->free_red,
+                     gc, 1, out2);
+  hipLaunchKernelGGL(k_free_sum_columns, dim3(1), dim3(64), 0, h->stream, (const double *)nullptr,
+                     (const double *)h->free_red + gc, rows - gc, 1, out2 + 1);
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }
@@ -811,7 +950,9 @@ static int residual_free(psba_ctx *h, int which) {
   const int grid = free_grid(h->d.nO, 256);
   ProfScope ps(h, PSBA_K_RESIDUAL);
   hipLaunchKernelGGL(k_free_residual<T>, dim3(grid), dim3(256), 0, h->stream, a, h->free_red);
-  hipLaunchKernelGGL(k_free_sum_columns, dim3(1), dim3(64), 0, h->stream, (const double *)nullptr, h->free_red, grid, 1,
+  // F: the observations' partials, then the camera priors', then the point priors' (none without priors)
+  const int rows = grid + prior_cost_parts<T>(h, a.cams, a.pts, h->free_red + grid, nullptr);
+  hipLaunchKernelGGL(k_free_sum_columns, dim3(1), dim3(64), 0, h->stream, (const double *)nullptr, h->free_red, rows, 1,
                      h->scal + SC_COST);
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
@@ -876,7 +1017,7 @@ static int schur_free(psba_ctx *h, double mu) {
   return PSBA_OK;
 }
 
-template <class T, bool HELD>
+template <class T, bool HELD, bool PRIOR>
 static int backsub_free(psba_ctx *h, double mu) {
   const Dims &d = h->d;
   FreeBackArgs a;
@@ -891,6 +1032,7 @@ static int backsub_free(psba_ctx *h, double mu) {
   a.ptr = h->ptr;
   a.held_pose = h->held_poses;
   a.held_pt = h->held_pts;
+  a.pr = free_priors(h);
   a.dp = h->dp;
   a.newcams = h->cams[1 - h->cur];
   a.newpts = h->pts[1 - h->cur];
@@ -905,10 +1047,10 @@ static int backsub_free(psba_ctx *h, double mu) {
   const int grid = free_grid(d.nP, KD_RED / 4 - 8);
   ProfScope ps(h, PSBA_K_BACKSUB);
   if (T::CNP == KD_CNP && h->kd_rep)
-    hipLaunchKernelGGL(k_kd_backsub_cams_groups<HELD>, dim3(1), dim3(256), 0, h->stream, a, (const int *)h->kd_rep);
+    hipLaunchKernelGGL((k_kd_backsub_cams_groups<HELD, PRIOR>), dim3(1), dim3(256), 0, h->stream, a, (const int *)h->kd_rep);
   else
-    hipLaunchKernelGGL((k_free_backsub_cams<T, HELD>), dim3(1), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL((k_free_backsub_pts<T, HELD>), dim3(grid), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL((k_free_backsub_cams<T, HELD, PRIOR>), dim3(1), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL((k_free_backsub_pts<T, HELD, PRIOR>), dim3(grid), dim3(256), 0, h->stream, a);
   // set 0 of the SC_NPART partial sets carries the whole sums (k_free_finalize zeroed the others)
   hipLaunchKernelGGL(k_free_sum_columns, dim3(1), dim3(64), 0, h->stream, (const double *)h->free_red,
                      (const double *)h->free_red + 4, grid, 4, h->scal + SC_PART);
@@ -916,15 +1058,21 @@ static int backsub_free(psba_ctx *h, double mu) {
   return PSBA_OK;
 }
 
-// one dispatch on the camera block per launcher; the launchers whose kernels read the held masks also on has_held
+// one dispatch on the camera block per launcher; the launchers whose kernels read the held masks also on has_held,
+// those whose kernels read the priors also on has_prior
 #define FREE_DISPATCH(fn, ...) (h->cnp == KD_CNP ? fn<FreeKD>(__VA_ARGS__) : fn<FreeK>(__VA_ARGS__))
 #define FREE_DISPATCH_HELD(fn, ...)                                                                        \
   (h->cnp == KD_CNP ? (h->has_held ? fn<FreeKD, true>(__VA_ARGS__) : fn<FreeKD, false>(__VA_ARGS__)) \
                     : (h->has_held ? fn<FreeK, true>(__VA_ARGS__) : fn<FreeK, false>(__VA_ARGS__)))
-int launch_linearize_free(psba_ctx *h, bool ahead, bool publish) { return FREE_DISPATCH_HELD(linearize_free, h, ahead, publish); }
+#define FREE_DISPATCH_HP1(T, fn, ...)                                                                             \
+  (h->has_held ? (h->has_prior ? fn<T, true, true>(__VA_ARGS__) : fn<T, true, false>(__VA_ARGS__)) \
+               : (h->has_prior ? fn<T, false, true>(__VA_ARGS__) : fn<T, false, false>(__VA_ARGS__)))
+#define FREE_DISPATCH_HP(fn, ...) (h->cnp == KD_CNP ? FREE_DISPATCH_HP1(FreeKD, fn, __VA_ARGS__) : FREE_DISPATCH_HP1(FreeK, fn, __VA_ARGS__))
+int launch_linearize_free(psba_ctx *h, bool ahead, bool publish) { return FREE_DISPATCH_HP(linearize_free, h, ahead, publish); }
+int launch_prior_cost_free(psba_ctx *h, int which, double *out2_dev) { return FREE_DISPATCH(prior_cost_free, h, which, out2_dev); }
 int launch_residual_free(psba_ctx *h, int which) { return FREE_DISPATCH(residual_free, h, which); }
 int launch_max_diag_free(psba_ctx *h) { return FREE_DISPATCH_HELD(max_diag_free, h); }
 int launch_schur_free(psba_ctx *h, double mu) { return FREE_DISPATCH(schur_free, h, mu); }
-int launch_backsub_free(psba_ctx *h, double mu) { return FREE_DISPATCH_HELD(backsub_free, h, mu); }
+int launch_backsub_free(psba_ctx *h, double mu) { return FREE_DISPATCH_HP(backsub_free, h, mu); }
 
 }  // namespace psba

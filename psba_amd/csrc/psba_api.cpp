@@ -576,6 +576,128 @@ int psba_held_counts(psba_handle h, int *n_held_poses, int *n_held_pts) {
 
 static int d2h(psba_ctx *h, void *dst, const void *src, size_t bytes);
 
+// ---- Gaussian priors on cameras and points of the free-intrinsics route ----
+// one kind: n blocks of m parameters; checks every block and compacts those whose information is not all zero into
+// idx [n] (-1: none), list and rec [mean (m) | information (m x m), symmetrised]
+static int priors_pack(psba_ctx *h, const char *what, int n, int m, const double *mean, const double *info,
+                       std::vector<int> &idx, std::vector<int> &list, std::vector<double> &rec) {
+  idx.assign((size_t)n, -1);
+  for (int b = 0; mean && b < n; b++) {
+    const double *mu = mean + (size_t)m * b, *L = info + (size_t)m * m * b;
+    double big = 0.0;
+    for (int r = 0; r < m; r++)
+      if (!std::isfinite(mu[r])) return fail(h, PSBA_E_INVALID, "psba_set_priors: mean[%d] of %s %d is not finite", r, what, b);
+    for (int t = 0; t < m * m; t++) {
+      if (!std::isfinite(L[t]))
+        return fail(h, PSBA_E_INVALID, "psba_set_priors: information[%d][%d] of %s %d is not finite", t / m, t % m, what, b);
+      big = std::fmax(big, std::fabs(L[t]));
+    }
+    for (int r = 0; r < m; r++)
+      if (L[m * r + r] < 0.0)
+        return fail(h, PSBA_E_INVALID, "psba_set_priors: information[%d][%d] of %s %d is negative (%.17g)", r, r, what, b,
+                    L[m * r + r]);
+    for (int r = 0; r < m; r++)
+      for (int c = r + 1; c < m; c++)
+        if (std::fabs(L[m * r + c] - L[m * c + r]) > 1e-12 * big)
+          return fail(h, PSBA_E_INVALID, "psba_set_priors: information of %s %d is not symmetric at [%d][%d] (%.17g vs %.17g)",
+                      what, b, r, c, L[m * r + c], L[m * c + r]);
+    if (big == 0.0) continue;  // all zero: no prior
+    idx[b] = (int)list.size();
+    list.push_back(b);
+    rec.insert(rec.end(), mu, mu + m);
+    for (int r = 0; r < m; r++)
+      for (int c = 0; c < m; c++) rec.push_back(0.5 * (L[m * r + c] + L[m * c + r]));
+  }
+  return PSBA_OK;
+}
+
+int psba_set_priors(psba_handle h, const double *cam_mean, const double *cam_info, const double *pt_mean,
+                    const double *pt_info) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp != 6, "psba_set_priors: free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD); "
+                       "six-parameter blocks carry no priors");
+  NEED(h, !h->backsub_pending, "psba_set_priors: a damping try is in flight (psba_backsub_wait first)");
+  if ((cam_mean == nullptr) != (cam_info == nullptr))
+    return fail(h, PSBA_E_INVALID, "psba_set_priors: cam_mean and cam_info are both NULL or both given");
+  if ((pt_mean == nullptr) != (pt_info == nullptr))
+    return fail(h, PSBA_E_INVALID, "psba_set_priors: pt_mean and pt_info are both NULL or both given");
+  const int nC = h->d.nC, nP = h->d.nP, cnp = h->cnp;
+  std::vector<int> cidx, pidx, clist, plist;
+  std::vector<double> crec, prec;
+  TRY(priors_pack(h, "camera", nC, cnp, cam_mean, cam_info, cidx, clist, crec));
+  TRY(priors_pack(h, "point", nP, 3, pt_mean, pt_info, pidx, plist, prec));
+  const int ncp = (int)clist.size(), npp = (int)plist.size();
+  // no block with a prior is no priors.  With one, every table is staged (the kernels test no pointer; a kind without
+  // priors keeps one unused element) in buffers of their own and swapped in only when all are on the device
+  DevBuf<int> d_cidx, d_pidx, d_clist, d_plist;
+  DevBuf<double> d_crec, d_prec;
+  if (ncp || npp) {
+    if (clist.empty()) clist.push_back(0);
+    if (plist.empty()) plist.push_back(0);
+    if (crec.empty()) crec.assign((size_t)cnp + cnp * cnp, 0.0);
+    if (prec.empty()) prec.assign(12, 0.0);
+    auto stage = [&]() -> int {
+      TRY(d_cidx.alloc(h, cidx.size()));
+      TRY(d_pidx.alloc(h, pidx.size()));
+      TRY(d_clist.alloc(h, clist.size()));
+      TRY(d_plist.alloc(h, plist.size()));
+      TRY(d_crec.alloc(h, crec.size()));
+      TRY(d_prec.alloc(h, prec.size()));
+      PSBA_HIP(h, hipMemcpyAsync(d_cidx, cidx.data(), sizeof(int) * cidx.size(), hipMemcpyHostToDevice, h->stream));
+      PSBA_HIP(h, hipMemcpyAsync(d_pidx, pidx.data(), sizeof(int) * pidx.size(), hipMemcpyHostToDevice, h->stream));
+      PSBA_HIP(h, hipMemcpyAsync(d_clist, clist.data(), sizeof(int) * clist.size(), hipMemcpyHostToDevice, h->stream));
+      PSBA_HIP(h, hipMemcpyAsync(d_plist, plist.data(), sizeof(int) * plist.size(), hipMemcpyHostToDevice, h->stream));
+      PSBA_HIP(h, hipMemcpyAsync(d_crec, crec.data(), sizeof(double) * crec.size(), hipMemcpyHostToDevice, h->stream));
+      PSBA_HIP(h, hipMemcpyAsync(d_prec, prec.data(), sizeof(double) * prec.size(), hipMemcpyHostToDevice, h->stream));
+      return PSBA_OK;
+    };
+    const int rc = stage();
+    const hipError_t e = hipStreamSynchronize(h->stream);  // (the host vectors and a staged buffer outlive the copies)
+    if (rc != PSBA_OK) return rc;
+    PSBA_HIP(h, e);
+  } else {
+    PSBA_HIP(h, hipStreamSynchronize(h->stream));  // nothing queued still reads the old tables
+  }
+  h->prior_cidx = std::move(d_cidx);
+  h->prior_pidx = std::move(d_pidx);
+  h->prior_clist = std::move(d_clist);
+  h->prior_plist = std::move(d_plist);
+  h->prior_crec = std::move(d_crec);
+  h->prior_prec = std::move(d_prec);
+  h->n_cam_priors = ncp;
+  h->n_pt_priors = npp;
+  h->has_prior = ncp > 0 || npp > 0;
+  lens_changed(h);
+  return PSBA_OK;
+}
+
+int psba_prior_counts(psba_handle h, int *n_cam_priors, int *n_pt_priors) {
+  CHECK_H(h);
+  if (n_cam_priors) *n_cam_priors = h->n_cam_priors;
+  if (n_pt_priors) *n_pt_priors = h->n_pt_priors;
+  return PSBA_OK;
+}
+
+int psba_prior_cost(psba_handle h, int which, double *cams_part, double *pts_part) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp != 6, "psba_prior_cost: free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)");
+  NEED(h, !h->backsub_pending, "psba_prior_cost: a damping try is in flight (psba_backsub_wait first)");
+  if (which != PSBA_PARAMS_CUR && which != PSBA_PARAMS_NEW) return fail(h, PSBA_E_INVALID, "%s: which = %d", __func__, which);
+  double out[2] = {0.0, 0.0};
+  if (h->has_prior) {
+    if (!h->prior_out) TRY(h->prior_out.alloc(h, 2));
+    TRY(launch_prior_cost_free(h, which, h->prior_out));
+    TRY(d2h(h, out, h->prior_out, sizeof(out)));
+  } else {
+    PSBA_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  if (cams_part) *cams_part = out[0];
+  if (pts_part) *pts_part = out[1];
+  return PSBA_OK;
+}
+
 // ---- the damping rule of the free-intrinsics route ----
 int psba_set_damping(psba_handle h, int kind, double dmin, double dmax) {
   CHECK_H(h);

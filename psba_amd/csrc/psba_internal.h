@@ -312,6 +312,15 @@ struct ProblemState {
   psba::DevBuf<unsigned char> held_poses, held_pts;  // [nC], [nP]
   int n_held_poses = 0, n_held_pts = 0;
   bool has_held = false;
+  // Gaussian priors of this route (psba_set_priors), compacted: the record of each block (-1: no prior),
+  // the records mean | information of the blocks that have one, and the list of those blocks.  All six are allocated
+  // while any block has a prior (has_prior: the PRIOR kernel instantiations), none otherwise; an upload resets to none
+  psba::DevBuf<int> prior_cidx, prior_pidx;      // [nC], [nP]
+  psba::DevBuf<int> prior_clist, prior_plist;    // [n_cam_priors], [n_pt_priors] (at least one element)
+  psba::DevBuf<double> prior_crec, prior_prec;   // [n_cam_priors][cnp + cnp^2], [n_pt_priors][12]
+  psba::DevBuf<double> prior_out;                // [2] psba_prior_cost's device output, allocated on first use
+  int n_cam_priors = 0, n_pt_priors = 0;
+  bool has_prior = false;
   // the damping rule of this route (psba_set_damping): N + mu I, or N + mu D with Marquardt's
   // D_k = min(max(N_kk, dmin), dmax).  damp_D [nT] belongs to the current linearization, damp_D_alt to the one queued
   // ahead (psba_accept swaps them with the rest); both are allocated by the first switch to Marquardt
@@ -457,6 +466,7 @@ int build_blockprod_plan(int nCams, int nObs, const int *iidx, const int *jidx, 
                          BlockProdPlanHost &out);  // blockprod_plan.cpp
 int launch_linearize_free(psba_ctx *h, bool ahead, bool publish);
 int launch_residual_free(psba_ctx *h, int which);
+int launch_prior_cost_free(psba_ctx *h, int which, double *out2_dev);
 int launch_max_diag_free(psba_ctx *h);
 int launch_schur_free(psba_ctx *h, double mu);
 int launch_backsub_free(psba_ctx *h, double mu);

@@ -4,8 +4,12 @@ free, and the mask of Bundle Adjustment in the Large), on 54camsvarK / 54pts and
 variants are alternated within one process (one LM run of each per round), so that drift of the machine hits all of
 them alike; both blocks run the kernels of kernels_free.hip.  --seg sweeps the segment length of the S assembly
 (PSBA_FKD_SEG, read at upload; the sweep opens handles of the 16-block only).  --held adds every variant once more
-with the poses of cameras 0 and 1 held (psba_set_held, DESIGN 7i: the same launches and the same products).
-Usage: python scripts/freekd_time.py [--rounds N] [--iters N] [--seg 16,64,256] [--problem p54|venice|both] [--held]"""
+with the poses of cameras 0 and 1 held (psba_set_held, DESIGN 7i: the same launches and the same products).  --priors
+adds every variant once more with a weak diagonal prior about the start on every camera and on every 16th point
+(psba_set_priors, DESIGN 7j: the PRIOR instantiations of the same launches, two more cost kernels per psba_residual;
+the variant without is the PRIOR = false code).  --problem wide65 is tests/freekd_twin.py's wide_problem(65).
+Usage: python scripts/freekd_time.py [--rounds N] [--iters N] [--seg 16,64,256] [--problem p54|venice|both|wide65]
+       [--held] [--priors]"""
 import argparse
 import os
 import sys
@@ -20,7 +24,7 @@ from psba_amd import synth  # noqa: E402
 CLASSES = [("linearize", 0), ("S assembly", 1), ("Cholesky", 2), ("back-subst.", 3)]
 
 
-def open_handle(prob, model, free, seg, held=False):
+def open_handle(prob, model, free, seg, held=False, priors=False):
     if seg:
         os.environ["PSBA_FKD_SEG"] = str(seg)
     else:
@@ -34,6 +38,11 @@ def open_handle(prob, model, free, seg, held=False):
         poses = np.zeros(prob["nC"], dtype=np.uint8)
         poses[:2] = 1
         h.set_held(poses, None)
+    if priors:
+        cams, pts = h.get_params(0)
+        pt_info = np.zeros(pts.shape)
+        pt_info[::16] = 1e-6
+        h.set_priors(cams, np.full(cams.shape, 1e-6), pts, pt_info)
     return h
 
 
@@ -44,6 +53,7 @@ def main():
     ap.add_argument("--seg", default="")
     ap.add_argument("--problem", default="both")
     ap.add_argument("--held", action="store_true")
+    ap.add_argument("--priors", action="store_true")
     args = ap.parse_args()
     data = os.path.join(ROOT, "tests", "golden", "data")
     probs = []
@@ -51,6 +61,10 @@ def main():
         probs.append(("54camsvarK", psba_amd.read_problem(os.path.join(data, "54camsvarK.txt"), os.path.join(data, "54pts.txt"))))
     if args.problem in ("venice", "both"):
         probs.append(("venice-shaped", synth.venice_shaped()))
+    if args.problem == "wide65":
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from freekd_twin import wide_problem
+        probs.append(("wide_problem(65)", wide_problem(65)))
     segs = [int(s) for s in args.seg.split(",") if s] or [0]
     for pname, prob in probs:
         print(f"{pname}: {prob['nC']} cameras, {prob['nP']} points, {prob['nO']} observations; {args.iters} LM iterations "
@@ -63,7 +77,10 @@ def main():
         variants = [v + (False,) for v in variants]
         if args.held:
             variants = [w for v in variants for w in (v, (v[0] + " held", v[1], v[2], v[3], True))]
-        handles = [(name, open_handle(prob, model, free, s, held)) for name, model, free, s, held in variants]
+        variants = [v + (False,) for v in variants]
+        if args.priors:
+            variants = [w for v in variants for w in (v, (v[0] + " priors",) + v[1:5] + (True,))]
+        handles = [(name, open_handle(prob, model, free, s, held, pri)) for name, model, free, s, held, pri in variants]
         ms = {name: [] for name, _ in handles}
         for rnd in range(args.rounds + 1):
             for name, h in handles:
@@ -81,7 +98,7 @@ def main():
                 t, n = h.profile_get(ck)
                 parts.append(f"{cn} {1e3 * t / max(res.tries, 1):.1f} us")
             h.profile_enable(False)
-            print(f"  {name:26s} ms/try median {np.median(ms[name]):.4f} (min {min(ms[name]):.4f} max {max(ms[name]):.4f}); "
+            print(f"  {name:33s} ms/try median {np.median(ms[name]):.4f} (min {min(ms[name]):.4f} max {max(ms[name]):.4f}); "
                   f"per try: " + "  ".join(parts) + f"  [{res.tries} tries, cost {res.init_err:.4e} -> {res.final_err:.4e}]",
                   flush=True)
             h.close()
