@@ -5,7 +5,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["psba_api.cpp", "schur_plan.cpp", "lm_loop.cpp", "tr_loop.cpp", "sba_io.cpp", "kernels_linearize.hip",
+SOURCES = ["psba_api.cpp", "problem_options.cpp", "schur_plan.cpp", "lm_loop.cpp", "tr_loop.cpp", "sba_io.cpp", "kernels_linearize.hip",
            "kernels_tr.hip",
            "kernels_schur.hip", "kernels_free.hip", "blockprod_plan.cpp", "kernels_chol.hip", "kernels_pcg.hip", "kernels_chol_graph.hip", "kernels_backsub.hip",
            "kernels_cov.hip"]
@@ -14,7 +14,7 @@ EXPERIMENTS = bool(os.environ.get("PSBA_BUILD_EXPERIMENTS"))
 if EXPERIMENTS:
     SOURCES += ["kernels_schur_ring.hip", "schur_ring_plan.cpp", "kernels_schur_modes.hip"]
 OUT = os.path.join(HERE, "libpsba_hip_exp.so" if EXPERIMENTS else "libpsba_hip.so")
-HEADERS = ["psba_internal.h", "dev_buf.h", "camera_model.h", "chol_factor32.h", "schur_common.h", "schur_lds_args.h", os.path.join("..", "..", "include", "psba_hip.h")]
+HEADERS = ["psba_internal.h", "api_common.h", "dev_buf.h", "camera_model.h", "chol_factor32.h", "schur_common.h", "schur_lds_args.h", os.path.join("..", "..", "include", "psba_hip.h")]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-result", "-x", "hip"] + (["-DPSBA_BUILD_EXPERIMENTS"] if EXPERIMENTS else [])

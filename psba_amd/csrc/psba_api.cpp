@@ -12,8 +12,8 @@
 #include <new>
 #include <vector>
 
+#include "api_common.h"
 #include "camera_model.h"
-#include "psba_internal.h"
 
 using namespace psba;
 
@@ -56,46 +56,6 @@ ProfScope::~ProfScope() {
   if (idx >= 0) (void)hipEventRecord(h->spans[idx].b, h->stream);
 }
 
-}  // namespace psba
-
-// every entry point makes the handle's device current: a host may keep handles on several GPUs
-// in one process, or call from a thread whose current device is another one
-// With a communicator the try's scalar all-reduce and its copy to the host run on a side stream
-// (psba_backsub_async), beside the linearization that is queued ahead; whatever else is queued on
-// the main stream before psba_backsub_wait has returned must come after them.
-#define CHECK_H_NOJOIN(h)                 \
-  do {                                    \
-    if (!(h)) return PSBA_E_INVALID;      \
-    (void)hipSetDevice((h)->device);      \
-  } while (0)
-#define CHECK_H(h)                                                         \
-  do {                                                                     \
-    CHECK_H_NOJOIN(h);                                                     \
-    if ((h)->scal_side) {                                                  \
-      (void)hipStreamWaitEvent((h)->stream, (h)->scal_event, 0);           \
-      (h)->scal_side = false;                                              \
-    }                                                                      \
-  } while (0)
-#define NEED(h, cond, what)                                             \
-  do {                                                                  \
-    if (!(cond)) return fail((h), PSBA_E_STATE, "%s: %s", __func__, what); \
-  } while (0)
-// the verbs that exist for the six-parameter camera block only
-#define SIX_ONLY "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)"
-#define NEED_SIX(h) NEED(h, (h)->cnp == 6, SIX_ONLY)
-#define RCCL(h, call)                                                                   \
-  do {                                                                                  \
-    ncclResult_t r__ = (call);                                                          \
-    if (r__ != ncclSuccess)                                                             \
-      return fail((h), PSBA_E_RCCL, "%s failed: %s", #call, ncclGetErrorString(r__));   \
-  } while (0)
-#define TRY(expr)                 \
-  do {                            \
-    int rc__ = (expr);            \
-    if (rc__ < 0) return rc__;    \
-  } while (0)
-
-namespace psba {
 int alloc_bytes(psba_ctx *h, void **p, size_t bytes, bool pinned) {
   *p = nullptr;
   if (pinned) {
@@ -110,6 +70,14 @@ int alloc_bytes(psba_ctx *h, void **p, size_t bytes, bool pinned) {
   }
   return PSBA_OK;
 }
+
+int d2h(psba_ctx *h, void *dst, const void *src, size_t bytes) {
+  if (!dst) return PSBA_OK;
+  PSBA_HIP(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+  PSBA_HIP(h, hipStreamSynchronize(h->stream));
+  return PSBA_OK;
+}
+
 }  // namespace psba
 
 // v on the device, in a buffer of its own (the blocking copy goes through the null stream: psba_upload_problem ends
@@ -206,544 +174,6 @@ int psba_schur_path(psba_handle h, int *path) {
   NEED(h, h->uploaded, "no problem uploaded");
   if (path) *path = h->cnp != 6 ? 5 : h->solver == PSBA_SOLVER_PCG ? 4 : getenv("PSBA_SCHUR_ATOMIC") ? 2 : h->ring_nWg > 0 ? 3 : h->nGroups > 0 ? 0 : 1;
   return PSBA_OK;
-}
-
-int psba_set_camera_model(psba_handle h, int model) {
-  CHECK_H(h);
-  if (model != PSBA_CAMERA_FIXED_K && model != PSBA_CAMERA_FREE_K && model != PSBA_CAMERA_FREE_KD)
-    return fail(h, PSBA_E_INVALID, "unknown camera model %d", model);
-  NEED(h, !h->uploaded, "psba_set_camera_model before psba_upload_problem (every buffer depends on the camera block)");
-  h->cnp = model == PSBA_CAMERA_FREE_KD ? KD_CNP : model == PSBA_CAMERA_FREE_K ? FK_CNP : 6;
-  return PSBA_OK;
-}
-
-// ---- lens model (camera_model.h) -------------------------------------------------------------
-static int lens_settable(psba_ctx *h, const char *what) {
-  if (!h->uploaded) return fail(h, PSBA_E_STATE, "%s: no problem uploaded", what);
-  if (h->cnp != 6)
-    return fail(h, PSBA_E_STATE, "%s: the fixed-intrinsics camera block only (not PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)", what);
-  if (h->backsub_pending) return fail(h, PSBA_E_STATE, "%s: a damping try is in flight (psba_backsub_wait first)", what);
-  return PSBA_OK;
-}
-
-// the model changed: a linearization queued ahead (or kept for the next psba_linearize) was made with the old one
-static void lens_changed(psba_ctx *h) {
-  h->ahead = false;
-  h->lin_is_ahead = false;
-  h->linearized = h->assembled = h->solved = false;
-  h->free_obs = false;
-  h->damp_ok = false;
-  h->cov_ok = h->cov_pts_ok = false;
-}
-
-static int groups_split(psba_ctx *h, const char *who, const std::vector<int> &rep, const double *v, int stride, int ncols,
-                        int col0);
-
-// PSBA_CAMERA_FREE_KD: kc is part of the camera block -- the starting values go into columns 5..9 of the current
-// parameters and of the copy psba_reset_params restores
-static int set_start_distortion(psba_ctx *h, const double *kc) {
-  if (h->backsub_pending) return fail(h, PSBA_E_STATE, "psba_set_distortion: a damping try is in flight (psba_backsub_wait first)");
-  const int nC = h->d.nC;
-  for (int t = 0; kc && t < 5 * nC; t++)
-    if (!std::isfinite(kc[t])) return fail(h, PSBA_E_INVALID, "psba_set_distortion: kc[%d] of camera %d is not finite", t % 5, t / 5);
-  if (kc && !h->kd_rep_h.empty()) TRY(groups_split(h, "psba_set_distortion", h->kd_rep_h, kc, 5, 5, 5));
-  std::vector<double> c((size_t)h->d.nA);
-  double *dst[2] = {h->cams[h->cur], h->params0};
-  for (int k = 0; k < 2; k++) {
-    PSBA_HIP(h, hipMemcpyAsync(c.data(), dst[k], sizeof(double) * c.size(), hipMemcpyDeviceToHost, h->stream));
-    PSBA_HIP(h, hipStreamSynchronize(h->stream));
-    for (int j = 0; j < nC; j++)
-      for (int q = 0; q < 5; q++) c[(size_t)KD_CNP * j + 5 + q] = kc ? kc[5 * j + q] : 0.0;
-    PSBA_HIP(h, hipMemcpyAsync(dst[k], c.data(), sizeof(double) * c.size(), hipMemcpyHostToDevice, h->stream));
-    PSBA_HIP(h, hipStreamSynchronize(h->stream));
-  }
-  h->ahead = h->lin_is_ahead = false;
-  h->linearized = h->assembled = h->solved = h->backsubbed = false;
-  h->free_obs = false;
-  h->damp_ok = false;
-  h->cov_ok = h->cov_pts_ok = false;
-  return PSBA_OK;
-}
-
-int psba_set_distortion(psba_handle h, const double *kc) {
-  CHECK_H(h);
-  if (h->uploaded && h->cnp == KD_CNP) return set_start_distortion(h, kc);
-  TRY(lens_settable(h, __func__));
-  if (!kc) {
-    h->lens_kc.reset();
-    h->lens &= ~LENS_DIST;
-  } else {
-    for (int t = 0; t < 5 * h->d.nC; t++)
-      if (!std::isfinite(kc[t])) return fail(h, PSBA_E_INVALID, "%s: kc[%d] of camera %d is not finite", __func__, t % 5, t / 5);
-    if (!h->lens_kc) TRY(h->lens_kc.alloc(h, (size_t)5 * h->d.nC));
-    PSBA_HIP(h, hipMemcpyAsync(h->lens_kc, kc, sizeof(double) * 5 * (size_t)h->d.nC, hipMemcpyHostToDevice, h->stream));
-    PSBA_HIP(h, hipStreamSynchronize(h->stream));
-    h->lens |= LENS_DIST;
-  }
-  lens_changed(h);
-  return PSBA_OK;
-}
-
-int psba_set_obs_covariance(psba_handle h, const double *cov) {
-  CHECK_H(h);
-  TRY(lens_settable(h, __func__));
-  if (!cov) {
-    h->lens_w.reset();
-    h->lens &= ~LENS_COV;
-    lens_changed(h);
-    return PSBA_OK;
-  }
-  // Sigma = [p q; q r] -> Sigma^-1 = [r -q; -q p] / det = L^T L, L = [l00 l01; 0 l11]
-  std::vector<double> w((size_t)LENS_WSTRIDE * h->d.nO, 0.0);
-  for (int a = 0; a < h->d.nO; a++) {
-    const double *c = cov + 4 * (size_t)a;
-    const double p = c[0], r = c[3];
-    const double big = std::fmax(std::fmax(std::fabs(c[0]), std::fabs(c[1])), std::fmax(std::fabs(c[2]), std::fabs(c[3])));
-    if (!(std::isfinite(p) && std::isfinite(c[1]) && std::isfinite(c[2]) && std::isfinite(r)))
-      return fail(h, PSBA_E_INVALID, "%s: covariance of observation %d is not finite", __func__, a);
-    if (std::fabs(c[1] - c[2]) > 1e-12 * big)
-      return fail(h, PSBA_E_INVALID, "%s: covariance of observation %d is not symmetric (%.17g vs %.17g)", __func__, a, c[1], c[2]);
-    const double q = 0.5 * (c[1] + c[2]);
-    const double det = p * r - q * q;
-    if (!(p > 0.0) || !(det > 0.0))
-      return fail(h, PSBA_E_INVALID, "%s: covariance of observation %d is not positive definite", __func__, a);
-    const double i00 = r / det, i01 = -q / det, i11 = p / det;
-    const double l00 = std::sqrt(i00), l01 = i01 / l00;
-    const double t = i11 - l01 * l01;
-    if (!(t > 0.0)) return fail(h, PSBA_E_INVALID, "%s: covariance of observation %d is not positive definite", __func__, a);
-    w[(size_t)LENS_WSTRIDE * a] = l00;
-    w[(size_t)LENS_WSTRIDE * a + 1] = l01;
-    w[(size_t)LENS_WSTRIDE * a + 2] = std::sqrt(t);
-  }
-  if (!h->lens_w) TRY(h->lens_w.alloc(h, w.size()));
-  PSBA_HIP(h, hipMemcpyAsync(h->lens_w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, h->stream));
-  PSBA_HIP(h, hipStreamSynchronize(h->stream));
-  h->lens |= LENS_COV;
-  lens_changed(h);
-  return PSBA_OK;
-}
-
-int psba_lens_model(psba_handle h, int *has_distortion, int *has_covariance) {
-  CHECK_H(h);
-  if (has_distortion) *has_distortion = ((h->lens & LENS_DIST) || h->cnp == KD_CNP) ? 1 : 0;
-  if (has_covariance) *has_covariance = (h->lens & LENS_COV) ? 1 : 0;
-  return PSBA_OK;
-}
-
-// ---- robust loss (camera_model.h RobustLoss) ----
-static_assert(PSBA_LOSS_NONE == LOSS_NONE && PSBA_LOSS_HUBER == LOSS_HUBER && PSBA_LOSS_CAUCHY == LOSS_CAUCHY &&
-                  PSBA_LOSS_SOFT_L1 == LOSS_SOFT_L1,
-              "loss kinds of the C ABI and the kernels");
-
-int psba_set_robust_loss(psba_handle h, int kind, double scale) {
-  CHECK_H(h);
-  TRY(lens_settable(h, __func__));
-  if (kind < PSBA_LOSS_NONE || kind > PSBA_LOSS_SOFT_L1) return fail(h, PSBA_E_INVALID, "%s: unknown loss kind %d", __func__, kind);
-  if (!(std::isfinite(scale) && scale > 0.0))
-    return fail(h, PSBA_E_INVALID, "%s: the scale must be finite and > 0 (got %.17g)", __func__, scale);
-  h->loss_kind = kind;
-  h->loss_c = scale;
-  if (kind == PSBA_LOSS_NONE)
-    h->lens &= ~LENS_ROBUST;  // the plain instantiations: bit for bit what a handle that never set a loss computes
-  else
-    h->lens |= LENS_ROBUST;
-  lens_changed(h);
-  return PSBA_OK;
-}
-
-int psba_robust_loss(psba_handle h, int *kind, double *scale) {
-  CHECK_H(h);
-  if (kind) *kind = h->loss_kind;
-  if (scale) *scale = h->loss_c;
-  return PSBA_OK;
-}
-
-// ---- fixed parameter blocks (camera_model.h FixedMask) ----
-int psba_set_fixed(psba_handle h, const unsigned char *fixed_cams, const unsigned char *fixed_pts) {
-  CHECK_H(h);
-  TRY(lens_settable(h, __func__));
-  const int nC = h->d.nC, nP = h->d.nP;
-  int nfc = 0, nfp = 0;
-  for (int j = 0; fixed_cams && j < nC; j++) nfc += fixed_cams[j] ? 1 : 0;
-  for (int i = 0; fixed_pts && i < nP; i++) nfp += fixed_pts[i] ? 1 : 0;
-  // (under a rank layout this rank sees only its own points: the other ranks' may be free)
-  if (h->nranks == 1 && nfc == nC && nfp == nP)
-    return fail(h, PSBA_E_INVALID, "%s: every camera and every point is fixed: no free parameter is left", __func__);
-  // a mask without a non-zero entry is no mask.  The new masks are staged in buffers of their own and swapped in
-  // only when both are on the device: an allocation or a copy that fails leaves the handle as it was
-  std::vector<unsigned char> fc, fp;
-  DevBuf<unsigned char> new_c, new_p;
-  auto stage = [&]() -> int {
-    if (nfc) {
-      fc.resize((size_t)nC);
-      for (int j = 0; j < nC; j++) fc[j] = fixed_cams[j] ? 1 : 0;
-      TRY(new_c.alloc(h, (size_t)nC));
-      PSBA_HIP(h, hipMemcpyAsync(new_c, fc.data(), fc.size(), hipMemcpyHostToDevice, h->stream));
-    }
-    if (nfp) {
-      fp.resize((size_t)nP);
-      for (int i = 0; i < nP; i++) fp[i] = fixed_pts[i] ? 1 : 0;
-      TRY(new_p.alloc(h, (size_t)nP));
-      PSBA_HIP(h, hipMemcpyAsync(new_p, fp.data(), fp.size(), hipMemcpyHostToDevice, h->stream));
-    }
-    PSBA_HIP(h, hipStreamSynchronize(h->stream));  // (also: nothing queued still reads the old masks)
-    return PSBA_OK;
-  };
-  const int rc = stage();
-  if (rc != PSBA_OK) {
-    (void)hipStreamSynchronize(h->stream);  // (before the staged buffers go)
-    return rc;
-  }
-  h->fix_cams = std::move(new_c);
-  h->fix_pts = std::move(new_p);
-  h->n_fix_cams = nfc;
-  h->n_fix_pts = nfp;
-  h->has_fixed = nfc > 0 || nfp > 0;  // none: the plain kernel instantiations, as on a handle that never set a mask
-  h->struct_only = nfc == nC;
-  h->try_shortcut = false;
-  lens_changed(h);
-  return PSBA_OK;
-}
-
-int psba_fixed_counts(psba_handle h, int *n_fixed_cams, int *n_fixed_pts) {
-  CHECK_H(h);
-  if (n_fixed_cams) *n_fixed_cams = h->n_fix_cams;
-  if (n_fixed_pts) *n_fixed_pts = h->n_fix_pts;
-  return PSBA_OK;
-}
-
-// ---- per-parameter mask of the ten intrinsics (PSBA_CAMERA_FREE_KD) ----
-int psba_set_intrinsics_mask(psba_handle h, const unsigned char *free10) {
-  CHECK_H(h);
-  NEED(h, h->uploaded, "no problem uploaded");
-  NEED(h, h->cnp == KD_CNP, "psba_set_intrinsics_mask: PSBA_CAMERA_FREE_KD only");
-  NEED(h, !h->backsub_pending, "psba_set_intrinsics_mask: a damping try is in flight (psba_backsub_wait first)");
-  unsigned m = 0;
-  for (int k = 0; k < 10; k++) m |= (!free10 || free10[k]) ? 1u << k : 0u;
-  h->kd_mask = m;
-  lens_changed(h);
-  return PSBA_OK;
-}
-
-int psba_intrinsics_mask(psba_handle h, unsigned char *out10) {
-  CHECK_H(h);
-  NEED(h, h->uploaded, "no problem uploaded");
-  NEED(h, h->cnp == KD_CNP, "psba_intrinsics_mask: PSBA_CAMERA_FREE_KD only");
-  for (int k = 0; out10 && k < 10; k++) out10[k] = (h->kd_mask >> k) & 1u;
-  return PSBA_OK;
-}
-
-// ---- intrinsics shared between cameras (PSBA_CAMERA_FREE_KD) ----
-// members of a group hold bit-identical intrinsics: v[stride j + k], k < ncols, against the representative's; the
-// message counts columns from col0 (the camera block's numbering)
-static int groups_split(psba_ctx *h, const char *who, const std::vector<int> &rep, const double *v, int stride, int ncols,
-                        int col0) {
-  for (int j = 0; j < (int)rep.size(); j++)
-    for (int k = 0; rep[j] != j && k < ncols; k++)
-      if (memcmp(v + (size_t)stride * j + k, v + (size_t)stride * rep[j] + k, sizeof(double)) != 0)
-        return fail(h, PSBA_E_INVALID, "%s: camera %d differs from camera %d, the representative of its group, in column %d "
-                    "(%.17g against %.17g): members of a group hold bit-identical intrinsics",
-                    who, j, rep[j], col0 + k, v[(size_t)stride * j + k], v[(size_t)stride * rep[j] + k]);
-  return PSBA_OK;
-}
-
-int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam) {
-  CHECK_H(h);
-  NEED(h, h->uploaded, "no problem uploaded");
-  NEED(h, h->cnp == KD_CNP, "psba_set_intrinsics_groups: PSBA_CAMERA_FREE_KD only");
-  NEED(h, !h->backsub_pending, "psba_set_intrinsics_groups: a damping try is in flight (psba_backsub_wait first)");
-  const int nC = h->d.nC;
-  // the representative of a label is the first camera that carries it
-  std::vector<int> rep((size_t)nC), order((size_t)nC);
-  for (int j = 0; j < nC; j++) order[j] = j;
-  if (group_of_cam)
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return group_of_cam[a] < group_of_cam[b]; });
-  int ngroups = 0;
-  for (int t = 0; t < nC; t++) {
-    const bool first = !group_of_cam || t == 0 || group_of_cam[order[t]] != group_of_cam[order[t - 1]];
-    rep[order[t]] = first ? order[t] : rep[order[t - 1]];
-    ngroups += first ? 1 : 0;
-  }
-  std::vector<int> gidx((size_t)nC, -1), gptr(1, 0), gmem;
-  DevBuf<int> d_rep, d_gidx, d_gptr, d_gmem;
-  if (ngroups < nC) {  // (every camera alone is no grouping: the ungrouped launches)
-    std::vector<double> c((size_t)h->d.nA);
-    const double *src[2] = {h->cams[h->cur], h->params0};
-    const char *who[2] = {"psba_set_intrinsics_groups (current parameters)", "psba_set_intrinsics_groups (the psba_reset_params copy)"};
-    for (int k = 0; k < 2; k++) {
-      PSBA_HIP(h, hipMemcpyAsync(c.data(), src[k], sizeof(double) * c.size(), hipMemcpyDeviceToHost, h->stream));
-      PSBA_HIP(h, hipStreamSynchronize(h->stream));
-      TRY(groups_split(h, who[k], rep, c.data(), KD_CNP, 10, 0));
-    }
-    std::vector<int> count((size_t)nC, 0);
-    for (int j = 0; j < nC; j++) count[rep[j]]++;
-    for (int j = 0; j < nC; j++)  // groups in the order of their representatives, members ascending
-      if (rep[j] == j && count[j] > 1) {
-        for (int m = j; m < nC; m++)
-          if (rep[m] == j) {
-            gidx[m] = (int)gptr.size() - 1;
-            gmem.push_back(m);
-          }
-        gptr.push_back((int)gmem.size());
-      }
-    // staged in buffers of their own and swapped in when all are on the device (as psba_set_fixed does)
-    auto stage = [&](DevBuf<int> &dst, const std::vector<int> &v) -> int {
-      TRY(dst.alloc(h, v.size()));
-      PSBA_HIP(h, hipMemcpyAsync(dst, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice, h->stream));
-      return PSBA_OK;
-    };
-    int rc = stage(d_rep, rep);
-    if (rc == PSBA_OK) rc = stage(d_gidx, gidx);
-    if (rc == PSBA_OK) rc = stage(d_gptr, gptr);
-    if (rc == PSBA_OK) rc = stage(d_gmem, gmem);
-    const hipError_t e = hipStreamSynchronize(h->stream);  // (also before a staged buffer goes)
-    if (rc != PSBA_OK) return rc;
-    PSBA_HIP(h, e);
-  } else {
-    PSBA_HIP(h, hipStreamSynchronize(h->stream));  // nothing queued still reads the old tables
-    rep.clear();
-  }
-  h->kd_rep_h = std::move(rep);
-  h->kd_ngroups = h->kd_rep_h.empty() ? 0 : ngroups;
-  h->kd_nmg = (int)gptr.size() - 1;
-  h->kd_rep = std::move(d_rep);
-  h->kd_gidx = std::move(d_gidx);
-  h->kd_gptr = std::move(d_gptr);
-  h->kd_gmem = std::move(d_gmem);
-  lens_changed(h);
-  return PSBA_OK;
-}
-
-int psba_intrinsics_groups(psba_handle h, int *rep_of_cam, int *n_groups) {
-  CHECK_H(h);
-  NEED(h, h->uploaded, "no problem uploaded");
-  NEED(h, h->cnp == KD_CNP, "psba_intrinsics_groups: PSBA_CAMERA_FREE_KD only");
-  for (int j = 0; rep_of_cam && j < h->d.nC; j++) rep_of_cam[j] = h->kd_rep_h.empty() ? j : h->kd_rep_h[j];
-  if (n_groups) *n_groups = h->kd_rep_h.empty() ? h->d.nC : h->kd_ngroups;
-  return PSBA_OK;
-}
-
-// ---- held poses and points of the free-intrinsics route ----
-int psba_set_held(psba_handle h, const unsigned char *held_poses, const unsigned char *held_pts) {
-  CHECK_H(h);
-  NEED(h, h->uploaded, "no problem uploaded");
-  NEED(h, h->cnp != 6, "free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD); six-parameter blocks "
-                       "are held as a whole by psba_set_fixed");
-  NEED(h, !h->backsub_pending, "a damping try is in flight (psba_backsub_wait first)");
-  const int nC = h->d.nC, nP = h->d.nP;
-  int nhc = 0, nhp = 0;
-  for (int j = 0; held_poses && j < nC; j++) nhc += held_poses[j] ? 1 : 0;
-  for (int i = 0; held_pts && i < nP; i++) nhp += held_pts[i] ? 1 : 0;
-  if (nhc == nC && nhp == nP)
-    return fail(h, PSBA_E_INVALID, "%s: every pose and every point is held (a resection of the intrinsics alone is not supported)",
-                __func__);
-  // a mask without a non-zero entry is no mask.  With one, both masks are staged (the kernels test no pointer) in
-  // buffers of their own and swapped in only when both are on the device, as psba_set_fixed does
-  DevBuf<unsigned char> new_c, new_p;
-  if (nhc || nhp) {
-    std::vector<unsigned char> hc((size_t)nC, 0), hp((size_t)nP, 0);
-    for (int j = 0; held_poses && j < nC; j++) hc[j] = held_poses[j] ? 1 : 0;
-    for (int i = 0; held_pts && i < nP; i++) hp[i] = held_pts[i] ? 1 : 0;
-    auto stage = [&]() -> int {
-      TRY(new_c.alloc(h, (size_t)nC));
-      TRY(new_p.alloc(h, (size_t)nP));
-      PSBA_HIP(h, hipMemcpyAsync(new_c, hc.data(), hc.size(), hipMemcpyHostToDevice, h->stream));
-      PSBA_HIP(h, hipMemcpyAsync(new_p, hp.data(), hp.size(), hipMemcpyHostToDevice, h->stream));
-      return PSBA_OK;
-    };
-    const int rc = stage();
-    const hipError_t e = hipStreamSynchronize(h->stream);  // (the host vectors and a staged buffer outlive the copies)
-    if (rc != PSBA_OK) return rc;
-    PSBA_HIP(h, e);
-  } else {
-    PSBA_HIP(h, hipStreamSynchronize(h->stream));  // nothing queued still reads the old masks
-  }
-  h->held_poses = std::move(new_c);
-  h->held_pts = std::move(new_p);
-  h->n_held_poses = nhc;
-  h->n_held_pts = nhp;
-  h->has_held = nhc > 0 || nhp > 0;
-  lens_changed(h);
-  return PSBA_OK;
-}
-
-int psba_held_counts(psba_handle h, int *n_held_poses, int *n_held_pts) {
-  CHECK_H(h);
-  if (n_held_poses) *n_held_poses = h->n_held_poses;
-  if (n_held_pts) *n_held_pts = h->n_held_pts;
-  return PSBA_OK;
-}
-
-static int d2h(psba_ctx *h, void *dst, const void *src, size_t bytes);
-
-// ---- Gaussian priors on cameras and points of the free-intrinsics route ----
-// one kind: n blocks of m parameters; checks every block and compacts those whose information is not all zero into
-// idx [n] (-1: none), list and rec [mean (m) | information (m x m), symmetrised]
-static int priors_pack(psba_ctx *h, const char *what, int n, int m, const double *mean, const double *info,
-                       std::vector<int> &idx, std::vector<int> &list, std::vector<double> &rec) {
-  idx.assign((size_t)n, -1);
-  for (int b = 0; mean && b < n; b++) {
-    const double *mu = mean + (size_t)m * b, *L = info + (size_t)m * m * b;
-    double big = 0.0;
-    for (int r = 0; r < m; r++)
-      if (!std::isfinite(mu[r])) return fail(h, PSBA_E_INVALID, "psba_set_priors: mean[%d] of %s %d is not finite", r, what, b);
-    for (int t = 0; t < m * m; t++) {
-      if (!std::isfinite(L[t]))
-        return fail(h, PSBA_E_INVALID, "psba_set_priors: information[%d][%d] of %s %d is not finite", t / m, t % m, what, b);
-      big = std::fmax(big, std::fabs(L[t]));
-    }
-    for (int r = 0; r < m; r++)
-      if (L[m * r + r] < 0.0)
-        return fail(h, PSBA_E_INVALID, "psba_set_priors: information[%d][%d] of %s %d is negative (%.17g)", r, r, what, b,
-                    L[m * r + r]);
-    for (int r = 0; r < m; r++)
-      for (int c = r + 1; c < m; c++)
-        if (std::fabs(L[m * r + c] - L[m * c + r]) > 1e-12 * big)
-          return fail(h, PSBA_E_INVALID, "psba_set_priors: information of %s %d is not symmetric at [%d][%d] (%.17g vs %.17g)",
-                      what, b, r, c, L[m * r + c], L[m * c + r]);
-    if (big == 0.0) continue;  // all zero: no prior
-    idx[b] = (int)list.size();
-    list.push_back(b);
-    rec.insert(rec.end(), mu, mu + m);
-    for (int r = 0; r < m; r++)
-      for (int c = 0; c < m; c++) rec.push_back(0.5 * (L[m * r + c] + L[m * c + r]));
-  }
-  return PSBA_OK;
-}
-
-int psba_set_priors(psba_handle h, const double *cam_mean, const double *cam_info, const double *pt_mean,
-                    const double *pt_info) {
-  CHECK_H(h);
-  NEED(h, h->uploaded, "no problem uploaded");
-  NEED(h, h->cnp != 6, "psba_set_priors: free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD); "
-                       "six-parameter blocks carry no priors");
-  NEED(h, !h->backsub_pending, "psba_set_priors: a damping try is in flight (psba_backsub_wait first)");
-  if ((cam_mean == nullptr) != (cam_info == nullptr))
-    return fail(h, PSBA_E_INVALID, "psba_set_priors: cam_mean and cam_info are both NULL or both given");
-  if ((pt_mean == nullptr) != (pt_info == nullptr))
-    return fail(h, PSBA_E_INVALID, "psba_set_priors: pt_mean and pt_info are both NULL or both given");
-  const int nC = h->d.nC, nP = h->d.nP, cnp = h->cnp;
-  std::vector<int> cidx, pidx, clist, plist;
-  std::vector<double> crec, prec;
-  TRY(priors_pack(h, "camera", nC, cnp, cam_mean, cam_info, cidx, clist, crec));
-  TRY(priors_pack(h, "point", nP, 3, pt_mean, pt_info, pidx, plist, prec));
-  const int ncp = (int)clist.size(), npp = (int)plist.size();
-  // no block with a prior is no priors.  With one, every table is staged (the kernels test no pointer; a kind without
-  // priors keeps one unused element) in buffers of their own and swapped in only when all are on the device
-  DevBuf<int> d_cidx, d_pidx, d_clist, d_plist;
-  DevBuf<double> d_crec, d_prec;
-  if (ncp || npp) {
-    if (clist.empty()) clist.push_back(0);
-    if (plist.empty()) plist.push_back(0);
-    if (crec.empty()) crec.assign((size_t)cnp + cnp * cnp, 0.0);
-    if (prec.empty()) prec.assign(12, 0.0);
-    auto stage = [&]() -> int {
-      TRY(d_cidx.alloc(h, cidx.size()));
-      TRY(d_pidx.alloc(h, pidx.size()));
-      TRY(d_clist.alloc(h, clist.size()));
-      TRY(d_plist.alloc(h, plist.size()));
-      TRY(d_crec.alloc(h, crec.size()));
-      TRY(d_prec.alloc(h, prec.size()));
-      PSBA_HIP(h, hipMemcpyAsync(d_cidx, cidx.data(), sizeof(int) * cidx.size(), hipMemcpyHostToDevice, h->stream));
-      PSBA_HIP(h, hipMemcpyAsync(d_pidx, pidx.data(), sizeof(int) * pidx.size(), hipMemcpyHostToDevice, h->stream));
-      PSBA_HIP(h, hipMemcpyAsync(d_clist, clist.data(), sizeof(int) * clist.size(), hipMemcpyHostToDevice, h->stream));
-      PSBA_HIP(h, hipMemcpyAsync(d_plist, plist.data(), sizeof(int) * plist.size(), hipMemcpyHostToDevice, h->stream));
-      PSBA_HIP(h, hipMemcpyAsync(d_crec, crec.data(), sizeof(double) * crec.size(), hipMemcpyHostToDevice, h->stream));
-      PSBA_HIP(h, hipMemcpyAsync(d_prec, prec.data(), sizeof(double) * prec.size(), hipMemcpyHostToDevice, h->stream));
-      return PSBA_OK;
-    };
-    const int rc = stage();
-    const hipError_t e = hipStreamSynchronize(h->stream);  // (the host vectors and a staged buffer outlive the copies)
-    if (rc != PSBA_OK) return rc;
-    PSBA_HIP(h, e);
-  } else {
-    PSBA_HIP(h, hipStreamSynchronize(h->stream));  // nothing queued still reads the old tables
-  }
-  h->prior_cidx = std::move(d_cidx);
-  h->prior_pidx = std::move(d_pidx);
-  h->prior_clist = std::move(d_clist);
-  h->prior_plist = std::move(d_plist);
-  h->prior_crec = std::move(d_crec);
-  h->prior_prec = std::move(d_prec);
-  h->n_cam_priors = ncp;
-  h->n_pt_priors = npp;
-  h->has_prior = ncp > 0 || npp > 0;
-  lens_changed(h);
-  return PSBA_OK;
-}
-
-int psba_prior_counts(psba_handle h, int *n_cam_priors, int *n_pt_priors) {
-  CHECK_H(h);
-  if (n_cam_priors) *n_cam_priors = h->n_cam_priors;
-  if (n_pt_priors) *n_pt_priors = h->n_pt_priors;
-  return PSBA_OK;
-}
-
-int psba_prior_cost(psba_handle h, int which, double *cams_part, double *pts_part) {
-  CHECK_H(h);
-  NEED(h, h->uploaded, "no problem uploaded");
-  NEED(h, h->cnp != 6, "psba_prior_cost: free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)");
-  NEED(h, !h->backsub_pending, "psba_prior_cost: a damping try is in flight (psba_backsub_wait first)");
-  if (which != PSBA_PARAMS_CUR && which != PSBA_PARAMS_NEW) return fail(h, PSBA_E_INVALID, "%s: which = %d", __func__, which);
-  double out[2] = {0.0, 0.0};
-  if (h->has_prior) {
-    if (!h->prior_out) TRY(h->prior_out.alloc(h, 2));
-    TRY(launch_prior_cost_free(h, which, h->prior_out));
-    TRY(d2h(h, out, h->prior_out, sizeof(out)));
-  } else {
-    PSBA_HIP(h, hipStreamSynchronize(h->stream));
-  }
-  if (cams_part) *cams_part = out[0];
-  if (pts_part) *pts_part = out[1];
-  return PSBA_OK;
-}
-
-// ---- the damping rule of the free-intrinsics route ----
-int psba_set_damping(psba_handle h, int kind, double dmin, double dmax) {
-  CHECK_H(h);
-  NEED(h, h->uploaded, "no problem uploaded");
-  NEED(h, h->cnp != 6, "psba_set_damping: free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD); "
-                       "six-parameter blocks keep the reference's N + mu I");
-  NEED(h, !h->backsub_pending, "psba_set_damping: a damping try is in flight (psba_backsub_wait first)");
-  if (kind != PSBA_DAMPING_IDENTITY && kind != PSBA_DAMPING_MARQUARDT)
-    return fail(h, PSBA_E_INVALID, "psba_set_damping: unknown kind %d", kind);
-  if (dmin == 0.0) dmin = 1e-6;
-  if (dmax == 0.0) dmax = 1e32;
-  if (!(std::isfinite(dmin) && std::isfinite(dmax) && dmin > 0.0 && dmin <= dmax))
-    return fail(h, PSBA_E_INVALID, "psba_set_damping: clamps (%g, %g): 0 < dmin <= dmax, both finite (0 = the default)", dmin,
-                dmax);
-  if (kind == PSBA_DAMPING_MARQUARDT && !h->damp_D) {  // both sets or none: a refused call changes nothing
-    DevBuf<double> D, D_alt;
-    TRY(D.alloc(h, (size_t)h->d.nT));
-    TRY(D_alt.alloc(h, (size_t)h->d.nT));
-    h->damp_D = std::move(D);
-    h->damp_D_alt = std::move(D_alt);
-  }
-  h->damp_kind = kind;
-  h->damp_dmin = dmin;
-  h->damp_dmax = dmax;
-  lens_changed(h);  // (a linearization queued ahead carries no D, or one of other clamps)
-  return PSBA_OK;
-}
-
-int psba_damping(psba_handle h, int *kind, double *dmin, double *dmax) {
-  CHECK_H(h);
-  NEED(h, h->uploaded, "no problem uploaded");
-  NEED(h, h->cnp != 6, "psba_damping: free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)");
-  if (kind) *kind = h->damp_kind;
-  if (dmin) *dmin = h->damp_dmin;
-  if (dmax) *dmax = h->damp_dmax;
-  return PSBA_OK;
-}
-
-// test hook (psba_hip.h): D as k_free_damp_diag stored it for the current linearization
-int psba_get_damping_diag(psba_handle h, double *D) {
-  CHECK_H(h);
-  NEED(h, h->uploaded, "no problem uploaded");
-  NEED(h, h->cnp != 6, "psba_get_damping_diag: free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD)");
-  NEED(h, h->damp_kind == PSBA_DAMPING_MARQUARDT, "psba_set_damping(PSBA_DAMPING_MARQUARDT) first");
-  NEED(h, h->damp_ok, "psba_linearize first (every verb that moves the parameters or the model invalidates the diagonal)");
-  return d2h(h, D, h->damp_D, sizeof(double) * (size_t)h->d.nT);
 }
 
 int psba_obs_sq_residuals(psba_handle h, int which, double *s) {
@@ -1204,6 +634,10 @@ int psba_upload_problem(psba_handle h, int nCams, int n3Dpts, int n2Dprojs, cons
   return PSBA_OK;
 }
 
+// psba_set_params and psba_reset_params may run while a try is in flight, where the setters refuse: they replace the
+// parameters the try was made for, so the try is given up as a whole and nothing waits for its scalars any more
+static void abandon_try(psba_ctx *h) { h->backsub_pending = h->publish_deferred = h->publish_in_k1 = false; }
+
 int psba_set_params(psba_handle h, const double *camsEx, const double *pts3D) {
   CHECK_H(h);
   NEED(h, h->uploaded, "no problem uploaded");
@@ -1213,11 +647,8 @@ int psba_set_params(psba_handle h, const double *camsEx, const double *pts3D) {
   PSBA_HIP(h, hipMemcpyAsync(h->pts[h->cur], pts3D, sizeof(double) * h->d.nB,
                              hipMemcpyHostToDevice, h->stream));
   PSBA_HIP(h, hipStreamSynchronize(h->stream));
-  h->linearized = h->assembled = h->solved = h->backsubbed = false;
-  h->ahead = h->lin_is_ahead = h->backsub_pending = h->publish_deferred = h->publish_in_k1 = false;
-  h->free_obs = false;
-  h->damp_ok = false;
-  h->cov_ok = h->cov_pts_ok = false;
+  params_changed(h);
+  abandon_try(h);
   return PSBA_OK;
 }
 
@@ -1228,11 +659,8 @@ int psba_reset_params(psba_handle h) {
                              h->stream));
   PSBA_HIP(h, hipMemcpyAsync(h->pts[h->cur], h->params0 + h->d.nA, sizeof(double) * h->d.nB,
                              hipMemcpyDeviceToDevice, h->stream));
-  h->linearized = h->assembled = h->solved = h->backsubbed = false;
-  h->ahead = h->lin_is_ahead = h->backsub_pending = h->publish_deferred = h->publish_in_k1 = false;
-  h->free_obs = false;
-  h->damp_ok = false;
-  h->cov_ok = h->cov_pts_ok = false;
+  params_changed(h);
+  abandon_try(h);
   return PSBA_OK;
 }
 
@@ -1558,8 +986,6 @@ int psba_accept(psba_handle h) {
 }
 
 // ---- operators of the trust-region caller ---------------------------------
-
-static int d2h(psba_ctx *h, void *dst, const void *src, size_t bytes);
 
 // ---- the sharded dense factorization, piece by piece (kernels_chol_graph.hip: chol_dist_*) ----
 int psba_chol_dist_shape(psba_handle h, int *n32, int *NB, int *sharded) {
@@ -1988,13 +1414,6 @@ static int ensure_dbg(psba_ctx *h) {
   if (!h->dbg_Y) TRY(h->dbg_Y.alloc(h, (size_t)18 * d.nO));
   if (!h->dbg_Vinv) TRY(h->dbg_Vinv.alloc(h, (size_t)9 * d.nP));
   if (!h->dbg_eb) TRY(h->dbg_eb.alloc(h, (size_t)3 * d.nP));
-  return PSBA_OK;
-}
-
-static int d2h(psba_ctx *h, void *dst, const void *src, size_t bytes) {
-  if (!dst) return PSBA_OK;
-  PSBA_HIP(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-  PSBA_HIP(h, hipStreamSynchronize(h->stream));
   return PSBA_OK;
 }
 

@@ -164,7 +164,9 @@ constexpr int RUN_MAX = 32;       // products a lane sums in registers before it
 // ProblemState: everything an upload creates or invalidates -- the problem's buffers and schedules, the settings that
 // belong to a problem (lens model, loss, fixed blocks) and the state of the try in flight.  A new upload and
 // psba_destroy replace it by a default-constructed one: its members release what they own and every scalar is back
-// at its initial value.  A new per-problem field goes here, with its initial value, and nothing else has to be updated.
+// at its initial value.  A new per-problem field goes here, with its initial value, and nothing else has to be updated;
+// a new derived-state flag (one that says "this was computed for the current model and parameters") is cleared in
+// model_changed (problem_options.cpp), and nowhere else.
 struct ProblemState {
   psba::Dims d;
   // ---- device memory ----
