@@ -704,7 +704,8 @@ int psba_algorithmic_bytes(psba_handle h, int kernel, double *bytes);
  * common point exist (the lower block triangle as a list; no dense buffer is allocated), and
  * psba_schur_solve runs conjugate gradients with a block-Jacobi preconditioner until
  * ||S x - e_a|| <= tol ||e_a|| or max_iter iterations; a diagonal block that is not positive definite or
- * a direction of non-positive curvature reports PSBA_NOT_SPD, so psba_levmar works unchanged; a solve
+ * a direction of non-positive curvature (or a residual that is not finite: NaN / Inf in S or e_a) reports
+ * PSBA_NOT_SPD, so psba_levmar works unchanged; a solve
  * that uses up max_iter returns PSBA_PCG_MAXIT (> 0: the step is usable, the LM gain ratio judges it, and
  * psba_levmar counts such solves in psba_lm_result.pcg_unconverged); e_a == 0 or an exactly solved system
  * is a converged solve with x as it stands, not a break-down.  The
@@ -724,6 +725,17 @@ int psba_pcg_info(psba_handle h, int *iters, double *relres, long long *blocks, 
 /* the assembled blocks: jk[2 blocks] = (j, k), k <= j; val[36 blocks] row-major; ea[nA]; any pointer may be NULL */
 int psba_get_sparse_S(psba_handle h, int *jk, double *val, double *ea);
 int psba_set_sparse_S(psba_handle h, const double *val, const double *ea);
+/* ---- mirror verb: y[nA] = S x[nA] on the stored blocks, formed by the kernel that forms the products of the solve
+ * (a stored block serves its own block row as it stands and its column's block row transposed; a diagonal block is
+ * read through its lower triangle only, its strict upper triangle is never touched).  The order of the sums of a row
+ * is fixed, so the same blocks and x give the same bits.  Same state as psba_get_sparse_S (between
+ * psba_schur_assemble and psba_schur_solve, PSBA_SOLVER_PCG, no structure-only try; PSBA_E_STATE otherwise);
+ * changes neither the blocks nor e_a nor a later solve.  Synchronises. */
+int psba_sparse_S_times(psba_handle h, const double *x, double *y);
+/* The verbs that work on the dense reduce buffer or the Cholesky chain -- psba_SPDinv_matVec,
+ * psba_get_reduce_buffer, psba_set_reduce_buffer, psba_chol_dist_begin / _superpanel / _block / _finish,
+ * psba_get_cholmod_factor, psba_covariance_compute -- return PSBA_E_STATE under PSBA_SOLVER_PCG before they copy or
+ * launch anything; the sba_func.h mirror's psba_compute_S / psba_compute_ea return PSBA_E_INVALID. */
 /* flags[nCams (nCams + 1) / 2]: 1 where block tri(j) + k (k <= j) has a product, i.e. cameras j and k see a common point */
 int psba_sparse_pattern(int nCams, int n3Dpts, int n2Dprojs, const int *iidx, const int *jidx, unsigned char *flags);
 int psba_set_sparse_pattern(psba_handle h, const unsigned char *flags, long long n);

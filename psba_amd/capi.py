@@ -149,6 +149,7 @@ SIGNATURES = [
     ("psba_pcg_info", C.c_int, [_h, _ip, _dp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("psba_get_sparse_S", C.c_int, [_h, _ip, _dp, _dp]),
     ("psba_set_sparse_S", C.c_int, [_h, _dp, _dp]),
+    ("psba_sparse_S_times", C.c_int, [_h, _dp, _dp]),
     ("psba_sparse_pattern", C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.POINTER(C.c_ubyte)]),
     ("psba_set_sparse_pattern", C.c_int, [_h, C.POINTER(C.c_ubyte), C.c_longlong]),
     ("psba_set_camera_model", C.c_int, [_h, C.c_int]),
@@ -844,6 +845,15 @@ class Psba:
         val = np.ascontiguousarray(val, dtype=np.float64)
         ea = np.ascontiguousarray(ea, dtype=np.float64)
         self._ck(lib.psba_set_sparse_S(self._h, _d(val), _d(ea)))
+
+    def sparse_S_times(self, x):
+        """psba_sparse_S_times: y = S x [nA] on the stored blocks, by the solve's own product kernel."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if x.size != 6 * self.nC:
+            raise PsbaError(-1, f"sparse_S_times: {x.size} entries for {6 * self.nC} unknowns")
+        y = np.empty(6 * self.nC)
+        self._ck(lib.psba_sparse_S_times(self._h, _d(x), _d(y)))
+        return y
 
     def set_sparse_pattern(self, flags):
         flags = np.ascontiguousarray(flags, dtype=np.uint8)

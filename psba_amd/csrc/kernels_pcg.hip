@@ -318,7 +318,8 @@ int launch_bsr_finalize(psba_ctx *h, double mu) {
 }
 
 // lambda = max(0, -min_i d_i) of the stored S (k_bsr_gershgorin), a small positive value when S is diagonally
-// dominant although the solve failed (rounding); info3 = { min d, max S_ii, 0 }
+// dominant although the solve failed (rounding); info3 = { min d, max d, 0 } as psba_hip.h says (max d, the largest
+// margin, is a lower bound of max S_ii and takes its place as the scale of that small value)
 int launch_bsr_gershgorin(psba_ctx *h, double *lambda, double *info3) {
   const int n = h->d.nA, nC = h->d.nC;
   double *d = h->pcg_vec + 3 * (size_t)n;  // (the solve's q: free between solves)
@@ -329,7 +330,7 @@ int launch_bsr_gershgorin(psba_ctx *h, double *lambda, double *info3) {
   PSBA_HIP(h, hipStreamSynchronize(h->stream));
   double dmin = hd[0];
   for (int i = 1; i < n; i++) dmin = hd[i] < dmin ? hd[i] : dmin;
-  // max S_ii >= max (d_i): a scale for the fallback
+  // max (d_i) <= max S_ii: a scale for the fallback
   double dmax = 0.0;
   for (int i = 0; i < n; i++) dmax = hd[i] > dmax ? hd[i] : dmax;
   double lam = dmin < 0.0 ? -dmin : 0.0;
@@ -341,6 +342,21 @@ int launch_bsr_gershgorin(psba_ctx *h, double *lambda, double *info3) {
     info3[1] = dmax;
     info3[2] = 0.0;
   }
+  return PSBA_OK;
+}
+
+// y = S x with the solve's own product kernel on the stored blocks (psba_sparse_S_times): x goes into the solve's p,
+// the product into its q (both free between solves), x.Sx into the 64 partial sums of slot 0 -- launch_pcg_solve
+// clears the whole scalar block before it starts, so a later solve sees nothing of this
+int launch_bsr_times(psba_ctx *h, const double *x_host, double *y_host) {
+  const int n = h->d.nA, nC = h->d.nC;
+  double *p = h->pcg_vec + 2 * (size_t)n, *q = p + n;
+  PSBA_HIP(h, hipMemcpyAsync(p, x_host, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_pcg_spmv, dim3((nC + 3) / 4), dim3(256), 0, h->stream, h->bs_val, h->bs_rowptr, h->bs_rowent, nC, p, q,
+                     h->pcg_scal, 0);
+  PSBA_HIP(h, hipGetLastError());
+  PSBA_HIP(h, hipMemcpyAsync(y_host, q, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+  PSBA_HIP(h, hipStreamSynchronize(h->stream));
   return PSBA_OK;
 }
 
@@ -392,7 +408,16 @@ int launch_pcg_solve(psba_ctx *h) {
       converged = true;
     }
     h->pcg_relres = hs[PC_BB] > 0.0 ? sqrt(rr / hs[PC_BB]) : 0.0;
-    if (converged || !(rr == rr)) break;
+    if (converged) break;
+    if (!(rr - rr == 0.0)) {
+      // a non-finite residual: NaN or Inf in S or e_a that the curvature test has not met yet (it meets it one
+      // iteration later, which max_iter or the end of a burst may cut off) -- reported like a failed factorization,
+      // never as an exhausted budget
+      PSBA_HIP(h, hipMemcpyAsync(h->status + 1, &h->try_id, sizeof(int), hipMemcpyHostToDevice, s));
+      PSBA_HIP(h, hipStreamSynchronize(s));
+      failed = true;
+      break;
+    }
   }
   // max_iter iterations without reaching tol: the step is used as it is (an inexact Newton step; the gain
   // ratio judges it), but the caller is told -- psba_schur_solve returns PSBA_PCG_MAXIT

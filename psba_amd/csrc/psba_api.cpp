@@ -1010,6 +1010,7 @@ int psba_chol_dist_exchange_plan(int n32, int NB, int nranks, int JE, long long 
 }
 int psba_chol_dist_begin(psba_handle h) {
   CHECK_H(h);
+  NEED_DENSE(h);
   NEED(h, h->assembled, "psba_schur_assemble (and the reduction over ranks) first");
   if (h->packed_pending) {
     TRY(launch_schur_expand(h));
@@ -1020,6 +1021,7 @@ int psba_chol_dist_begin(psba_handle h) {
 }
 int psba_chol_dist_superpanel(psba_handle h, int J) {
   CHECK_H(h);
+  NEED_DENSE(h);
   NEED(h, h->assembled, "psba_schur_assemble first");
   if (J < 0 || J >= h->n32) return fail(h, PSBA_E_INVALID, "super-panel column %d out of range", J);
   h->cholmod_factor = false;
@@ -1027,6 +1029,7 @@ int psba_chol_dist_superpanel(psba_handle h, int J) {
 }
 int psba_chol_dist_block(psba_handle h, int B, int set, double *buf, long long *n_doubles) {
   CHECK_H(h);
+  NEED_DENSE(h);
   NEED(h, h->assembled, "psba_schur_assemble first");
   if (B < 0 || 64 * B >= h->n32) return fail(h, PSBA_E_INVALID, "column block %d out of range", B);
   const int ncols = h->n32 - 64 * B < 64 ? h->n32 - 64 * B : 64;
@@ -1044,6 +1047,7 @@ int psba_chol_dist_block(psba_handle h, int B, int set, double *buf, long long *
 }
 int psba_chol_dist_finish(psba_handle h) {
   CHECK_H(h);
+  NEED_DENSE(h);
   NEED(h, h->assembled, "psba_schur_assemble first");
   h->cholmod_factor = false;
   TRY(chol_dist_finish(h));
@@ -1118,6 +1122,16 @@ int psba_set_sparse_S(psba_handle h, const double *val, const double *ea) {
   PSBA_HIP(h, hipStreamSynchronize(h->stream));
   h->solved = h->backsubbed = false;
   return PSBA_OK;
+}
+
+// y = S x on the stored blocks, with the kernel the solve uses for its products (a mirror verb: how that kernel is judged
+// on its own)
+int psba_sparse_S_times(psba_handle h, const double *x, double *y) {
+  CHECK_H(h);
+  NEED(h, h->assembled && h->solver == PSBA_SOLVER_PCG, "psba_schur_assemble with PSBA_SOLVER_PCG first");
+  NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");
+  if (!x || !y) return fail(h, PSBA_E_INVALID, "%s: null pointer", __func__);
+  return launch_bsr_times(h, x, y);
 }
 
 // host only: which blocks of the lower block triangle a (shard of a) problem produces
@@ -1562,6 +1576,7 @@ int psba_compute_ea(psba_handle h, double *ea) {
 
 int psba_SPDinv_matVec(psba_handle h, double *dpa) {
   CHECK_H(h);
+  NEED_DENSE(h);
   NEED(h, h->assembled, "compute_S / compute_ea first");
   NEED(h, !h->try_shortcut, "every camera is fixed: psba_schur_assemble assembled no S (compute_S / compute_ea first)");
   h->cholmod_factor = false;
@@ -1701,6 +1716,7 @@ int psba_get_reduce_buffer(psba_handle h, double *out) {
 
 int psba_set_reduce_buffer(psba_handle h, const double *in) {
   CHECK_H(h);
+  NEED_DENSE(h);
   NEED(h, h->cnp == 6 || h->cnp == KD_CNP, SIX_ONLY);
   NEED(h, h->assembled, "psba_schur_assemble first");
   NEED(h, !h->comm, "the reduce-buffer verbs are for handles without a communicator");
