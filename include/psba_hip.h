@@ -265,6 +265,39 @@ int psba_set_priors(psba_handle h, const double *cam_mean, const double *cam_inf
 int psba_prior_counts(psba_handle h, int *n_cam_priors, int *n_pt_priors);
 int psba_prior_cost(psba_handle h, int which, double *cams_part, double *pts_part);
 
+/* ---- observation weighting on the free-intrinsics models: robust loss and sigmas ----
+ * Real tracks carry mismatches, and a plain least-squares self-calibration is ruined by them.  psba_set_robust_loss,
+ * psba_set_obs_covariance and psba_obs_sq_residuals keep refusing these models; this verb is their counterpart here.
+ * Model (the same in psba_amd/csrc/kernels_free.hip and DESIGN 7k).  Observation a may carry a standard deviation
+ * sigma_a > 0; without sigmas sigma_a = 1.  A loss (kind, c) may be set, with the kinds, formulas and conventions of
+ * the robust losses below (PSBA_LOSS_*).  With e_a the route's residual:
+ *     s_a = |e_a / sigma_a|^2        F = sum_a rho(s_a) + the priors' two sums (the priors are not weighted)
+ * IRLS without the rho'' term: omega_a = sqrt(rho'(s_a)).  The kernel first multiplies e, both rows of A, and B by
+ * 1 / sigma_a (the reciprocal is stored once at the setter) and then by omega_a: two roundings per entry.  Everything
+ * behind the per-observation blocks reads the weighted blocks and is otherwise unchanged: W, Be, U, g_a, V, g_b, D of
+ * Marquardt, Y, S, e_a, the fold of the groups, the back-substitution and gain_den.  A zeroed column stays zero under
+ * the scaling, so every exact guarantee of the mask, the groups, the damping, the holds and the priors keeps holding.
+ * psba_residual, psba_begin, new_cost of the try and the costs and stop_cost of psba_levmar are all F;
+ * psba_get_free_obs_blocks returns the weighted W and B | e.  psba_linearize_ahead takes its weights at the proposal.
+ * sigma [n2Dprojs] in the uploaded observation order, or NULL.  (PSBA_LOSS_NONE, any scale, NULL) is no weighting: the
+ * handle then runs the kernels of one that never called this and produces the same bits, also after a weighted run.
+ * After psba_upload_problem (a new upload resets to (PSBA_LOSS_NONE, 1, no sigmas)); PSBA_E_STATE before an upload,
+ * while a try is in flight and on six-parameter camera blocks (those have psba_set_robust_loss /
+ * psba_set_obs_covariance); PSBA_E_INVALID for an unknown kind, for a scale that is not finite and > 0 (checked for
+ * every kind) and for a sigma that is not finite and > 0 (the text names the first offending observation).  A refused
+ * call changes nothing.  Setting the weighting discards a linearization queued ahead and invalidates
+ * psba_get_free_obs_blocks and psba_get_damping_diag.  No floating-point atomics: two runs are bit-identical.
+ * Still refused on these models: full 2 x 2 observation covariances, psba_covariance_compute, PSBA_SOLVER_PCG, rank
+ * layouts and the sba_func.h mirror.  PARITY UNPINNED, like the models it belongs to.
+ * psba_obs_weighting: what is set (any pointer may be NULL).
+ * psba_get_obs_weights: s[n2Dprojs], w[n2Dprojs] (either may be NULL) at PSBA_PARAMS_CUR / PSBA_PARAMS_NEW, uploaded
+ * observation order: s_a as above, w_a = omega_a / sigma_a, the factor the blocks were multiplied by.  Works with no
+ * weighting set (s = |e|^2, w = 1).  Synchronises.  PSBA_E_STATE on six-parameter blocks, while a try is in flight,
+ * and for PSBA_PARAMS_NEW without a proposal. */
+int psba_set_obs_weighting(psba_handle h, int loss_kind, double loss_scale, const double *sigma /* n2Dprojs or NULL */);
+int psba_obs_weighting(psba_handle h, int *loss_kind, double *loss_scale, int *has_sigma);
+int psba_get_obs_weights(psba_handle h, int which, double *s, double *w);
+
 /* ---- lens distortion and per-observation image covariances --------------------------
  * Model (the same in psba_amd/csrc/camera_model.h and DESIGN.md): P = R'(q) M + t, (x, y) = (Px, Py) / Pz,
  * r2 = x^2 + y^2, kc = (k1, k2, k3, k4, k5) in the Camera Calibration Toolbox order (the column order of the

@@ -167,6 +167,9 @@ SIGNATURES = [
     ("psba_set_priors", C.c_int, [_h, _dp, _dp, _dp, _dp]),
     ("psba_prior_counts", C.c_int, [_h, _ip, _ip]),
     ("psba_prior_cost", C.c_int, [_h, C.c_int, _dp, _dp]),
+    ("psba_set_obs_weighting", C.c_int, [_h, C.c_int, C.c_double, _dp]),
+    ("psba_obs_weighting", C.c_int, [_h, _ip, _dp, _ip]),
+    ("psba_get_obs_weights", C.c_int, [_h, C.c_int, _dp, _dp]),
     ("psba_read_problem_ex", C.c_int, [C.c_char_p, C.c_char_p, _dp, C.POINTER(CProblemEx)]),
     ("psba_free_problem_ex", None, [C.POINTER(CProblemEx)]),
     ("psba_convert_bal_kd", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p]),
@@ -659,6 +662,28 @@ class Psba:
         c, p = C.c_double(), C.c_double()
         self._ck(lib.psba_prior_cost(self._h, which, C.byref(c), C.byref(p)))
         return c.value, p.value
+
+    def set_obs_weighting(self, kind, scale=1.0, sigma=None):
+        """psba_set_obs_weighting (free-intrinsics models): a loss kind LOSS_NONE / LOSS_HUBER / LOSS_CAUCHY /
+        LOSS_SOFT_L1 with scale c > 0, and sigma [nO] standard deviations per observation in the uploaded order (None:
+        all 1).  (LOSS_NONE, any scale, None) clears the weighting."""
+        s = None if sigma is None else np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(-1))
+        if s is not None and self.nO and s.size != self.nO:  # (before an upload nO is 0: the library refuses)
+            raise PsbaError(-1, f"set_obs_weighting: {s.size} sigmas for {self.nO} observations")
+        self._ck(lib.psba_set_obs_weighting(self._h, int(kind), float(scale), None if s is None else _d(s)))
+
+    def obs_weighting(self):
+        """psba_obs_weighting -> (kind, scale, sigmas are set)"""
+        k, c, s = C.c_int(), C.c_double(), C.c_int()
+        self._ck(lib.psba_obs_weighting(self._h, C.byref(k), C.byref(c), C.byref(s)))
+        return k.value, c.value, bool(s.value)
+
+    def get_obs_weights(self, which=PARAMS_CUR):
+        """psba_get_obs_weights -> (s [nO], w [nO]) at PARAMS_CUR / PARAMS_NEW: s_a = |e_a / sigma_a|^2 and
+        w_a = omega_a / sigma_a, the factor the observation's blocks are multiplied by."""
+        s, w = np.empty(self.nO), np.empty(self.nO)
+        self._ck(lib.psba_get_obs_weights(self._h, which, _d(s), _d(w)))
+        return s, w
 
     def obs_sq_residuals(self, which=PARAMS_CUR):
         """psba_obs_sq_residuals: s_a = ||L_a e_a||^2 per observation [nO] at PARAMS_CUR / PARAMS_NEW."""

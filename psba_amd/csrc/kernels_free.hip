@@ -73,7 +73,35 @@ struct FreeArgs {
   double *pub_dst;
   double pub_stamp;
   const unsigned char *held_pose, *held_pt;  // read by the HELD instantiations only (last: the other offsets stay)
+  const double *isig;                        // read by the WGT instantiations only (below)
+  RobustLoss rl;
 };
+
+// ---- observation weighting (psba_set_obs_weighting) ----
+// Observation a may carry a standard deviation sigma_a > 0 (without sigmas sigma_a = 1), and a loss (kind, c) may be
+// set, with the kinds, formulas and conventions of DESIGN 7b (PSBA_LOSS_*, robust_eval in camera_model.h).  With e_a
+// the route's residual:
+//   s_a = |e_a / sigma_a|^2        F = sum_a rho(s_a) + the priors' two sums (the priors are not weighted)
+// IRLS without the rho'' term: omega_a = sqrt(rho'(s_a)).  The kernel first multiplies e, both rows of A, and B by
+// 1 / sigma_a (the reciprocal is stored once at the setter) and then by omega_a -- the order of whiten_obs followed by
+// robust_scale on the fixed route: two roundings per entry.  Everything behind the per-observation blocks reads the
+// weighted blocks and is otherwise unchanged: W, Be, U, g_a, V, g_b, D of Marquardt, Y, S, e_a, the fold of the
+// groups, the back-substitution and gain_den.  A zeroed column stays zero under the scaling, so every exact guarantee
+// of the mask, the groups, the damping, the holds and the priors keeps holding.  psba_residual, psba_begin, the try's
+// new cost and the costs of psba_levmar are all F; psba_get_free_obs_blocks returns the weighted W and B | e.
+// The kernels that see observations are templated on WGT; a handle without a weighting runs the false instantiations,
+// which are the code as it was (no load of the table, no loss argument read).  With WGT the table 1 / sigma [nO] is
+// always allocated (ones when only a loss is set), so no kernel tests a pointer.  The weights are per observation:
+// no sum is new, and every reduction keeps the order the upload fixes.
+// e <- e / sigma_a; s_a, rho(s_a) and omega_a of the scaled e
+__device__ __forceinline__ void free_weight(const RobustLoss &rl, double is, double &e0, double &e1, double &s, double &rho,
+                                            double &om) {
+  PSBA_FP_PINNED;
+  e0 *= is;
+  e1 *= is;
+  s = e0 * e0 + e1 * e1;
+  robust_eval(rl, s, rho, om);
+}
 
 // ---- Gaussian priors on cameras and points (psba_set_priors) ----
 // A camera j may carry a mean m_j [CNP] (the order of the camera block) and a symmetric positive semi-definite
@@ -135,7 +163,7 @@ __device__ __forceinline__ double free_wave_sum(double v) {
 
 // camera-major: one wave per unit = up to 64 observations of one camera, one per lane.  e, A (masked), B; W_a and
 // (B | e) to global memory, the Jacobian rows to LDS, then U and g_a of the unit by MFMA
-template <class T, bool HELD>
+template <class T, bool HELD, bool WGT>
 __global__ __launch_bounds__(64) void k_free_linearize(FreeArgs p) {
   constexpr int CNP = T::CNP, ROW = 2 * CNP + 3;
   __shared__ double sJ[KD_UNIT][ROW];
@@ -155,6 +183,17 @@ __global__ __launch_bounds__(64) void k_free_linearize(FreeArgs p) {
     double2 m;
     free_load<T>(p, a, i, j, cam, q0, M, m);
     T::linearize(cam, q0, M, m.x, m.y, e, A, B, p.mask);
+    if (WGT) {  // e, A, B by 1 / sigma_a, then by omega_a of the scaled e (before anything is stored)
+      const double is = p.isig[a];
+      double s, rho, om;
+      free_weight(p.rl, is, e[0], e[1], s, rho, om);
+      e[0] *= om;
+      e[1] *= om;
+#pragma unroll
+      for (int k = 0; k < 2 * CNP; k++) A[k] = (A[k] * is) * om;
+#pragma unroll
+      for (int k = 0; k < 6; k++) B[k] = (B[k] * is) * om;
+    }
     if (HELD) {  // (selects on registers, before anything is stored)
       const bool hp = p.held_pose[j] != 0, hq = p.held_pt[i] != 0;
 #pragma unroll
@@ -289,7 +328,7 @@ __global__ __launch_bounds__(256) void k_free_point_sums(const double *Be, const
 }
 
 // cost: per-workgroup partial sums; k_free_sum_columns adds them in workgroup order
-template <class T>
+template <class T, bool WGT>
 __global__ __launch_bounds__(256) void k_free_residual(FreeArgs p, double *part) {
   __shared__ double sRed[4];
   double sum = 0.0;
@@ -299,12 +338,37 @@ __global__ __launch_bounds__(256) void k_free_residual(FreeArgs p, double *part)
     double2 m;
     free_load<T>(p, a, i, j, cam, q0, M, m);
     T::residual(cam, q0, M, m.x, m.y, e0, e1);
-    sum += e0 * e0 + e1 * e1;
+    if (WGT) {  // rho(|e / sigma_a|^2)
+      double s, rho, om;
+      free_weight(p.rl, p.isig[a], e0, e1, s, rho, om);
+      sum += rho;
+    } else {
+      sum += e0 * e0 + e1 * e1;
+    }
   }
   sum = free_wave_sum(sum);
   if ((threadIdx.x & 63) == 0) sRed[threadIdx.x >> 6] = sum;
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = ((sRed[0] + sRed[1]) + sRed[2]) + sRed[3];
+}
+
+// psba_get_obs_weights: one thread per observation, s_a and w_a = omega_a / sigma_a (the factor the blocks are
+// multiplied by) at the parameter set of p, from the residual alone.  On a handle without a weighting isig is null
+// (s = |e|^2, w = 1): the only kernel of the file that tests the pointer, and no solver path runs it
+template <class T>
+__global__ __launch_bounds__(256) void k_free_obs_weights(FreeArgs p, double *s_out, double *w_out) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= p.nO) return;
+  int i, j;
+  double cam[T::CNP], q0[4], M[3], e0, e1;
+  double2 m;
+  free_load<T>(p, a, i, j, cam, q0, M, m);
+  T::residual(cam, q0, M, m.x, m.y, e0, e1);
+  const double is = p.isig ? p.isig[a] : 1.0;
+  double s, rho, om;
+  free_weight(p.rl, is, e0, e1, s, rho, om);
+  s_out[a] = s;
+  w_out[a] = om * is;
 }
 
 // dst[q] = head[q] + sum over rows r < n of part[ncol r + q], in row order (q < ncol <= 4; head may be null)
@@ -552,6 +616,8 @@ struct FreeBackArgs {
   int nA, nP;
   const unsigned char *held_pose, *held_pt;  // read by the HELD instantiations only
   FreePriors pr;                             // read by the PRIOR instantiations only
+  const double *isig;                        // read by the WGT instantiations only
+  RobustLoss rl;
 };
 // the camera priors' cost at the proposal, from the newcams this workgroup has just written (behind a barrier): the
 // try's `new cost` slot, thread per coordinate r: d_r (sum_c L[r][c] d[c])
@@ -601,7 +667,7 @@ __global__ __launch_bounds__(256) void k_free_backsub_cams(FreeBackArgs p) {  //
   if (PRIOR) v4[2] = free_prior_newcost<T::CNP>(p);
   free_block_sums4(v4, sRed, p.red);
 }
-template <class T, bool HELD, bool PRIOR>
+template <class T, bool HELD, bool PRIOR, bool WGT>
 __global__ __launch_bounds__(256) void k_free_backsub_pts(FreeBackArgs p) {
   constexpr int CNP = T::CNP;
   __shared__ double sRed[4][4];
@@ -657,7 +723,13 @@ __global__ __launch_bounds__(256) void k_free_backsub_pts(FreeBackArgs p) {
       for (int k = 0; k < 4; k++) q0[k] = p.camconst[9 * (size_t)j + 5 + k];
       const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
       T::residual(cam, q0, n3, m.x, m.y, r0, r1);
-      v4[2] += r0 * r0 + r1 * r1;
+      if (WGT) {  // rho(|e / sigma_a|^2) at the proposal
+        double s, rho, om;
+        free_weight(p.rl, p.isig[a], r0, r1, s, rho, om);
+        v4[2] += rho;
+      } else {
+        v4[2] += r0 * r0 + r1 * r1;
+      }
     }
     if (PRIOR) {  // the point's prior at its proposal, behind its observations
       const int k = p.pr.pidx[i];
@@ -871,6 +943,8 @@ static FreeArgs free_args(psba_ctx *h, int set) {
   a.pub_src = h->scal;
   a.pub_dst = nullptr;
   a.pub_stamp = 0.0;
+  a.isig = h->obs_isig;
+  a.rl = make_robust_loss(h->wgt_kind, h->wgt_c);
   return a;
 }
 static FreePriors free_priors(psba_ctx *h) {
@@ -886,7 +960,7 @@ static int free_grid(long long n, int cap) {
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-template <class T, bool HELD, bool PRIOR>
+template <class T, bool HELD, bool PRIOR, bool WGT>
 static int linearize_free(psba_ctx *h, bool ahead, bool publish) {
   const Dims &d = h->d;
   const int set = ahead ? 1 - h->cur : h->cur;
@@ -898,7 +972,7 @@ static int linearize_free(psba_ctx *h, bool ahead, bool publish) {
   h->coeff_w = h->coeff;
   double *Uo = ahead ? h->U_alt : h->U, *gao = ahead ? h->ga_alt : h->ga;
   ProfScope ps(h, PSBA_K_LINEARIZE);
-  hipLaunchKernelGGL((k_free_linearize<T, HELD>), dim3(h->nCamUnits), dim3(64), 0, h->stream, a);
+  hipLaunchKernelGGL((k_free_linearize<T, HELD, WGT>), dim3(h->nCamUnits), dim3(64), 0, h->stream, a);
   const long long nfin = (long long)d.nC * (T::CNP * T::CNP + T::CNP);
   const FreePriors pr = free_priors(h);
   hipLaunchKernelGGL((k_free_finish_cams<T, HELD, PRIOR>), dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, h->stream,
@@ -943,13 +1017,13 @@ static int prior_cost_free(psba_ctx *h, int which, double *out2) {
   return PSBA_OK;
 }
 
-template <class T>
+template <class T, bool WGT>
 static int residual_free(psba_ctx *h, int which) {
   const int set = which == PSBA_PARAMS_NEW ? 1 - h->cur : h->cur;
   FreeArgs a = free_args(h, set);
   const int grid = free_grid(h->d.nO, 256);
   ProfScope ps(h, PSBA_K_RESIDUAL);
-  hipLaunchKernelGGL(k_free_residual<T>, dim3(grid), dim3(256), 0, h->stream, a, h->free_red);
+  hipLaunchKernelGGL((k_free_residual<T, WGT>), dim3(grid), dim3(256), 0, h->stream, a, h->free_red);
   // F: the observations' partials, then the camera priors', then the point priors' (none without priors)
   const int rows = grid + prior_cost_parts<T>(h, a.cams, a.pts, h->free_red + grid, nullptr);
   hipLaunchKernelGGL(k_free_sum_columns, dim3(1), dim3(64), 0, h->stream, (const double *)nullptr, h->free_red, rows, 1,
@@ -1017,7 +1091,7 @@ static int schur_free(psba_ctx *h, double mu) {
   return PSBA_OK;
 }
 
-template <class T, bool HELD, bool PRIOR>
+template <class T, bool HELD, bool PRIOR, bool WGT>
 static int backsub_free(psba_ctx *h, double mu) {
   const Dims &d = h->d;
   FreeBackArgs a;
@@ -1033,6 +1107,8 @@ static int backsub_free(psba_ctx *h, double mu) {
   a.held_pose = h->held_poses;
   a.held_pt = h->held_pts;
   a.pr = free_priors(h);
+  a.isig = h->obs_isig;
+  a.rl = make_robust_loss(h->wgt_kind, h->wgt_c);
   a.dp = h->dp;
   a.newcams = h->cams[1 - h->cur];
   a.newpts = h->pts[1 - h->cur];
@@ -1050,7 +1126,7 @@ static int backsub_free(psba_ctx *h, double mu) {
     hipLaunchKernelGGL((k_kd_backsub_cams_groups<HELD, PRIOR>), dim3(1), dim3(256), 0, h->stream, a, (const int *)h->kd_rep);
   else
     hipLaunchKernelGGL((k_free_backsub_cams<T, HELD, PRIOR>), dim3(1), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL((k_free_backsub_pts<T, HELD, PRIOR>), dim3(grid), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL((k_free_backsub_pts<T, HELD, PRIOR, WGT>), dim3(grid), dim3(256), 0, h->stream, a);
   // set 0 of the SC_NPART partial sets carries the whole sums (k_free_finalize zeroed the others)
   hipLaunchKernelGGL(k_free_sum_columns, dim3(1), dim3(64), 0, h->stream, (const double *)h->free_red,
                      (const double *)h->free_red + 4, grid, 4, h->scal + SC_PART);
@@ -1058,21 +1134,36 @@ static int backsub_free(psba_ctx *h, double mu) {
   return PSBA_OK;
 }
 
+// psba_get_obs_weights: s and w (device, [nO] each) at a parameter set
+template <class T>
+static int obs_weights_free(psba_ctx *h, int which, double *s_dev, double *w_dev) {
+  const int set = which == PSBA_PARAMS_NEW ? 1 - h->cur : h->cur;
+  FreeArgs a = free_args(h, set);
+  hipLaunchKernelGGL(k_free_obs_weights<T>, dim3((unsigned)((h->d.nO + 255) / 256)), dim3(256), 0, h->stream, a, s_dev, w_dev);
+  PSBA_HIP(h, hipGetLastError());
+  return PSBA_OK;
+}
+
 // one dispatch on the camera block per launcher; the launchers whose kernels read the held masks also on has_held,
-// those whose kernels read the priors also on has_prior
+// those whose kernels read the priors also on has_prior, those whose kernels see observations also on has_weighting
 #define FREE_DISPATCH(fn, ...) (h->cnp == KD_CNP ? fn<FreeKD>(__VA_ARGS__) : fn<FreeK>(__VA_ARGS__))
 #define FREE_DISPATCH_HELD(fn, ...)                                                                        \
   (h->cnp == KD_CNP ? (h->has_held ? fn<FreeKD, true>(__VA_ARGS__) : fn<FreeKD, false>(__VA_ARGS__)) \
                     : (h->has_held ? fn<FreeK, true>(__VA_ARGS__) : fn<FreeK, false>(__VA_ARGS__)))
-#define FREE_DISPATCH_HP1(T, fn, ...)                                                                             \
-  (h->has_held ? (h->has_prior ? fn<T, true, true>(__VA_ARGS__) : fn<T, true, false>(__VA_ARGS__)) \
-               : (h->has_prior ? fn<T, false, true>(__VA_ARGS__) : fn<T, false, false>(__VA_ARGS__)))
-#define FREE_DISPATCH_HP(fn, ...) (h->cnp == KD_CNP ? FREE_DISPATCH_HP1(FreeKD, fn, __VA_ARGS__) : FREE_DISPATCH_HP1(FreeK, fn, __VA_ARGS__))
-int launch_linearize_free(psba_ctx *h, bool ahead, bool publish) { return FREE_DISPATCH_HP(linearize_free, h, ahead, publish); }
+#define FREE_DISPATCH_W(fn, ...)                                                                                   \
+  (h->cnp == KD_CNP ? (h->has_weighting ? fn<FreeKD, true>(__VA_ARGS__) : fn<FreeKD, false>(__VA_ARGS__)) \
+                    : (h->has_weighting ? fn<FreeK, true>(__VA_ARGS__) : fn<FreeK, false>(__VA_ARGS__)))
+#define FREE_DISPATCH_HPW2(T, H, fn, ...)                                                                                  \
+  (h->has_prior ? (h->has_weighting ? fn<T, H, true, true>(__VA_ARGS__) : fn<T, H, true, false>(__VA_ARGS__)) \
+                : (h->has_weighting ? fn<T, H, false, true>(__VA_ARGS__) : fn<T, H, false, false>(__VA_ARGS__)))
+#define FREE_DISPATCH_HPW1(T, fn, ...) (h->has_held ? FREE_DISPATCH_HPW2(T, true, fn, __VA_ARGS__) : FREE_DISPATCH_HPW2(T, false, fn, __VA_ARGS__))
+#define FREE_DISPATCH_HPW(fn, ...) (h->cnp == KD_CNP ? FREE_DISPATCH_HPW1(FreeKD, fn, __VA_ARGS__) : FREE_DISPATCH_HPW1(FreeK, fn, __VA_ARGS__))
+int launch_linearize_free(psba_ctx *h, bool ahead, bool publish) { return FREE_DISPATCH_HPW(linearize_free, h, ahead, publish); }
+int launch_obs_weights_free(psba_ctx *h, int which, double *s_dev, double *w_dev) { return FREE_DISPATCH(obs_weights_free, h, which, s_dev, w_dev); }
 int launch_prior_cost_free(psba_ctx *h, int which, double *out2_dev) { return FREE_DISPATCH(prior_cost_free, h, which, out2_dev); }
-int launch_residual_free(psba_ctx *h, int which) { return FREE_DISPATCH(residual_free, h, which); }
+int launch_residual_free(psba_ctx *h, int which) { return FREE_DISPATCH_W(residual_free, h, which); }
 int launch_max_diag_free(psba_ctx *h) { return FREE_DISPATCH_HELD(max_diag_free, h); }
 int launch_schur_free(psba_ctx *h, double mu) { return FREE_DISPATCH(schur_free, h, mu); }
-int launch_backsub_free(psba_ctx *h, double mu) { return FREE_DISPATCH_HP(backsub_free, h, mu); }
+int launch_backsub_free(psba_ctx *h, double mu) { return FREE_DISPATCH_HPW(backsub_free, h, mu); }
 
 }  // namespace psba

@@ -1,5 +1,5 @@
 // problem_options.cpp -- the settings of an uploaded problem (include/psba_hip.h): camera model, lens model,
-// robust loss, fixed blocks, the mask and the groups of the intrinsics, held poses and points, priors, the damping rule,
+// robust loss, fixed blocks, the mask and the groups of the intrinsics, held poses and points, priors, the observation weighting, the damping rule,
 // and their getters.  Every setter is built from the same three pieces: settable() says whether it may run now,
 // stage() puts new device tables in place all or nothing, model_changed() / params_changed() drop what was derived.
 #include <algorithm>
@@ -451,6 +451,42 @@ int psba_prior_cost(psba_handle h, int which, double *cams_part, double *pts_par
   }
   if (cams_part) *cams_part = out[0];
   if (pts_part) *pts_part = out[1];
+  return PSBA_OK;
+}
+
+// ---- observation weighting of the free-intrinsics route ----
+int psba_set_obs_weighting(psba_handle h, int loss_kind, double loss_scale, const double *sigma) {
+  CHECK_H(h);
+  TRY(settable(h, __func__, FREE_MODELS, "; six-parameter blocks: psba_set_robust_loss / psba_set_obs_covariance"));
+  if (loss_kind < PSBA_LOSS_NONE || loss_kind > PSBA_LOSS_SOFT_L1)
+    return fail(h, PSBA_E_INVALID, "%s: unknown loss kind %d", __func__, loss_kind);
+  if (!(std::isfinite(loss_scale) && loss_scale > 0.0))
+    return fail(h, PSBA_E_INVALID, "%s: the scale must be finite and > 0 (got %.17g)", __func__, loss_scale);
+  const int nO = h->d.nO;
+  for (int a = 0; sigma && a < nO; a++)
+    if (!(std::isfinite(sigma[a]) && sigma[a] > 0.0 && std::isfinite(1.0 / sigma[a])))  // (the reciprocal is what is stored)
+      return fail(h, PSBA_E_INVALID, "%s: sigma of observation %d must be finite and > 0 (got %.17g)", __func__, a, sigma[a]);
+  // (none, any scale, no sigmas) is no weighting: no table, the plain instantiations.  With a loss alone the table holds
+  // ones (the kernels test no pointer)
+  const bool on = loss_kind != PSBA_LOSS_NONE || sigma;
+  std::vector<double> isig;
+  if (on) isig.assign((size_t)nO, 1.0);
+  for (int a = 0; sigma && a < nO; a++) isig[a] = 1.0 / sigma[a];
+  TRY(stage(h, Staged(h->obs_isig, isig)));
+  h->wgt_kind = loss_kind;
+  h->wgt_c = loss_scale;
+  h->wgt_sigma = sigma != nullptr;
+  h->has_weighting = on;
+  model_changed(h);
+  return PSBA_OK;
+}
+
+int psba_obs_weighting(psba_handle h, int *loss_kind, double *loss_scale, int *has_sigma) {
+  CHECK_H(h);
+  TRY(settable(h, __func__, FREE_MODELS, "", ANY_TIME));
+  if (loss_kind) *loss_kind = h->wgt_kind;
+  if (loss_scale) *loss_scale = h->wgt_c;
+  if (has_sigma) *has_sigma = h->wgt_sigma ? 1 : 0;
   return PSBA_OK;
 }
 

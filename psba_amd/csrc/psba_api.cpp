@@ -1294,6 +1294,24 @@ int psba_get_free_obs_blocks(psba_handle h, double *W, double *Be) {
   return d2h(h, Be, h->free_Be, sizeof(double) * 8 * (size_t)h->d.nO);
 }
 
+// s_a and w_a = omega_a / sigma_a of the observation weighting at a parameter set; without a weighting
+// s = |e|^2 and w = 1
+int psba_get_obs_weights(psba_handle h, int which, double *s, double *w) {
+  CHECK_H(h);
+  NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, h->cnp != 6, "free-intrinsics models only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD); six-parameter blocks: psba_obs_sq_residuals");
+  if (which != PSBA_PARAMS_CUR && which != PSBA_PARAMS_NEW) return fail(h, PSBA_E_INVALID, "%s: which = %d", __func__, which);
+  NEED(h, !h->backsub_pending, "a damping try is in flight (psba_backsub_wait first)");
+  NEED(h, which == PSBA_PARAMS_CUR || h->backsubbed, "PSBA_PARAMS_NEW: no proposal (psba_backsub first)");
+  const size_t nO = (size_t)h->d.nO;
+  if (!h->obs_sw) TRY(h->obs_sw.alloc(h, 2 * nO));
+  TRY(launch_obs_weights_free(h, which, h->obs_sw, h->obs_sw + nO));
+  if (s) TRY(d2h(h, s, h->obs_sw, sizeof(double) * nO));
+  if (w) TRY(d2h(h, w, h->obs_sw + nO, sizeof(double) * nO));
+  PSBA_HIP(h, hipStreamSynchronize(h->stream));
+  return PSBA_OK;
+}
+
 // ---- covariance of the estimate (kernels_cov.hip) ------------------------------------
 
 namespace {

@@ -323,6 +323,14 @@ struct ProblemState {
   psba::DevBuf<double> prior_out;                // [2] psba_prior_cost's device output, allocated on first use
   int n_cam_priors = 0, n_pt_priors = 0;
   bool has_prior = false;
+  // observation weighting of this route (psba_set_obs_weighting): a loss (kind, scale) and 1 / sigma per
+  // observation.  has_weighting (the WGT kernel instantiations) = a loss other than none or sigmas; the table is then
+  // allocated (ones when only a loss is set), none otherwise; an upload resets to (none, 1, no sigmas)
+  int wgt_kind = 0;
+  double wgt_c = 1.0;
+  bool wgt_sigma = false, has_weighting = false;
+  psba::DevBuf<double> obs_isig;   // [nO] 1 / sigma_a
+  psba::DevBuf<double> obs_sw;     // [2 nO] psba_get_obs_weights' device output s | w, allocated on first use
   // the damping rule of this route (psba_set_damping): N + mu I, or N + mu D with Marquardt's
   // D_k = min(max(N_kk, dmin), dmax).  damp_D [nT] belongs to the current linearization, damp_D_alt to the one queued
   // ahead (psba_accept swaps them with the rest); both are allocated by the first switch to Marquardt
@@ -468,6 +476,7 @@ int build_blockprod_plan(int nCams, int nObs, const int *iidx, const int *jidx, 
                          BlockProdPlanHost &out);  // blockprod_plan.cpp
 int launch_linearize_free(psba_ctx *h, bool ahead, bool publish);
 int launch_residual_free(psba_ctx *h, int which);
+int launch_obs_weights_free(psba_ctx *h, int which, double *s_dev, double *w_dev);
 int launch_prior_cost_free(psba_ctx *h, int which, double *out2_dev);
 int launch_max_diag_free(psba_ctx *h);
 int launch_schur_free(psba_ctx *h, double mu);

@@ -7,9 +7,11 @@ them alike; both blocks run the kernels of kernels_free.hip.  --seg sweeps the s
 with the poses of cameras 0 and 1 held (psba_set_held, DESIGN 7i: the same launches and the same products).  --priors
 adds every variant once more with a weak diagonal prior about the start on every camera and on every 16th point
 (psba_set_priors, DESIGN 7j: the PRIOR instantiations of the same launches, two more cost kernels per psba_residual;
-the variant without is the PRIOR = false code).  --problem wide65 is tests/freekd_twin.py's wide_problem(65).
+the variant without is the PRIOR = false code).  --weights adds every variant once more with Cauchy, c = 2, and sigmas
+drawn log-uniform in [0.5, 2] (psba_set_obs_weighting, DESIGN 7k: the WGT instantiations of the same launches; the
+variant without is the WGT = false code).  --problem wide65 is tests/freekd_twin.py's wide_problem(65).
 Usage: python scripts/freekd_time.py [--rounds N] [--iters N] [--seg 16,64,256] [--problem p54|venice|both|wide65]
-       [--held] [--priors]"""
+       [--held] [--priors] [--weights]"""
 import argparse
 import os
 import sys
@@ -24,7 +26,7 @@ from psba_amd import synth  # noqa: E402
 CLASSES = [("linearize", 0), ("S assembly", 1), ("Cholesky", 2), ("back-subst.", 3)]
 
 
-def open_handle(prob, model, free, seg, held=False, priors=False):
+def open_handle(prob, model, free, seg, held=False, priors=False, weights=False):
     if seg:
         os.environ["PSBA_FKD_SEG"] = str(seg)
     else:
@@ -43,6 +45,9 @@ def open_handle(prob, model, free, seg, held=False, priors=False):
         pt_info = np.zeros(pts.shape)
         pt_info[::16] = 1e-6
         h.set_priors(cams, np.full(cams.shape, 1e-6), pts, pt_info)
+    if weights:
+        sigma = np.exp(np.random.default_rng(5).uniform(np.log(0.5), np.log(2.0), int(prob["nO"])))
+        h.set_obs_weighting(psba_amd.LOSS_CAUCHY, 2.0, sigma)
     return h
 
 
@@ -54,6 +59,7 @@ def main():
     ap.add_argument("--problem", default="both")
     ap.add_argument("--held", action="store_true")
     ap.add_argument("--priors", action="store_true")
+    ap.add_argument("--weights", action="store_true")
     args = ap.parse_args()
     data = os.path.join(ROOT, "tests", "golden", "data")
     probs = []
@@ -80,7 +86,10 @@ def main():
         variants = [v + (False,) for v in variants]
         if args.priors:
             variants = [w for v in variants for w in (v, (v[0] + " priors",) + v[1:5] + (True,))]
-        handles = [(name, open_handle(prob, model, free, s, held, pri)) for name, model, free, s, held, pri in variants]
+        variants = [v + (False,) for v in variants]
+        if args.weights:
+            variants = [w for v in variants for w in (v, (v[0] + " weights",) + v[1:6] + (True,))]
+        handles = [(name, open_handle(prob, model, free, s, held, pri, wgt)) for name, model, free, s, held, pri, wgt in variants]
         ms = {name: [] for name, _ in handles}
         for rnd in range(args.rounds + 1):
             for name, h in handles:
