@@ -436,6 +436,59 @@ int psba_get_point_covariance(psba_handle h, double *out /* n3Dpts*9, full symme
 /* measurement: HIP-event milliseconds of the last psba_covariance_compute that returned PSBA_OK -- factor (with the
  * compaction), inverse (with the mirror), points.  Linearization and assembly are timed by psba_profile_get. */
 int psba_covariance_times(psba_handle h, double ms3[3]);
+
+/* ---- covariance of the refined cameras and points with free intrinsics (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD;
+ * DESIGN 7l) -- verbs of their own: psba_covariance_compute keeps refusing both models and its getters return 6 x 6
+ * blocks ------------------------------------------------------------------------------------------------------------
+ * Definition (the same text in psba_amd/csrc/kernels_freecov.hip and DESIGN.md).  The covariance is taken at the
+ * current parameters, on the linearization of psba_linearize(h, 1, 1).  That linearization is exactly what the route's
+ * normal equations see: the intrinsics mask, the groups, held poses and points, the priors' information in U and V,
+ * blocks weighted by omega / sigma.  Let N be that system and D the diagonal of psba_set_damping (I for the identity
+ * rule).  For mu >= 0 and scale > 0 the covariance is built in three steps.
+ *   reduced camera part   X = S(mu)^-1 on the live coordinates of the folded S.  A live coordinate is not masked, is
+ *                         not a held pose coordinate, is not folded away by the groups, and is not padding
+ *   returned camera part  C_aa = scale E X E^T, where E copies a representative's shared intrinsic to the members of
+ *                         its group: rows and columns of masked and held coordinates are exactly 0 (not the inverse
+ *                         of the placeholder); a folded-away coordinate's row and column are bit-identical to its
+ *                         representative's, because shared intrinsics are perfectly correlated; C_aa is bit-symmetric
+ *   point i               C_bb,i = scale V*_i^-1 + sum_{j,k in cams(i)} Y_ij^T C_jk Y_ik, with the expanded C_aa,
+ *                         V*_i = V_i + mu D_i and Y_ij the block that k_free_Y stored for this mu.  A held point gives
+ *                         zeros; a point without observations, and one whose blocks Y are all zero, scale V*^-1
+ * mu = 0 is the covariance and needs a gauge: held poses or priors.  mu > 0 is a regularised inverse and NOT a
+ * covariance.  The cross blocks C_ab are not returned.  PARITY UNPINNED, as for psba_covariance_compute.
+ * psba_free_covariance_compute follows the rules of psba_covariance_compute.  With reassemble != 0 it linearizes with
+ * (1, 1) unless that linearization is current, then runs psba_schur_assemble(mu) and psba_schur_reduce; the handle is
+ * left as after those calls (a psba_schur_solve may follow; psba_get_reduce_buffer returns the S that was inverted),
+ * and a psba_levmar after a compute takes the path it would have taken without it.  reassemble = 0 inverts what the
+ * reduce buffer holds; only the camera part is valid afterwards.  The inverse is that of psba_covariance_compute (its
+ * blocked Cholesky and inverse on 16 x 16 MFMA tiles, on a private copy of S) between a compaction to the live
+ * coordinates and an expansion over the groups.  Returns PSBA_OK, PSBA_NOT_SPD or PSBA_SINGULAR_V (bit-or; the
+ * outputs are invalid then) and synchronises.  PSBA_E_STATE before an upload, while a try is in flight and on
+ * six-parameter blocks (the text names psba_covariance_compute); PSBA_E_INVALID for a mu that is not finite and >= 0
+ * and for a scale that is not finite and > 0; a refused call changes nothing.
+ * The getters return PSBA_E_STATE until a compute has returned PSBA_OK and again after anything that moves the
+ * parameters or the model: every setter of the route, psba_set_params, psba_reset_params, psba_accept,
+ * psba_upload_problem.  psba_get_free_point_covariance and psba_get_free_sigmas also return PSBA_E_STATE after a
+ * compute with reassemble = 0.  No floating-point atomics: two computes on the same state return bit-identical
+ * arrays. */
+int psba_free_covariance_compute(psba_handle h, double mu, double scale, int reassemble);
+/* pairs[2 n_pairs] = (j, k) in any order, out[cnp^2 n_pairs] row-major = C_jk (cnp = psba_camera_block); pairs NULL:
+ * n_pairs must be nCams, the diagonal blocks */
+int psba_get_free_camera_covariance(psba_handle h, int n_pairs, const int *pairs, double *out);
+int psba_get_free_covariance_matrix(psba_handle h, double *Caa /* (cnp nCams)^2 row-major, symmetric */);
+int psba_get_free_point_covariance(psba_handle h, double *out /* n3Dpts*9, full symmetric 3x3 */);
+/* sigma[nT] = [cnp per camera ; 3 per point]: the square roots of the diagonals of C_aa and of the C_bb,i (one small
+ * kernel); a coordinate with variance 0 (masked, held) gives 0 */
+int psba_get_free_sigmas(psba_handle h, double *sigma);
+/* test hook in the style of psba_get_free_obs_blocks: V [n3Dpts][9] = V_i as the linearization stored it (undamped,
+ * full symmetric; the priors' information included, a held point's placeholder) and Y [n2Dprojs][cnp][3] = the blocks
+ * k_free_Y stored at the last psba_schur_assemble.  Either pointer may be null.  Needs an assembled try
+ * (psba_schur_assemble, or psba_free_covariance_compute with reassemble != 0, and no psba_schur_solve since):
+ * PSBA_E_STATE otherwise and for six-parameter blocks. */
+int psba_get_free_point_blocks(psba_handle h, double *V, double *Y);
+/* measurement: HIP-event milliseconds of the last psba_free_covariance_compute that returned PSBA_OK -- factor (with
+ * the compaction), inverse (with the expansion), points */
+int psba_free_covariance_times(psba_handle h, double ms3[3]);
 /* which S-assembly route the uploaded problem takes: 0 = LDS-resident partitions of the block
  * triangle with the static schedule (fewer than 2048 cameras, up to 8 GB of partial-sum slabs on
  * this rank), 1 = the owner route for larger problems (one thread per block segment,

@@ -204,6 +204,13 @@ SIGNATURES = [
     ("psba_get_covariance_matrix", C.c_int, [_h, _dp]),
     ("psba_get_point_covariance", C.c_int, [_h, _dp]),
     ("psba_covariance_times", C.c_int, [_h, _dp]),
+    ("psba_free_covariance_compute", C.c_int, [_h, C.c_double, C.c_double, C.c_int]),
+    ("psba_get_free_camera_covariance", C.c_int, [_h, C.c_int, _ip, _dp]),
+    ("psba_get_free_covariance_matrix", C.c_int, [_h, _dp]),
+    ("psba_get_free_point_covariance", C.c_int, [_h, _dp]),
+    ("psba_get_free_sigmas", C.c_int, [_h, _dp]),
+    ("psba_get_free_point_blocks", C.c_int, [_h, _dp, _dp]),
+    ("psba_free_covariance_times", C.c_int, [_h, _dp]),
 ]
 # only in a library built with PSBA_BUILD_EXPERIMENTS=1 (round 3's rejected ring route and its test hooks)
 EXPERIMENT_SIGNATURES = [
@@ -993,6 +1000,56 @@ class Psba:
     def covariance_times(self):
         """psba_covariance_times: HIP-event ms (factor, inverse, points) of the last covariance()."""
         return self._out(lib.psba_covariance_times, 3)[1]
+
+    # ---- covariance of the estimate with free intrinsics (blocks of 11 and 16; DESIGN 7l) ----
+    def _sizes(self):
+        """(cnp, nA, nT) of the uploaded problem; (6, 1, 1) before an upload (the library refuses, nothing is written)"""
+        cnp = getattr(self, "cnp", 6)
+        return cnp, max(cnp * self.nC, 1), max(cnp * self.nC + 3 * self.nP, 1)
+
+    def free_covariance(self, mu=0.0, scale=1.0, reassemble=True):
+        """psba_free_covariance_compute: C_aa = scale E S(mu)^-1 E^T on the live coordinates and the point blocks, at the
+        current parameters (mu = 0, the covariance, needs a gauge: held poses or priors).  scale is a number.  Returns
+        PSBA_OK, PSBA_NOT_SPD or PSBA_SINGULAR_V (the getters refuse then); raises on errors."""
+        return self._ck(lib.psba_free_covariance_compute(self._h, float(mu), float(scale), int(bool(reassemble))))
+
+    def free_camera_covariance(self, pairs=None):
+        """psba_get_free_camera_covariance: [n, cnp, cnp] blocks C_jk of the pairs [(j, k), ...]; None: the nC diagonal
+        blocks."""
+        cnp = self._sizes()[0]
+        if pairs is None:
+            out = np.empty((max(self.nC, 1), cnp, cnp))
+            self._ck(lib.psba_get_free_camera_covariance(self._h, self.nC, None, _d(out)))
+            return out[:self.nC]
+        p = _c(pairs, np.int32).reshape(-1, 2)
+        out = np.empty((p.shape[0], cnp, cnp))
+        self._ck(lib.psba_get_free_camera_covariance(self._h, p.shape[0], _i(p), _d(out)))
+        return out
+
+    def free_covariance_matrix(self):
+        """psba_get_free_covariance_matrix: C_aa [nA, nA], symmetric; zero rows and columns for masked and held
+        coordinates, a folded-away coordinate's equal to its representative's."""
+        nA = self._sizes()[1]
+        return self._out(lib.psba_get_free_covariance_matrix, nA * nA)[1].reshape(nA, nA)
+
+    def free_point_covariance(self):
+        """psba_get_free_point_covariance: C_bb,i [nP, 3, 3] (not after free_covariance(reassemble=False))."""
+        return self._out(lib.psba_get_free_point_covariance, max(9 * self.nP, 1))[1][:9 * self.nP].reshape(self.nP, 3, 3)
+
+    def free_sigmas(self):
+        """psba_get_free_sigmas: [nT] standard deviations = sqrt of the diagonals of C_aa and of the C_bb,i."""
+        return self._out(lib.psba_get_free_sigmas, self._sizes()[2])[1]
+
+    def free_point_blocks(self):
+        """psba_get_free_point_blocks (test hook): V [nP, 3, 3] undamped, Y [nO, cnp, 3] of the last assemble."""
+        cnp = self._sizes()[0]
+        V, Y = np.empty(max(9 * self.nP, 1)), np.empty(max(3 * cnp * self.nO, 1))
+        self._ck(lib.psba_get_free_point_blocks(self._h, _d(V), _d(Y)))
+        return V[:9 * self.nP].reshape(self.nP, 3, 3), Y[:3 * cnp * self.nO].reshape(self.nO, cnp, 3)
+
+    def free_covariance_times(self):
+        """psba_free_covariance_times: HIP-event ms (factor, inverse, points) of the last free_covariance()."""
+        return self._out(lib.psba_free_covariance_times, 3)[1]
 
     def trust_region(self, max_iter=50, start_itno=0, verbose=False, log_cap=512, init_lambda=0.0):
         opts = TrOptions(max_iter, start_itno, int(verbose), log_cap, init_lambda)

@@ -1,0 +1,48 @@
+// free_blocks.h -- what the kernel files of the free-intrinsics route share (kernels_free.hip, kernels_freecov.hip):
+// the two camera blocks the kernels are templated on, and the groups' tables with the predicate of a folded-away
+// coordinate.  Device code only.
+#pragma once
+#include "camera_model.h"
+
+namespace psba {
+
+typedef double kd4 __attribute__((ext_vector_type(4)));
+
+// the camera block: CNP parameters, the first NI of them intrinsics (the mask's bits); linearization and residual
+struct FreeK {
+  static constexpr int CNP = FK_CNP, NI = 5;
+  static __device__ __forceinline__ void linearize(const double *cam, const double *q0, const double *M, double mx,
+                                                   double my, double *e, double *A, double *B, unsigned) {
+    linearize_obs_freek(cam, q0, M, mx, my, e, A, B);  // (no mask: all five intrinsics are free)
+  }
+  static __device__ __forceinline__ void residual(const double *cam, const double *q0, const double *M, double mx,
+                                                  double my, double &e0, double &e1) {
+    residual_obs(cam, q0, cam + 5, M, mx, my, e0, e1);
+  }
+};
+struct FreeKD {
+  static constexpr int CNP = KD_CNP, NI = 10;
+  static __device__ __forceinline__ void linearize(const double *cam, const double *q0, const double *M, double mx,
+                                                   double my, double *e, double *A, double *B, unsigned mask) {
+    linearize_obs_freekd(cam, q0, M, mx, my, e, A, B, mask);
+  }
+  static __device__ __forceinline__ void residual(const double *cam, const double *q0, const double *M, double mx,
+                                                  double my, double &e0, double &e1) {
+    residual_obs_dist(cam, q0, cam + 10, M, cam + 5, mx, my, e0, e1);
+  }
+};
+// ---- intrinsics shared between cameras (psba_set_intrinsics_groups): the tables of the groups ----
+struct KdGroups {
+  const int *rep;   // [nC] representative of each camera
+  const int *gidx;  // [nC] the camera's group among those with several members, -1: alone
+  const int *gptr;  // [nmg + 1] CSR over gmem
+  const int *gmem;  // members, ascending; the first of a group is its representative
+  int nmg;
+  unsigned mask;
+};
+__device__ __forceinline__ bool kd_folded(const KdGroups &G, int t) {  // t: coordinate of the camera part
+  const int k = t % KD_CNP;
+  return k < 10 && ((G.mask >> k) & 1u) && G.rep[t / KD_CNP] != t / KD_CNP;
+}
+
+}  // namespace psba

@@ -282,18 +282,21 @@ __global__ __launch_bounds__(64) void k_cov_points(const double *W, const double
     if (e__ != hipSuccess) return fail((h), PSBA_E_HIP, "covariance kernel launch failed: %s", hipGetErrorString(e__)); \
   } while (0)
 
-// S (the n32 x n32 head of the reduce buffer) -> cov_C = scale S^-1 with zeros on the held rows and columns.
-// ev (may be null): three events recorded before the factor, between factor and inverse, and behind the inverse
-int launch_cov_cameras(psba_ctx *h, double scale, hipEvent_t *ev) {
-  const int n32 = h->n32, nA = h->d.nA, NT = n32 / 16;
-  const size_t nn = (size_t)n32 * n32;
+// The camera part in stages, so that the factorization and the inverse run unchanged between a compaction and a finish
+// chosen by the caller (this file's for the fixed-K route, kernels_freecov.hip's for the free-intrinsics route).
+// the two squares and the inverses of the factor's diagonal tiles, on first use
+int cov_workspaces(psba_ctx *h) {
+  const size_t nn = (size_t)h->n32 * h->n32;
   if (!h->cov_L) COV_TRY(h->cov_L.alloc(h, nn));
   if (!h->cov_C) COV_TRY(h->cov_C.alloc(h, nn));
-  if (!h->cov_dinv) COV_TRY(h->cov_dinv.alloc(h, (size_t)256 * NT));
-  const unsigned nb = (unsigned)((nn + 255) / 256);
+  if (!h->cov_dinv) COV_TRY(h->cov_dinv.alloc(h, (size_t)256 * (h->n32 / 16)));
+  return PSBA_OK;
+}
+
+// cov_L (a compacted copy of S) -> its Cholesky factor in place, cov_dinv, cov_status[0] on a bad pivot
+int launch_cov_factor(psba_ctx *h) {
+  const int n32 = h->n32, NT = n32 / 16;
   hipStream_t s = h->stream;
-  if (ev) PSBA_HIP(h, hipEventRecord(ev[0], s));
-  k_cov_compact<<<nb, 256, 0, s>>>(h->red, h->cov_L, h->fix_cams, nA, n32);
   for (int p = 0; p < NT; p++) {
     k_cov_diag<<<1, 64, 0, s>>>(h->cov_L, h->cov_dinv, n32, p, h->cov_status);
     const int rest = NT - p - 1;
@@ -303,8 +306,30 @@ int launch_cov_cameras(psba_ctx *h, double scale, hipEvent_t *ev) {
     }
   }
   COV_LAUNCHED(h);
+  return PSBA_OK;
+}
+
+// the factor in cov_L -> the lower triangle of its inverse in cov_C
+int launch_cov_inverse(psba_ctx *h) {
+  const int n32 = h->n32, NT = n32 / 16;
+  k_cov_inverse<<<NT, 256, 0, h->stream>>>(h->cov_L, h->cov_dinv, h->cov_C, n32, NT);
+  COV_LAUNCHED(h);
+  return PSBA_OK;
+}
+
+// S (the n32 x n32 head of the reduce buffer) -> cov_C = scale S^-1 with zeros on the held rows and columns.
+// ev (may be null): three events recorded before the factor, between factor and inverse, and behind the inverse
+int launch_cov_cameras(psba_ctx *h, double scale, hipEvent_t *ev) {
+  const int n32 = h->n32, nA = h->d.nA;
+  const size_t nn = (size_t)n32 * n32;
+  COV_TRY(cov_workspaces(h));
+  const unsigned nb = (unsigned)((nn + 255) / 256);
+  hipStream_t s = h->stream;
+  if (ev) PSBA_HIP(h, hipEventRecord(ev[0], s));
+  k_cov_compact<<<nb, 256, 0, s>>>(h->red, h->cov_L, h->fix_cams, nA, n32);
+  COV_TRY(launch_cov_factor(h));
   if (ev) PSBA_HIP(h, hipEventRecord(ev[1], s));
-  k_cov_inverse<<<NT, 256, 0, s>>>(h->cov_L, h->cov_dinv, h->cov_C, n32, NT);
+  COV_TRY(launch_cov_inverse(h));
   k_cov_finish<<<nb, 256, 0, s>>>(h->cov_C, h->fix_cams, nA, n32, scale);
   COV_LAUNCHED(h);
   if (ev) PSBA_HIP(h, hipEventRecord(ev[2], s));

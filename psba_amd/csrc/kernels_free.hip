@@ -18,36 +18,12 @@
 // camera unit / per segment of a block's product list, partial results combined in unit / segment order -- so two
 // runs give bit-identical reduce buffers and LM logs.
 #include "camera_model.h"
+#include "free_blocks.h"
 #include "psba_internal.h"
 #include "schur_common.h"
 
 namespace psba {
 
-typedef double kd4 __attribute__((ext_vector_type(4)));
-
-// the camera block: CNP parameters, the first NI of them intrinsics (the mask's bits); linearization and residual
-struct FreeK {
-  static constexpr int CNP = FK_CNP, NI = 5;
-  static __device__ __forceinline__ void linearize(const double *cam, const double *q0, const double *M, double mx,
-                                                   double my, double *e, double *A, double *B, unsigned) {
-    linearize_obs_freek(cam, q0, M, mx, my, e, A, B);  // (no mask: all five intrinsics are free)
-  }
-  static __device__ __forceinline__ void residual(const double *cam, const double *q0, const double *M, double mx,
-                                                  double my, double &e0, double &e1) {
-    residual_obs(cam, q0, cam + 5, M, mx, my, e0, e1);
-  }
-};
-struct FreeKD {
-  static constexpr int CNP = KD_CNP, NI = 10;
-  static __device__ __forceinline__ void linearize(const double *cam, const double *q0, const double *M, double mx,
-                                                   double my, double *e, double *A, double *B, unsigned mask) {
-    linearize_obs_freekd(cam, q0, M, mx, my, e, A, B, mask);
-  }
-  static __device__ __forceinline__ void residual(const double *cam, const double *q0, const double *M, double mx,
-                                                  double my, double &e0, double &e1) {
-    residual_obs_dist(cam, q0, cam + 10, M, cam + 5, mx, my, e0, e1);
-  }
-};
 // per observation: W (or Y) is CNP x 3 row-major; per unit: the partial A^T A (CNP x CNP) | A^T e (CNP); the LDS row
 // of a staged observation is A (2 x CNP) | e | pad (an odd stride: 25 and 35)
 
@@ -743,19 +719,6 @@ __global__ __launch_bounds__(256) void k_free_backsub_pts(FreeBackArgs p) {
 // A free intrinsic coordinate k < 10 of a camera that is not the representative (lowest member) of its group is
 // "folded away": its row and column are added to the representative's and it is left as a masked coordinate is.
 // The kernels below are for blocks of 16 only and run only on a handle with groups; every sum goes over the members in ascending camera order.
-struct KdGroups {
-  const int *rep;   // [nC] representative of each camera
-  const int *gidx;  // [nC] the camera's group among those with several members, -1: alone
-  const int *gptr;  // [nmg + 1] CSR over gmem
-  const int *gmem;  // members, ascending; the first of a group is its representative
-  int nmg;
-  unsigned mask;
-};
-__device__ __forceinline__ bool kd_folded(const KdGroups &G, int t) {  // t: coordinate of the camera part
-  const int k = t % KD_CNP;
-  return k < 10 && ((G.mask >> k) & 1u) && G.rep[t / KD_CNP] != t / KD_CNP;
-}
-
 // k_free_finalize without the damping and with the whole square symmetric entry by entry (the diagonal blocks of
 // -sum Y_a W_a^T are symmetric only to rounding: their lower triangle is the matrix), so that the fold may read any
 // entry: S = blockdiag(U) - sum Y W^T, e_a, identity padding, the accumulators zeroed, the try stamp set

@@ -359,6 +359,13 @@ struct ProblemState {
   bool cov_ok = false;                // cov_C is the camera covariance of the current parameters and model
   bool cov_pts_ok = false;            // ... and cov_pts the point blocks (not after reassemble = 0)
   double cov_ms[3] = {0.0, 0.0, 0.0}; // factor, inverse, points of the last compute (psba_covariance_times)
+  // ... with free intrinsics (psba_free_covariance_compute; kernels_freecov.hip): the workspaces above
+  // (cov_L, cov_C, cov_dinv, cov_pts, cov_status, cov_ms) are shared, Y is the route's own free_Y; the coordinate map
+  // and the expanded result are this route's, as are the two flags (the getters of 7h keep refusing a free handle)
+  psba::DevBuf<int> fcov_src;         // [nA] -1 masked or held | itself: live | the representative's coordinate: folded away
+  psba::DevBuf<double> fcov_C;        // [n32][n32] scale E X E^T
+  bool fcov_ok = false;               // fcov_C is the camera covariance of the current parameters and model
+  bool fcov_pts_ok = false;           // ... and cov_pts the point blocks (not after reassemble = 0)
   // debug dumps for the sba_func.h mirror (allocated on first use)
   psba::DevBuf<double> dbg_ex, dbg_JA, dbg_JB, dbg_Y, dbg_Vinv, dbg_eb;
 
@@ -503,6 +510,14 @@ int launch_struct_only_try(psba_ctx *h, double mu);
 int launch_cov_cameras(psba_ctx *h, double scale, hipEvent_t *ev);
 int launch_cov_points(psba_ctx *h, double mu, double scale, bool with_C);
 int launch_cov_gather(psba_ctx *h, const int2 *pairs_dev, int n_pairs, double *out_dev);
+int cov_workspaces(psba_ctx *h);     // the stages of launch_cov_cameras between its compaction and its finish
+int launch_cov_factor(psba_ctx *h);
+int launch_cov_inverse(psba_ctx *h);
+// kernels_freecov.hip
+int launch_fcov_cameras(psba_ctx *h, double scale, hipEvent_t *ev);
+int launch_fcov_points(psba_ctx *h, double mu, double scale);
+int launch_fcov_gather(psba_ctx *h, const int2 *pairs_dev, int n_pairs, double *out_dev);
+int launch_fcov_sigmas(psba_ctx *h, double *sigma_dev);
 // kernels_tr.hip
 int launch_jmul(psba_ctx *h, const double *x1_dev, const double *x2_dev, double *out1_dev, double *dots_dev);
 int launch_pack_g(psba_ctx *h, double *g_dev);
