@@ -440,7 +440,7 @@ int psba_covariance_times(psba_handle h, double ms3[3]);
 /* ---- covariance of the refined cameras and points with free intrinsics (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD;
  * DESIGN 7l) -- verbs of their own: psba_covariance_compute keeps refusing both models and its getters return 6 x 6
  * blocks ------------------------------------------------------------------------------------------------------------
- * Definition (the same text in psba_amd/csrc/kernels_freecov.hip and DESIGN.md).  The covariance is taken at the
+ * Definition (the same text in psba_amd/csrc/kernels_cov.hip and DESIGN.md).  The covariance is taken at the
  * current parameters, on the linearization of psba_linearize(h, 1, 1).  That linearization is exactly what the route's
  * normal equations see: the intrinsics mask, the groups, held poses and points, the priors' information in U and V,
  * blocks weighted by omega / sigma.  Let N be that system and D the diagonal of psba_set_damping (I for the identity

@@ -980,13 +980,17 @@ class Psba:
 
     def camera_covariance(self, pairs=None):
         """psba_get_camera_covariance: [n, 6, 6] blocks C_jk of the pairs [(j, k), ...]; None: the nC diagonal blocks."""
+        return self._camera_blocks(lib.psba_get_camera_covariance, 6, pairs)
+
+    def _camera_blocks(self, getter, cnp, pairs):
+        """the pair marshalling of both camera-covariance getters: [n, cnp, cnp]"""
         if pairs is None:
-            out = np.empty((self.nC, 6, 6))
-            self._ck(lib.psba_get_camera_covariance(self._h, self.nC, None, _d(out)))
-            return out
+            out = np.empty((max(self.nC, 1), cnp, cnp))
+            self._ck(getter(self._h, self.nC, None, _d(out)))
+            return out[:self.nC]
         p = _c(pairs, np.int32).reshape(-1, 2)
-        out = np.empty((p.shape[0], 6, 6))
-        self._ck(lib.psba_get_camera_covariance(self._h, p.shape[0], _i(p), _d(out)))
+        out = np.empty((p.shape[0], cnp, cnp))
+        self._ck(getter(self._h, p.shape[0], _i(p), _d(out)))
         return out
 
     def covariance_matrix(self):
@@ -1016,15 +1020,7 @@ class Psba:
     def free_camera_covariance(self, pairs=None):
         """psba_get_free_camera_covariance: [n, cnp, cnp] blocks C_jk of the pairs [(j, k), ...]; None: the nC diagonal
         blocks."""
-        cnp = self._sizes()[0]
-        if pairs is None:
-            out = np.empty((max(self.nC, 1), cnp, cnp))
-            self._ck(lib.psba_get_free_camera_covariance(self._h, self.nC, None, _d(out)))
-            return out[:self.nC]
-        p = _c(pairs, np.int32).reshape(-1, 2)
-        out = np.empty((p.shape[0], cnp, cnp))
-        self._ck(lib.psba_get_free_camera_covariance(self._h, p.shape[0], _i(p), _d(out)))
-        return out
+        return self._camera_blocks(lib.psba_get_free_camera_covariance, self._sizes()[0], pairs)
 
     def free_covariance_matrix(self):
         """psba_get_free_covariance_matrix: C_aa [nA, nA], symmetric; zero rows and columns for masked and held

@@ -1,5 +1,5 @@
-// api_common.h -- what the files of the C-ABI host layer share (psba_api.cpp, problem_options.cpp): the macros every
-// entry point opens with and the few helpers that cross the two files.
+// api_common.h -- what the files of the C-ABI host layer share (psba_api.cpp, problem_options.cpp, covariance.cpp):
+// the macros every entry point opens with and the few helpers that cross the files.
 #pragma once
 #include <vector>
 

@@ -1,8 +1,9 @@
-// free_blocks.h -- what the kernel files of the free-intrinsics route share (kernels_free.hip, kernels_freecov.hip):
+// free_blocks.h -- what the kernel files that serve the free-intrinsics route share (kernels_free.hip, kernels_cov.hip):
 // the two camera blocks the kernels are templated on, and the groups' tables with the predicate of a folded-away
-// coordinate.  Device code only.
+// coordinate.
 #pragma once
 #include "camera_model.h"
+#include "psba_internal.h"
 
 namespace psba {
 
@@ -43,6 +44,17 @@ struct KdGroups {
 __device__ __forceinline__ bool kd_folded(const KdGroups &G, int t) {  // t: coordinate of the camera part
   const int k = t % KD_CNP;
   return k < 10 && ((G.mask >> k) & 1u) && G.rep[t / KD_CNP] != t / KD_CNP;
+}
+// the handle's tables as a kernel argument
+inline KdGroups kd_groups(const psba_ctx *h) {
+  KdGroups G;
+  G.rep = h->kd_rep;
+  G.gidx = h->kd_gidx;
+  G.gptr = h->kd_gptr;
+  G.gmem = h->kd_gmem;
+  G.nmg = h->kd_nmg;
+  G.mask = h->kd_mask;
+  return G;
 }
 
 }  // namespace psba

@@ -872,17 +872,6 @@ __global__ __launch_bounds__(256) void k_kd_backsub_cams_groups(FreeBackArgs p, 
   free_block_sums4(v4, sRed, p.red);
 }
 
-static KdGroups kd_groups(psba_ctx *h) {
-  KdGroups G;
-  G.rep = h->kd_rep;
-  G.gidx = h->kd_gidx;
-  G.gptr = h->kd_gptr;
-  G.gmem = h->kd_gmem;
-  G.nmg = h->kd_nmg;
-  G.mask = h->kd_mask;
-  return G;
-}
-
 // (kd_mask and kd_rep are what the setters left: they refuse blocks of 11, which so keep all free and no groups)
 static FreeArgs free_args(psba_ctx *h, int set) {
   FreeArgs a;

@@ -23,7 +23,6 @@ void model_changed(psba_ctx *h) {
   h->free_obs = false;
   h->damp_ok = false;
   h->cov_ok = h->cov_pts_ok = false;
-  h->fcov_ok = h->fcov_pts_ok = false;
 }
 
 void params_changed(psba_ctx *h) {

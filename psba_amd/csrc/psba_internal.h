@@ -348,24 +348,20 @@ struct ProblemState {
   psba::DevBuf<double> chol_L;    // [(2 n32+16)][n32] panel chain: the Cholesky factor | forward-solved e_a row | L^-T
   psba::DevBuf<double> dist_buf;  // sharded factorization: packed column blocks of one super-panel (allocated on first use)
   psba::DevBuf<double> chol_ws;   // [ceil(nA/32)][32*32] inverses of the diagonal blocks of L (diagBlkAux_buffer)
-  // covariance of the estimate (psba_covariance_compute; kernels_cov.hip): workspaces of its own, allocated
-  // on first use -- the private copy of S that becomes its factor, the inverse, the inverses of the factor's diagonal
-  // tiles, Y_ij of the points, the 3 x 3 point blocks and the two status words (not SPD, singular V)
-  psba::DevBuf<double> cov_L, cov_C;  // [n32][n32] each
-  psba::DevBuf<double> cov_dinv;      // [n32 / 16][256]
+  // covariance of the estimate (psba_covariance_compute and psba_free_covariance_compute; covariance.cpp,
+  // kernels_cov.hip): one set of workspaces for every camera block, allocated on first use.  A handle
+  // has one camera model for its life, so one pair of flags serves both verb families; each family's getters refuse
+  // the other's handle by its camera block (cnp).  Y_ij of the points is cov_Y for blocks of 6, the route's free_Y else
+  psba::DevBuf<double> cov_A;         // [n32][n32] over one compute: compacted S -> its Cholesky factor -> C_aa, the result
+  psba::DevBuf<double> cov_X;         // [n32][n32] the lower triangle of the inverse (read by the finish alone)
+  psba::DevBuf<int> cov_src;          // [nA] -1 fixed, masked or held | itself: live | the representative's coordinate: folded away
+  psba::DevBuf<double> cov_dinv;      // [n32 / 16][256] inverses of the factor's diagonal tiles
   psba::DevBuf<double> cov_Y;         // [nO][18]
   psba::DevBuf<double> cov_pts;       // [nP][9]
-  psba::DevBuf<int> cov_status;       // [2]
-  bool cov_ok = false;                // cov_C is the camera covariance of the current parameters and model
+  psba::DevBuf<int> cov_status;       // [2] not SPD, singular V
+  bool cov_ok = false;                // cov_A is the camera covariance of the current parameters and model
   bool cov_pts_ok = false;            // ... and cov_pts the point blocks (not after reassemble = 0)
   double cov_ms[3] = {0.0, 0.0, 0.0}; // factor, inverse, points of the last compute (psba_covariance_times)
-  // ... with free intrinsics (psba_free_covariance_compute; kernels_freecov.hip): the workspaces above
-  // (cov_L, cov_C, cov_dinv, cov_pts, cov_status, cov_ms) are shared, Y is the route's own free_Y; the coordinate map
-  // and the expanded result are this route's, as are the two flags (the getters of 7h keep refusing a free handle)
-  psba::DevBuf<int> fcov_src;         // [nA] -1 masked or held | itself: live | the representative's coordinate: folded away
-  psba::DevBuf<double> fcov_C;        // [n32][n32] scale E X E^T
-  bool fcov_ok = false;               // fcov_C is the camera covariance of the current parameters and model
-  bool fcov_pts_ok = false;           // ... and cov_pts the point blocks (not after reassemble = 0)
   // debug dumps for the sba_func.h mirror (allocated on first use)
   psba::DevBuf<double> dbg_ex, dbg_JA, dbg_JB, dbg_Y, dbg_Vinv, dbg_eb;
 
@@ -508,15 +504,8 @@ int launch_publish_scal(psba_ctx *h, hipStream_t s);
 int launch_struct_only_try(psba_ctx *h, double mu);
 // kernels_cov.hip
 int launch_cov_cameras(psba_ctx *h, double scale, hipEvent_t *ev);
-int launch_cov_points(psba_ctx *h, double mu, double scale, bool with_C);
+int launch_cov_points(psba_ctx *h, double mu, double scale);
 int launch_cov_gather(psba_ctx *h, const int2 *pairs_dev, int n_pairs, double *out_dev);
-int cov_workspaces(psba_ctx *h);     // the stages of launch_cov_cameras between its compaction and its finish
-int launch_cov_factor(psba_ctx *h);
-int launch_cov_inverse(psba_ctx *h);
-// kernels_freecov.hip
-int launch_fcov_cameras(psba_ctx *h, double scale, hipEvent_t *ev);
-int launch_fcov_points(psba_ctx *h, double mu, double scale);
-int launch_fcov_gather(psba_ctx *h, const int2 *pairs_dev, int n_pairs, double *out_dev);
 int launch_fcov_sigmas(psba_ctx *h, double *sigma_dev);
 // kernels_tr.hip
 int launch_jmul(psba_ctx *h, const double *x1_dev, const double *x2_dev, double *out1_dev, double *dots_dev);

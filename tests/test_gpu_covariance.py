@@ -219,6 +219,26 @@ def test_inverse_against_extended_precision_inverse_of_the_devices_own_S(n):
     h.close()
 
 
+def test_fixed_cameras_away_from_the_leading_tile():
+    """Every other test here fixes cameras 0 and 1, whose coordinates 0 .. 11 lie inside the first 16 x 16 tile.  With
+    cameras 2 and 5 fixed the dead coordinates 12 .. 17 straddle the tile edge at 16 and 30 .. 35 the edge at 32, so a
+    wrong index on a fixed camera in the compaction or the finish shows."""
+    prob = _golden(7)
+    fc = np.zeros(7, dtype=np.uint8)
+    fc[[2, 5]] = 1
+    h = _handle(prob, fc, None)
+    free = np.repeat(fc == 0, 6)
+    h.linearize(1.0, 1.0)
+    for mu in (0.0, 1e-6 * h.max_diag()):
+        assert h.covariance(mu) == capi.PSBA_OK
+        _judge_inverse(h.covariance_matrix(), _S(h), free, f"cameras 2 and 5 fixed, mu = {mu:.3g}")
+        D = h.camera_covariance()
+        assert np.all(D[fc != 0] == 0.0) and np.all(np.einsum("jkk->jk", D[fc == 0]) > 0.0)
+        P = h.point_covariance()
+        assert np.array_equal(P, np.transpose(P, (0, 2, 1)))
+    h.close()
+
+
 # ---- 3. chosen matrices through reassemble = 0 -----------------------------------------------------------------------
 def test_chosen_matrices_through_reassemble_0():
     prob = _golden(54)
