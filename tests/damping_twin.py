@@ -6,12 +6,12 @@ TwinKD (tests/freekd_twin.py) with N + mu D in the place of N + mu I.
     point system V + mu diag(D_b), camera diagonal U_kk + mu D_k, gain_den = dp . (mu D dp + g)
     levmar: mu_0 = tau (not tau max diag), everything else lm_loop.cpp as TwinKD.levmar restates it
 
-With D = 1 and mu_0 = tau max diag the loop below is TwinKD.levmar operation by operation (the test pins the logs
-equal), so the two rules differ in the twin by exactly what they differ by in the library.
+The loop is TwinKD.levmar itself: TwinDamp overrides only its starting mu and the D of a linearization, so the two rules
+differ in the twin by exactly what they differ by in the library (the test pins the logs of the identity rule equal).
 """
 import numpy as np
 
-from freekd_twin import CNP, LmResult, TwinKD
+from freekd_twin import CNP, TwinKD
 
 DMIN, DMAX = 1e-6, 1e32     # the defaults of psba_set_damping
 IDENTITY, MARQUARDT = 0, 1
@@ -49,63 +49,16 @@ class TwinDamp(TwinKD):
         ea = g[:nA] - N[:nA, nA:] @ X[:, nA]
         return S, ea
 
+    damping, dmin, dmax = IDENTITY, DMIN, DMAX    # the rule of the levmar in progress
+
+    def start_mu(self, tau, N):
+        return tau if self.damping == MARQUARDT else super().start_mu(tau, N)
+
+    def damping_diag(self, N):
+        return damp_diag(N, self.dmin, self.dmax) if self.damping == MARQUARDT else super().damping_diag(N)
+
     def levmar(self, max_iter=20, init_mu=0.0, stop_small=True, damping=MARQUARDT, dmin=DMIN, dmax=DMAX):
         """TwinKD.levmar with N + mu D.  damping = IDENTITY: D = 1 and mu_0 = tau max diag (the log of TwinKD.levmar);
         MARQUARDT: D = damp_diag(N) of every linearization and mu_0 = tau."""
-        STOP, EPS_SQ = 1e-12, 1e-24
-        tau = init_mu if init_mu != 0.0 else 1e-3
-        res, log = LmResult(), []
-        ex, N, g = self.normal()
-        res.init_err = ex
-        mu, nu, p_L2, first, flag, tries = 0.0, 2, 0.0, True, 0, 0
-        itno = 0
-        while itno < max_iter and flag == 0:
-            if not first:
-                _, N, g = self.normal()
-            else:
-                mu0 = tau if damping == MARQUARDT else tau * self.max_diag(N)
-                mu, p_L2, nu, first = mu0, 1e3, 2, False
-                res.mu0 = mu
-            D = damp_diag(N, dmin, dmax) if damping == MARQUARDT else np.ones(self.nT)
-            while True:
-                tries += 1
-                try:
-                    L = np.linalg.cholesky(N + mu * np.diag(D))
-                    dp = np.linalg.solve(L.T, np.linalg.solve(L, g))
-                except np.linalg.LinAlgError:
-                    dp = None
-                if dp is not None:
-                    dp[:self.nA][~self.free_a] = 0.0
-                    dp_L2 = float(dp @ dp)
-                    if dp_L2 < p_L2 * STOP * STOP:
-                        flag = 1
-                        break
-                    if dp_L2 >= (p_L2 + STOP) / EPS_SQ:
-                        flag = 2
-                        break
-                    newc = self.cams + dp[:self.nA].reshape(self.nC, CNP)
-                    newp = self.pts + dp[self.nA:].reshape(self.nP, 3)
-                    new_ex = self.cost(newc, newp)
-                    rho = (ex - new_ex) / float(dp @ ((mu * D) * dp + g))
-                    log.append([itno, new_ex, rho, mu, 1.0 if rho > 0 else 0.0])
-                    if rho > 0:
-                        tmp = 2 * rho - 1
-                        tmp = 1.0 - tmp * tmp * tmp
-                        mu *= tmp if tmp >= 1.0 / 3.0 else 1.0 / 3.0
-                        nu = 2
-                        self.cams, self.pts = newc, newp
-                        p_L2 = float((newc * newc).sum() + (newp * newp).sum())
-                        ex = new_ex
-                        break
-                else:
-                    log.append([itno, np.nan, np.nan, mu, -1.0])
-                mu *= nu
-                if 2.0 * nu > 1e9:
-                    flag = 2
-                    break
-                nu *= 2
-            if stop_small and ex <= STOP:
-                flag = 3
-            itno += 1
-        res.flag, res.iters, res.tries, res.final_err, res.mu_final = flag, itno, tries, ex, mu
-        return res, np.asarray(log).reshape(-1, 5)
+        self.damping, self.dmin, self.dmax = damping, dmin, dmax
+        return super().levmar(max_iter, init_mu, stop_small)

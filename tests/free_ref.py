@@ -71,7 +71,7 @@ import numpy as np
 
 import assembly_ref as ar
 import dense_ref as dr
-from freekd_twin import CNP, TwinKD, start_kc
+from freekd_twin import CNP, TwinKD, ldl_rows, obs_by_point, start_kc
 
 LD = ar.LD
 ALL = (1,) * 10
@@ -123,9 +123,19 @@ class Route:
         self.nA, self.nB = cnp * self.nC, 3 * self.nP
         self.nT = self.nA + self.nB
         # rows / columns of the twin's 16-wide camera part that this route has
-        sel = np.arange(CNP) if cnp == 16 else SEL11
-        self.rows = (CNP * np.arange(self.nC)[:, None] + sel[None, :]).reshape(-1)
+        self.sel = np.arange(CNP) if cnp == 16 else SEL11
+        self.rows = (CNP * np.arange(self.nC)[:, None] + self.sel[None, :]).reshape(-1)
         self.held = np.flatnonzero(~self.twin.free_a[self.rows])
+        self.held_pts = np.zeros(self.nP, dtype=bool)        # (held_ref's routes hold points; schur_blocks skips them)
+
+    def current(self):
+        """the twin's current parameters as this route has them: (cams [nC, cnp], pts [nP, 3])"""
+        return self.twin.cams[:, self.sel].copy(), self.twin.pts.copy()
+
+    def schur_start(self, dtype, fault=None):
+        """what schur_blocks adds the observations' sums to: (U, g_a, V, g_b), zero without priors"""
+        return (np.zeros((self.nC, self.cnp, self.cnp), dtype), np.zeros((self.nC, self.cnp), dtype),
+                np.zeros((self.nP, 3, 3), dtype), np.zeros((self.nP, 3), dtype))
 
     def cams16(self, cams):
         """[nC, cnp] of this route -> the twin's [nC, 16]"""
@@ -139,7 +149,7 @@ class Route:
     def blocks(self):
         """e [nO, 2], A [nO, 2, cnp], B [nO, 2, 3], proj [nO, 2] at the start"""
         e, A, B = self.twin.linearize()
-        return e, A[:, :, np.arange(CNP) if self.cnp == 16 else SEL11], B, self.twin.t.m - e
+        return e, A[:, :, self.sel], B, self.twin.t.m - e
 
     def residuals(self, cams, pts):
         """fp64 residuals [nO, 2] and projections at (cams [nC, cnp], pts)"""
@@ -241,48 +251,43 @@ def check_damp_diag(D, sm_diag, envN, rule, held, coeff=1.0):
     return ratio, k, int(low.sum()), int(high.sum())
 
 
-def schur_blocks(rt, mu, D, camera=True, dtype=np.longdouble):
+def block_diagonal(U):
+    """[nA, nA] with the blocks U [nC, cnp, cnp] on its diagonal, in U's dtype"""
+    nC, cnp, _ = U.shape
+    S = np.zeros((nC * cnp, nC * cnp), U.dtype)
+    for j in range(nC):
+        S[cnp * j:cnp * j + cnp, cnp * j:cnp * j + cnp] = U[j]
+    return S
+
+
+def schur_blocks(rt, mu, D, camera=True, dtype=np.longdouble, coeff=1.0, fault=None):
     """TwinKD.schur_blocks restated on the route's own columns for N + mu diag(D): S [nA, nA] and e_a with every sum in
     `dtype` (80-bit), U_kk + mu D_k (camera=False: the camera diagonal is left undamped, for the fold of shared_ref)
-    and V_i + mu diag(D_i); the placeholder 1 at held coordinates."""
+    and V_i + mu diag(D_i); the placeholder coeff at held coordinates.  The one restatement for every route of the
+    free-intrinsics references; what differs is asked of the route: rt.held_pts (a held point is skipped: its W is
+    zero, so it contributes nothing, and at mu = 0 its V is singular) and rt.schur_start (the prior terms the sums start
+    from, with prior_ref's faults).  Under the identity rule D is all ones and mu D is mu exactly."""
     e, A, B, _ = rt.blocks()
     e, A, B = e.astype(dtype), A.astype(dtype), B.astype(dtype)
-    nC, nP, cnp, nA = rt.nC, rt.nP, rt.cnp, rt.nA
+    cnp, nA = rt.cnp, rt.nA
     D = np.asarray(D, dtype=np.float64).astype(dtype)
     mu = dtype(mu)
-    U = np.zeros((nC, cnp, cnp), dtype)
-    ga = np.zeros((nC, cnp), dtype)
+    U, ga, V, gb = rt.schur_start(dtype, fault)
     np.add.at(U, rt.j, np.einsum("nri,nrk->nik", A, A))
     np.add.at(ga, rt.j, np.einsum("nri,nr->ni", A, e))
-    V = np.zeros((nP, 3, 3), dtype)
-    gb = np.zeros((nP, 3), dtype)
     np.add.at(V, rt.i, np.einsum("nri,nrk->nik", B, B))
     np.add.at(gb, rt.i, np.einsum("nri,nr->ni", B, e))
     W = np.einsum("nri,nrk->nik", A, B)
-    S = np.zeros((nA, nA), dtype)
-    for j in range(nC):
-        S[cnp * j:cnp * j + cnp, cnp * j:cnp * j + cnp] = U[j]
-    S[rt.held, rt.held] = 1
+    S = block_diagonal(U)
+    S[rt.held, rt.held] = dtype(coeff)
     if camera:
         S[np.arange(nA), np.arange(nA)] += mu * D[:nA]
     ea = ga.reshape(-1).copy()
-    order = np.argsort(rt.i, kind="stable")
-    ptr = np.searchsorted(rt.i[order], np.arange(nP + 1))
-    for i in range(nP):
-        obs = order[ptr[i]:ptr[i + 1]]
-        if obs.size == 0:
+    for i, obs in obs_by_point(rt.i, rt.nP):
+        if rt.held_pts[i]:
             continue
-        v = V[i] + np.diag(mu * D[nA + 3 * i:nA + 3 * i + 3])
-        l10, l20 = v[0, 1] / v[0, 0], v[0, 2] / v[0, 0]
-        d1 = v[1, 1] - l10 * v[0, 1]
-        l21 = (v[1, 2] - l20 * v[0, 1]) / d1
-        d2 = v[2, 2] - l20 * v[0, 2] - l21 * l21 * d1
         Wi = W[obs].reshape(-1, 3)
-        z1 = Wi[:, 1] - l10 * Wi[:, 0]
-        z2 = Wi[:, 2] - l20 * Wi[:, 0] - l21 * z1
-        y2 = z2 / d2
-        y1 = z1 / d1 - l21 * y2
-        Yi = np.stack([Wi[:, 0] / v[0, 0] - l10 * y1 - l20 * y2, y1, y2], 1)
+        Yi = ldl_rows(V[i] + np.diag(mu * D[nA + 3 * i:nA + 3 * i + 3]), Wi)
         rows = (cnp * rt.j[obs][:, None] + np.arange(cnp)[None, :]).reshape(-1)
         S[np.ix_(rows, rows)] -= Yi @ Wi.T
         ea[rows] -= Yi @ gb[i]
@@ -425,79 +430,93 @@ def plain_damp_diag(rt, U, V, rule, fault=None):
     return D
 
 
-def plain_schur(rt, mu, point_solve=ldl_solve, rule=NO_RULE, fault=None):
-    """S [nA, nA], e_a, and the pieces (V*, W, g) in fp64 from the twin's blocks, Y = W V*^-1 by `point_solve`"""
-    if rule.marquardt:
-        return plain_schur_damped(rt, mu, rule, fault)
-    e, A, B, _ = rt.blocks()
-    nC, nP, cnp, nA = rt.nC, rt.nP, rt.cnp, rt.nA
-    U = np.zeros((nC, cnp, cnp))
+def plain_sums(rt, e, A, B, prior=None):
+    """K1 in fp64 numpy: U [nC, cnp, cnp], g_a, V [nP, 3, 3], g_b and W [nO, cnp, 3] of the blocks; prior = (L, L d, G,
+    G d) is added to the four sums (prior_ref)"""
+    U = np.zeros((rt.nC, rt.cnp, rt.cnp))
     np.add.at(U, rt.j, np.einsum("ari,ark->aik", A, A))
-    ga = np.zeros((nC, cnp))
+    ga = np.zeros((rt.nC, rt.cnp))
     np.add.at(ga, rt.j, np.einsum("ari,ar->ai", A, e))
-    V = np.zeros((nP, 3, 3))
+    V = np.zeros((rt.nP, 3, 3))
     np.add.at(V, rt.i, np.einsum("ari,ark->aik", B, B))
-    gb = np.zeros((nP, 3))
+    gb = np.zeros((rt.nP, 3))
     np.add.at(gb, rt.i, np.einsum("ari,ar->ai", B, e))
-    W = np.einsum("ark,arc->akc", A, B)
-    Vs = V + mu * np.eye(3)[None]
-    Y = point_solve(Vs[rt.i], W)
-    S = np.zeros((nA, nA))
-    for j in range(nC):
-        S[cnp * j:cnp * j + cnp, cnp * j:cnp * j + cnp] = U[j]
-    S[rt.held, rt.held] = 1.0
-    S[np.arange(nA), np.arange(nA)] += mu
-    ea = ga.reshape(-1).copy()
-    order = np.argsort(rt.i, kind="stable")
-    ptr = np.searchsorted(rt.i[order], np.arange(nP + 1))
-    for i in range(nP):
-        obs = order[ptr[i]:ptr[i + 1]]
-        if obs.size == 0:
-            continue
-        rows = (cnp * rt.j[obs][:, None] + np.arange(cnp)[None, :]).reshape(-1)
-        S[np.ix_(rows, rows)] -= Y[obs].reshape(-1, 3) @ W[obs].reshape(-1, 3).T
-        ea[rows] -= Y[obs].reshape(-1, 3) @ gb[i]
-    return S, ea, dict(Vs=Vs, W=W, g=np.concatenate([ga.reshape(-1), gb.reshape(-1)]))
+    if prior is not None:
+        U += prior[0]
+        ga += prior[1]
+        V += prior[2]
+        gb += prior[3]
+    return U, ga, V, gb, np.einsum("ark,arc->akc", A, B)
 
 
-def plain_schur_damped(rt, mu, rule, fault=None, camera=True):
-    """plain_schur under Marquardt's rule: U_kk + mu D_k (camera=False: left undamped, for shared_ref's fold),
-    V_i + mu diag(D_i), D by plain_damp_diag; pieces as plain_schur's, D and the stored diagonal dU of U (placeholder
-    1 at held coordinates).  numpy rounds the product mu D_r and the sum where damp_point_block has one fma."""
-    e, A, B, _ = rt.blocks()
-    nC, nP, cnp, nA = rt.nC, rt.nP, rt.cnp, rt.nA
-    U = np.zeros((nC, cnp, cnp))
-    np.add.at(U, rt.j, np.einsum("ari,ark->aik", A, A))
-    ga = np.zeros((nC, cnp))
-    np.add.at(ga, rt.j, np.einsum("ari,ar->ai", A, e))
-    V = np.zeros((nP, 3, 3))
-    np.add.at(V, rt.i, np.einsum("ari,ark->aik", B, B))
-    gb = np.zeros((nP, 3))
-    np.add.at(gb, rt.i, np.einsum("ari,ar->ai", B, e))
-    W = np.einsum("ark,arc->akc", A, B)
-    D = plain_damp_diag(rt, U, V, rule, fault)
+def plain_scatter(rt, U, dU, ga, V, gb, W, mu, D, point_solve=ldl_solve, camera=True):
+    """The Schur assembly in fp64 numpy: V* = V + mu diag(D_b), Y = W V*^-1 by `point_solve`, S from the blocks U with
+    dU + mu D_a on its diagonal (dU [nA]: the stored diagonal, placeholders included; camera=False: dU alone), then
+    Y W^T and Y g_b of every point taken off S and e_a.  numpy rounds the product mu D_r and the sum where
+    damp_point_block has one fma.  Returns (S, e_a, V*)."""
+    cnp, nA = rt.cnp, rt.nA
     k3 = np.arange(3)
     Vs = V.copy()
     Vs[:, k3, k3] += mu * D[nA:].reshape(-1, 3)
     with np.errstate(divide="ignore", invalid="ignore"):
-        Y = ldl_solve(Vs[rt.i], W)
-    S = np.zeros((nA, nA))
-    for j in range(nC):
-        S[cnp * j:cnp * j + cnp, cnp * j:cnp * j + cnp] = U[j]
-    S[rt.held, rt.held] = 1.0
-    dU = np.diag(S).copy()
-    if camera:
-        S[np.arange(nA), np.arange(nA)] += mu * D[:nA]
+        Y = point_solve(Vs[rt.i], W)
+    S = block_diagonal(U)
+    S[np.arange(nA), np.arange(nA)] = dU + mu * D[:nA] if camera else dU
     ea = ga.reshape(-1).copy()
-    order = np.argsort(rt.i, kind="stable")
-    ptr = np.searchsorted(rt.i[order], np.arange(nP + 1))
-    for i in range(nP):
-        obs = order[ptr[i]:ptr[i + 1]]
-        if obs.size == 0:
-            continue
+    for i, obs in obs_by_point(rt.i, rt.nP):
         rows = (cnp * rt.j[obs][:, None] + np.arange(cnp)[None, :]).reshape(-1)
         S[np.ix_(rows, rows)] -= Y[obs].reshape(-1, 3) @ W[obs].reshape(-1, 3).T
         ea[rows] -= Y[obs].reshape(-1, 3) @ gb[i]
+    return S, ea, Vs
+
+
+def plain_solve(S, ea, fallback=False):
+    """dp_a of S dp_a = e_a by a Cholesky factorization of S scaled by its own diagonal (fallback: by LU where a
+    faulted S is not positive definite)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = 1.0 / np.sqrt(np.diag(S))
+        try:
+            L = np.linalg.cholesky(d[:, None] * S * d[None, :])
+        except np.linalg.LinAlgError:
+            if not fallback:
+                raise
+            return np.linalg.solve(S, ea)
+    return d * np.linalg.solve(L.T, np.linalg.solve(L, d * ea))
+
+
+def plain_finish(rt, S, ea, pc, dpa, mu, D, hold_b=None, keep=None, gain_den=None):
+    """The rest of a try from the camera step dpa [nA] (per camera, the held entries cleared by the caller): dp_b by
+    L D L^T against pc["Vs"] (zero at the points hold_b), the proposal and the four sums.  keep: the mask of the
+    parameters that count in dp_l2 and newp_l2 (shared_ref: every distinct one once); gain_den(dp, counted dp): the
+    caller's own sum where dp . (mu D dp + g) is not it."""
+    cnp, nA = rt.cnp, rt.nA
+    eb = pc["g"][nA:].reshape(-1, 3).copy()
+    np.subtract.at(eb, rt.i, np.einsum("akc,ak->ac", pc["W"], dpa.reshape(-1, cnp)[rt.j]))
+    dpb = ldl_solve(pc["Vs"], eb[:, None, :])[:, 0, :]
+    if hold_b is not None:
+        dpb[hold_b] = 0.0
+    dp = np.concatenate([dpa, dpb.reshape(-1)])
+    cams, pts = rt.current()
+    newcams, newpts = cams + dpa.reshape(-1, cnp), pts + dpb
+    e_new, _ = rt.residuals(newcams, newpts)
+    newp = np.concatenate([newcams.reshape(-1), newpts.reshape(-1)])
+    dr_, nr_ = (dp, newp) if keep is None else (dp[keep], newp[keep])
+    gd = dp @ ((mu * D) * dp + pc["g"]) if gain_den is None else gain_den(dp, dr_)
+    sc = dict(dp_l2=float(dr_ @ dr_), gain_den=float(gd), newp_l2=float(nr_ @ nr_),
+              new_cost=float((e_new * e_new).sum()))
+    return dict(S=S, ea=ea, dp=dp, newcams=newcams, newpts=newpts, sc=sc)
+
+
+def plain_schur(rt, mu, point_solve=ldl_solve, rule=NO_RULE, fault=None, camera=True):
+    """S [nA, nA], e_a, and the pieces in fp64 from the twin's blocks, Y = W V*^-1 by `point_solve`: V* (Vs), V, W, g,
+    D (plain_damp_diag under Marquardt's rule, ones under the identity: mu D is mu exactly) and the stored diagonal dU
+    of U (placeholder 1 at held coordinates).  camera=False leaves U_kk undamped, for shared_ref's fold."""
+    U, ga, V, gb, W = plain_sums(rt, *rt.blocks()[:3])
+    D = plain_damp_diag(rt, U, V, rule, fault) if rule.marquardt else np.ones(rt.nT)
+    k = np.arange(rt.cnp)
+    dU = U[:, k, k].reshape(-1)
+    dU[rt.held] = 1.0
+    S, ea, Vs = plain_scatter(rt, U, dU, ga, V, gb, W, mu, D, point_solve, camera)
     return S, ea, dict(Vs=Vs, V=V, W=W, g=np.concatenate([ga.reshape(-1), gb.reshape(-1)]), D=D, dU=dU)
 
 
@@ -505,42 +524,10 @@ def plain_try(rt, mu, rule=NO_RULE, fault=None):
     """One damping try in plain fp64: dp [nT] (dp_a by a Cholesky of the scaled S, dp_b by L D L^T), the proposal and
     the four sums.  Under Marquardt's rule also D; fault "backsub-identity": dp_b solved with V + mu I while Y was
     made with V + mu D (the others are plain_damp_diag's)."""
-    if rule.marquardt:
-        return plain_try_damped(rt, mu, rule, fault)
-    S, ea, pc = plain_schur(rt, mu)
-    d = 1.0 / np.sqrt(np.diag(S))
-    L = np.linalg.cholesky(d[:, None] * S * d[None, :])
-    dpa = d * np.linalg.solve(L.T, np.linalg.solve(L, d * ea))
+    S, ea, pc = plain_schur(rt, mu, rule=rule, fault=fault)
+    dpa = plain_solve(S, ea)
     dpa[rt.held] = 0.0
-    eb = pc["g"][rt.nA:].reshape(-1, 3).copy()
-    np.subtract.at(eb, rt.i, np.einsum("akc,ak->ac", pc["W"], dpa.reshape(-1, rt.cnp)[rt.j]))
-    dpb = ldl_solve(pc["Vs"], eb[:, None, :])[:, 0, :]
-    dp = np.concatenate([dpa, dpb.reshape(-1)])
-    cams = rt.twin.cams[:, np.arange(CNP) if rt.cnp == 16 else SEL11]
-    newcams, newpts = cams + dpa.reshape(-1, rt.cnp), rt.twin.pts + dpb
-    e_new, _ = rt.residuals(newcams, newpts)
-    newp = np.concatenate([newcams.reshape(-1), newpts.reshape(-1)])
-    sc = dict(dp_l2=float(dp @ dp), gain_den=float(dp @ (mu * dp + pc["g"])), newp_l2=float(newp @ newp),
-              new_cost=float((e_new * e_new).sum()))
-    return dict(S=S, ea=ea, dp=dp, newcams=newcams, newpts=newpts, sc=sc)
-
-
-def plain_try_damped(rt, mu, rule, fault=None):
-    S, ea, pc = plain_schur_damped(rt, mu, rule, fault)
-    D = pc["D"]
-    d = 1.0 / np.sqrt(np.diag(S))
-    L = np.linalg.cholesky(d[:, None] * S * d[None, :])
-    dpa = d * np.linalg.solve(L.T, np.linalg.solve(L, d * ea))
-    dpa[rt.held] = 0.0
-    eb = pc["g"][rt.nA:].reshape(-1, 3).copy()
-    np.subtract.at(eb, rt.i, np.einsum("akc,ak->ac", pc["W"], dpa.reshape(-1, rt.cnp)[rt.j]))
-    Vs = pc["V"] + mu * np.eye(3)[None] if fault == "backsub-identity" else pc["Vs"]
-    dpb = ldl_solve(Vs, eb[:, None, :])[:, 0, :]
-    dp = np.concatenate([dpa, dpb.reshape(-1)])
-    cams = rt.twin.cams[:, np.arange(CNP) if rt.cnp == 16 else SEL11]
-    newcams, newpts = cams + dpa.reshape(-1, rt.cnp), rt.twin.pts + dpb
-    e_new, _ = rt.residuals(newcams, newpts)
-    newp = np.concatenate([newcams.reshape(-1), newpts.reshape(-1)])
-    sc = dict(dp_l2=float(dp @ dp), gain_den=float(dp @ ((mu * D) * dp + pc["g"])), newp_l2=float(newp @ newp),
-              new_cost=float((e_new * e_new).sum()))
-    return dict(S=S, ea=ea, dp=dp, newcams=newcams, newpts=newpts, sc=sc, D=D)
+    if fault == "backsub-identity":
+        pc["Vs"] = pc["V"] + mu * np.eye(3)[None]
+    out = plain_finish(rt, S, ea, pc, dpa, mu, pc["D"])
+    return dict(out, D=pc["D"]) if rule.marquardt else out

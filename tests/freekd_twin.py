@@ -10,6 +10,11 @@ Built on lens_twin.Twin (projection, the six extrinsic columns and B); this file
 a dense J, N = J^T J with the placeholder 1 on the diagonal of masked coordinates, S and e_a by a dense solve of the
 point block, and a dense LM that restates the damping and accept rules of psba_amd/csrc/lm_loop.cpp.  Formulated
 differently from the HIP route on purpose: one dense matrix, no blocks, no Schur elimination inside the LM.
+
+Two things live here once for every reference of the free-intrinsics routes: TwinKD.levmar, the LM loop that
+damping_twin.TwinDamp, held_ref.HeldTwin (and prior_ref.PriorTwin, weight_ref.WeightTwin on it) and shared_ref.SharedTwin
+specialise by overriding system, start_mu, damping_diag, solve_step, proposal and norm2; and ldl_rows, the per-point L D L^T
+substitution of the 80-bit Schur restatements.
 """
 import numpy as np
 
@@ -131,56 +136,64 @@ class TwinKD:
             for k in np.flatnonzero(~self.free):
                 Uj[k, k] = 1
             S[CNP * j:CNP * j + CNP, CNP * j:CNP * j + CNP] = Uj + dtype(mu) * np.eye(CNP, dtype=dtype)
-        order = np.argsort(self.i, kind="stable")
-        bounds = np.searchsorted(self.i[order], np.arange(nP + 1))
-        for i in range(nP):
-            obs = order[bounds[i]:bounds[i + 1]]
-            if obs.size == 0:
-                continue
-            # Y = W (V + mu I)^-1 by L D L^T and substitution: backward stable per row, so a nearly singular block
-            # (a point seen once, small mu) does not amplify rounding the way a product with its inverse would
-            v = V[i] + dtype(mu) * np.eye(3, dtype=dtype)
-            l10, l20 = v[0, 1] / v[0, 0], v[0, 2] / v[0, 0]
-            d1 = v[1, 1] - l10 * v[0, 1]
-            l21 = (v[1, 2] - l20 * v[0, 1]) / d1
-            d2 = v[2, 2] - l20 * v[0, 2] - l21 * l21 * d1
+        for i, obs in obs_by_point(self.i, nP):
             Wi = W[obs].reshape(-1, 3)                 # rows: (observation, parameter)
-            z1 = Wi[:, 1] - l10 * Wi[:, 0]
-            z2 = Wi[:, 2] - l20 * Wi[:, 0] - l21 * z1
-            y2 = z2 / d2
-            y1 = z1 / d1 - l21 * y2
-            Yi = np.stack([Wi[:, 0] / v[0, 0] - l10 * y1 - l20 * y2, y1, y2], 1)
+            Yi = ldl_rows(V[i] + dtype(mu) * np.eye(3, dtype=dtype), Wi)
             rows = (CNP * self.j[obs][:, None] + np.arange(CNP)[None, :]).reshape(-1)
             S[np.ix_(rows, rows)] -= Yi @ Wi.T
             ea[rows] -= Yi @ gb[i]
         return S, ea
 
+    # ---- what levmar asks of the twin: a subclass overrides these, never the loop ----
+    def system(self):
+        """(cost, N, g) of the current parameters in the numbering of the loop"""
+        return self.normal()
+
+    def start_mu(self, tau, N):
+        return tau * self.max_diag(N)
+
+    def damping_diag(self, N):
+        """D [n] of a linearization: the system solved is N + mu diag(D)"""
+        return np.ones(N.shape[0])
+
+    def solve_step(self, N, g, mu, D):
+        """dp of (N + mu diag(D)) dp = g by a Cholesky factorization, None when it breaks down"""
+        dp = cholesky_solve(N + mu * np.diag(D), g)
+        if dp is not None:
+            dp[:self.nA][~self.free_a] = 0.0
+        return dp
+
+    def proposal(self, dp):
+        return self.cams + dp[:self.nA].reshape(self.nC, CNP), self.pts + dp[self.nA:].reshape(self.nP, 3)
+
+    def norm2(self, cams, pts):
+        """|p|^2 of the loop's p_L2"""
+        return float((cams * cams).sum() + (pts * pts).sum())
+
     def levmar(self, max_iter=20, init_mu=0.0, stop_small=True):
         """psba_amd/csrc/lm_loop.cpp restated (tr_handoff off): Nielsen's mu / nu update, the same stop tests, one
         log row (itno, cost after the try, rho, mu, accepted) per damping try.  stop_small=False leaves out the
-        loop's absolute stop (cost <= 1e-12), which ends a noise-free problem before fp64 is used up."""
+        loop's absolute stop (cost <= 1e-12), which ends a noise-free problem before fp64 is used up.  The only LM
+        loop of the free-intrinsics twins: the system is system() (normal() here), everything else that differs between them is one of
+        the methods above, and dp, g and D live in whatever numbering those methods share."""
         STOP, EPS_SQ = 1e-12, 1e-24
         tau = init_mu if init_mu != 0.0 else 1e-3
         res, log = LmResult(), []
-        ex, N, g = self.normal()
+        ex, N, g = self.system()
         res.init_err = ex
         mu, nu, p_L2, first, flag, tries = 0.0, 2, 0.0, True, 0, 0
         itno = 0
         while itno < max_iter and flag == 0:
             if not first:
-                _, N, g = self.normal()
+                _, N, g = self.system()
             else:
-                mu, p_L2, nu, first = tau * self.max_diag(N), 1e3, 2, False
+                mu, p_L2, nu, first = self.start_mu(tau, N), 1e3, 2, False
                 res.mu0 = mu
+            D = self.damping_diag(N)
             while True:
                 tries += 1
-                try:
-                    L = np.linalg.cholesky(N + mu * np.eye(self.nT))
-                    dp = np.linalg.solve(L.T, np.linalg.solve(L, g))
-                except np.linalg.LinAlgError:
-                    dp = None
+                dp = self.solve_step(N, g, mu, D)
                 if dp is not None:
-                    dp[:self.nA][~self.free_a] = 0.0
                     dp_L2 = float(dp @ dp)
                     if dp_L2 < p_L2 * STOP * STOP:
                         flag = 1
@@ -188,10 +201,9 @@ class TwinKD:
                     if dp_L2 >= (p_L2 + STOP) / EPS_SQ:
                         flag = 2
                         break
-                    newc = self.cams + dp[:self.nA].reshape(self.nC, CNP)
-                    newp = self.pts + dp[self.nA:].reshape(self.nP, 3)
+                    newc, newp = self.proposal(dp)
                     new_ex = self.cost(newc, newp)
-                    rho = (ex - new_ex) / float(dp @ (mu * dp + g))
+                    rho = (ex - new_ex) / float(dp @ ((mu * D) * dp + g))
                     log.append([itno, new_ex, rho, mu, 1.0 if rho > 0 else 0.0])
                     if rho > 0:
                         tmp = 2 * rho - 1
@@ -199,7 +211,7 @@ class TwinKD:
                         mu *= tmp if tmp >= 1.0 / 3.0 else 1.0 / 3.0
                         nu = 2
                         self.cams, self.pts = newc, newp
-                        p_L2 = float((newc * newc).sum() + (newp * newp).sum())
+                        p_L2 = self.norm2(newc, newp)
                         ex = new_ex
                         break
                 else:
@@ -214,6 +226,40 @@ class TwinKD:
             itno += 1
         res.flag, res.iters, res.tries, res.final_err, res.mu_final = flag, itno, tries, ex, mu
         return res, np.asarray(log).reshape(-1, 5)
+
+
+def cholesky_solve(M, g):
+    """M^-1 g through M = L L^T, None when the factorization breaks down"""
+    try:
+        L = np.linalg.cholesky(M)
+    except np.linalg.LinAlgError:
+        return None
+    return np.linalg.solve(L.T, np.linalg.solve(L, g))
+
+
+def obs_by_point(i, nP):
+    """(point, indices of its observations in their given order) for every point that has any"""
+    order = np.argsort(i, kind="stable")
+    ptr = np.searchsorted(i[order], np.arange(nP + 1))
+    for k in range(nP):
+        if ptr[k + 1] > ptr[k]:
+            yield k, order[ptr[k]:ptr[k + 1]]
+
+
+def ldl_rows(v, Wi):
+    """Y = Wi v^-1 for a symmetric v [3, 3] and rows Wi [n, 3], by L D L^T and substitution in the operands' dtype:
+    backward stable per row, so a nearly singular block (a point seen once, small mu) does not amplify rounding the way
+    a product with its inverse would.  The one statement of it for every 80-bit reference of the free-intrinsics
+    routes (TwinKD.schur_blocks, free_ref.schur_blocks)."""
+    l10, l20 = v[0, 1] / v[0, 0], v[0, 2] / v[0, 0]
+    d1 = v[1, 1] - l10 * v[0, 1]
+    l21 = (v[1, 2] - l20 * v[0, 1]) / d1
+    d2 = v[2, 2] - l20 * v[0, 2] - l21 * l21 * d1
+    z1 = Wi[:, 1] - l10 * Wi[:, 0]
+    z2 = Wi[:, 2] - l20 * Wi[:, 0] - l21 * z1
+    y2 = z2 / d2
+    y1 = z1 / d1 - l21 * y2
+    return np.stack([Wi[:, 0] / v[0, 0] - l10 * y1 - l20 * y2, y1, y2], 1)
 
 
 # ---- the test problems of tests/test_freekd_*.py ----

@@ -11,15 +11,16 @@ HeldRoute is free_ref.Route with the zeroed blocks and `held` extended by the po
 free_ref.py (sums, damp_ref, scale_diag, check_exact_parts, dpb_residual, scalars, solve_judge) applies unchanged with
 its constants; HeldSharedRoute is the same on shared_ref.SharedRoute.  The point placeholders, which free_ref has no
 notion of, are patched in by sums() below (V = coeff I, g_b = 0, zero envelopes; the diagonals `dampings` and damp_ref
-read patched the same way).  schur_blocks restates free_ref.schur_blocks with the held points skipped (their W is zero:
-they contribute nothing, and at mu = 0 their V of the sums is singular), and serves both damping rules: under the
-identity rule D is all ones and mu D is mu exactly."""
+read patched the same way).  schur_blocks IS free_ref.schur_blocks, which skips the points the route holds (their W is
+zero: they contribute nothing, and at mu = 0 their V of the sums is singular) and serves both damping rules; plain_try
+is assembled from free_ref's plain_sums, plain_scatter, plain_solve and plain_finish around its own fault switches; and
+HeldTwin is TwinKD's LM loop with the solve of a step overridden."""
 import numpy as np
 
 import assembly_ref as ar
 import free_ref as fr
 import shared_ref as sr
-from freekd_twin import CNP, LmResult, TwinKD
+from freekd_twin import CNP, TwinKD, cholesky_solve
 
 LD = ar.LD
 
@@ -123,50 +124,7 @@ def damp_ref(rt, sm, rule=fr.NO_RULE):
     return D, env
 
 
-def schur_blocks(rt, mu, D, camera=True, dtype=np.longdouble, coeff=1.0):
-    """free_ref.schur_blocks on the held route's blocks; a held point is skipped (W = 0: no contribution)"""
-    e, A, B, _ = rt.blocks()
-    e, A, B = e.astype(dtype), A.astype(dtype), B.astype(dtype)
-    nC, nP, cnp, nA = rt.nC, rt.nP, rt.cnp, rt.nA
-    D = np.asarray(D, dtype=np.float64).astype(dtype)
-    mu = dtype(mu)
-    U = np.zeros((nC, cnp, cnp), dtype)
-    ga = np.zeros((nC, cnp), dtype)
-    np.add.at(U, rt.j, np.einsum("nri,nrk->nik", A, A))
-    np.add.at(ga, rt.j, np.einsum("nri,nr->ni", A, e))
-    V = np.zeros((nP, 3, 3), dtype)
-    gb = np.zeros((nP, 3), dtype)
-    np.add.at(V, rt.i, np.einsum("nri,nrk->nik", B, B))
-    np.add.at(gb, rt.i, np.einsum("nri,nr->ni", B, e))
-    W = np.einsum("nri,nrk->nik", A, B)
-    S = np.zeros((nA, nA), dtype)
-    for j in range(nC):
-        S[cnp * j:cnp * j + cnp, cnp * j:cnp * j + cnp] = U[j]
-    S[rt.held, rt.held] = dtype(coeff)
-    if camera:
-        S[np.arange(nA), np.arange(nA)] += mu * D[:nA]
-    ea = ga.reshape(-1).copy()
-    order = np.argsort(rt.i, kind="stable")
-    ptr = np.searchsorted(rt.i[order], np.arange(nP + 1))
-    for i in range(nP):
-        obs = order[ptr[i]:ptr[i + 1]]
-        if obs.size == 0 or rt.held_pts[i]:
-            continue
-        v = V[i] + np.diag(mu * D[nA + 3 * i:nA + 3 * i + 3])
-        l10, l20 = v[0, 1] / v[0, 0], v[0, 2] / v[0, 0]
-        d1 = v[1, 1] - l10 * v[0, 1]
-        l21 = (v[1, 2] - l20 * v[0, 1]) / d1
-        d2 = v[2, 2] - l20 * v[0, 2] - l21 * l21 * d1
-        Wi = W[obs].reshape(-1, 3)
-        z1 = Wi[:, 1] - l10 * Wi[:, 0]
-        z2 = Wi[:, 2] - l20 * Wi[:, 0] - l21 * z1
-        y2 = z2 / d2
-        y1 = z1 / d1 - l21 * y2
-        Yi = np.stack([Wi[:, 0] / v[0, 0] - l10 * y1 - l20 * y2, y1, y2], 1)
-        rows = (cnp * rt.j[obs][:, None] + np.arange(cnp)[None, :]).reshape(-1)
-        S[np.ix_(rows, rows)] -= Yi @ Wi.T
-        ea[rows] -= Yi @ gb[i]
-    return S, ea
+schur_blocks = fr.schur_blocks      # (it skips the route's held points)
 
 
 def schur_ref(rt, sm, mu, rule=fr.NO_RULE):
@@ -264,30 +222,22 @@ def reduced_scaled_S(rt, mu=0.0):
 # ---- a plain fp64 evaluation with the faults the judges must reject -----------------------------------------------------
 
 def plain_try(rt, mu, rule=fr.NO_RULE, fault=None):
-    """free_ref.plain_try / plain_try_damped restated for the held route: one damping try in plain fp64 (what the
-    kernels compute), with g and max_diag.  Faults: "pose-column" (a held pose column of A left non-zero),
-    "no-placeholder" (the held diagonals keep their zero sums), "point-g" (g_b of a held point from its unzeroed B),
-    "max-diag-all" (the maximum over every coordinate of the unheld diagonal)."""
+    """free_ref.plain_try for the held route, from free_ref's pieces: one damping try in plain fp64 (what the kernels
+    compute), with g and max_diag.  Faults: "pose-column" (a held pose column of A left non-zero), "no-placeholder"
+    (the held diagonals keep their zero sums), "point-g" (g_b of a held point from its unzeroed B), "max-diag-all" (the
+    maximum over every coordinate of the unheld diagonal).  A faulted try leaves the held entries of the step as
+    they come out."""
     e, A, B, _ = rt.blocks(fault)
-    nC, nP, cnp, nA = rt.nC, rt.nP, rt.cnp, rt.nA
-    U = np.zeros((nC, cnp, cnp))
-    np.add.at(U, rt.j, np.einsum("ari,ark->aik", A, A))
-    ga = np.zeros((nC, cnp))
-    np.add.at(ga, rt.j, np.einsum("ari,ar->ai", A, e))
-    V = np.zeros((nP, 3, 3))
-    np.add.at(V, rt.i, np.einsum("ari,ark->aik", B, B))
-    gb = np.zeros((nP, 3))
-    np.add.at(gb, rt.i, np.einsum("ari,ar->ai", B, e))
-    W = np.einsum("ark,arc->akc", A, B)
+    U, ga, V, gb, W = fr.plain_sums(rt, e, A, B)
     hq = np.flatnonzero(rt.held_pts)
     V[hq] = np.eye(3)
     gb[hq] = 0.0
     if fault == "point-g":
         _, _, B0, _ = rt.unheld_blocks()
-        g0 = np.zeros((nP, 3))
+        g0 = np.zeros((rt.nP, 3))
         np.add.at(g0, rt.i, np.einsum("ari,ar->ai", B0, e))
         gb[hq] = g0[hq]
-    k, k3 = np.arange(cnp), np.arange(3)
+    k, k3 = np.arange(rt.cnp), np.arange(3)
     dU = U[:, k, k].reshape(-1)
     dU[rt.held_mask] = 1.0
     if fault != "no-placeholder":
@@ -296,52 +246,23 @@ def plain_try(rt, mu, rule=fr.NO_RULE, fault=None):
     max_diag = float(diag[rt.free_all].max())
     if fault == "max-diag-all":
         _, A0, B0, _ = rt.unheld_blocks()
-        d0, _ = ar._segsum((A0 * A0).sum(axis=1), rt.j, nC)
+        d0, _ = ar._segsum((A0 * A0).sum(axis=1), rt.j, rt.nC)
         max_diag = float(max(d0.max(), diag.max()))
     D = rule.clamp(diag) if rule.marquardt else np.ones(rt.nT)
-    Vs = V.copy()
-    Vs[:, k3, k3] += mu * D[nA:].reshape(-1, 3)
-    Y = fr.ldl_solve(Vs[rt.i], W)
-    S = np.zeros((nA, nA))
-    for j in range(nC):
-        S[cnp * j:cnp * j + cnp, cnp * j:cnp * j + cnp] = U[j]
-    S[np.arange(nA), np.arange(nA)] = dU + mu * D[:nA]
-    ea = ga.reshape(-1).copy()
-    order = np.argsort(rt.i, kind="stable")
-    ptr = np.searchsorted(rt.i[order], np.arange(nP + 1))
-    for i in range(nP):
-        obs = order[ptr[i]:ptr[i + 1]]
-        if obs.size == 0:
-            continue
-        rows = (cnp * rt.j[obs][:, None] + np.arange(cnp)[None, :]).reshape(-1)
-        S[np.ix_(rows, rows)] -= Y[obs].reshape(-1, 3) @ W[obs].reshape(-1, 3).T
-        ea[rows] -= Y[obs].reshape(-1, 3) @ gb[i]
+    S, ea, Vs = fr.plain_scatter(rt, U, dU, ga, V, gb, W, mu, D)
     g = np.concatenate([ga.reshape(-1), gb.reshape(-1)])
-    with np.errstate(divide="ignore", invalid="ignore"):
-        d = 1.0 / np.sqrt(np.diag(S))
-        L = np.linalg.cholesky(d[:, None] * S * d[None, :])
-    dpa = d * np.linalg.solve(L.T, np.linalg.solve(L, d * ea))
+    dpa = fr.plain_solve(S, ea)
     if fault is None:
         dpa[rt.held] = 0.0
-    eb = gb.copy()
-    np.subtract.at(eb, rt.i, np.einsum("akc,ak->ac", W, dpa.reshape(-1, cnp)[rt.j]))
-    dpb = fr.ldl_solve(Vs, eb[:, None, :])[:, 0, :]
-    if fault is None:
-        dpb[hq] = 0.0
-    dp = np.concatenate([dpa, dpb.reshape(-1)])
-    cams = rt.twin.cams[:, np.arange(CNP) if cnp == 16 else fr.SEL11]
-    newcams, newpts = cams + dpa.reshape(-1, cnp), rt.twin.pts + dpb
-    e_new, _ = rt.residuals(newcams, newpts)
-    newp = flat(newcams, newpts)
-    sc = dict(dp_l2=float(dp @ dp), gain_den=float(dp @ ((mu * D) * dp + g)), newp_l2=float(newp @ newp),
-              new_cost=float((e_new * e_new).sum()))
-    return dict(S=S, ea=ea, g=g, dp=dp, cams=cams, newcams=newcams, newpts=newpts, sc=sc, D=D, max_diag=max_diag)
+    out = fr.plain_finish(rt, S, ea, dict(Vs=Vs, W=W, g=g), dpa, mu, D, hold_b=hq if fault is None else None)
+    return dict(out, g=g, cams=rt.current()[0], D=D, max_diag=max_diag)
 
 
 # ---- a dense LM with the holds: TwinKD.levmar with the held columns deleted ---------------------------------------------
 
 class HeldTwin(TwinKD):
-    """TwinKD whose levmar solves the reduced system: poses [nC], pts [nP] flags, non-zero = held"""
+    """TwinKD whose levmar (TwinKD's own loop and log rows) solves the reduced system, with the largest diagonal entry
+    taken over the columns that are left: poses [nC], pts [nP] flags, non-zero = held"""
 
     def __init__(self, prob, kc=None, free=None, poses=None, pts=None):
         super().__init__(prob, kc, free)
@@ -351,66 +272,18 @@ class HeldTwin(TwinKD):
         fa[hp, 10:] = False
         self.keep = np.r_[fa.reshape(-1), np.repeat(~hq, 3)]   # the columns that are left
 
-    def levmar(self, max_iter=20, init_mu=0.0, stop_small=True):
-        """TwinKD.levmar (psba_amd/csrc/lm_loop.cpp restated) on the columns `keep`: N and g restricted to them, the
-        largest diagonal entry over them, the step scattered back with zeros; the same log rows"""
-        STOP, EPS_SQ = 1e-12, 1e-24
-        tau = init_mu if init_mu != 0.0 else 1e-3
+    def start_mu(self, tau, N):
+        return tau * float(np.diag(N)[self.keep].max())
+
+    def solve_step(self, N, g, mu, D):
+        """TwinKD.solve_step on the columns `keep`: N, g and D restricted to them, the step scattered back with zeros"""
         f = self.keep
-        res, log = LmResult(), []
-        ex, N, g = self.normal()
-        res.init_err = ex
-        mu, nu, p_L2, first, flag, tries = 0.0, 2, 0.0, True, 0, 0
-        itno = 0
-        while itno < max_iter and flag == 0:
-            if not first:
-                _, N, g = self.normal()
-            else:
-                mu, p_L2, nu, first = tau * float(np.diag(N)[f].max()), 1e3, 2, False
-                res.mu0 = mu
-            Nf, gf = N[np.ix_(f, f)], g[f]
-            while True:
-                tries += 1
-                try:
-                    L = np.linalg.cholesky(Nf + mu * np.eye(gf.size))
-                    dp = np.zeros(self.nT)
-                    dp[f] = np.linalg.solve(L.T, np.linalg.solve(L, gf))
-                except np.linalg.LinAlgError:
-                    dp = None
-                if dp is not None:
-                    dp_L2 = float(dp @ dp)
-                    if dp_L2 < p_L2 * STOP * STOP:
-                        flag = 1
-                        break
-                    if dp_L2 >= (p_L2 + STOP) / EPS_SQ:
-                        flag = 2
-                        break
-                    newc = self.cams + dp[:self.nA].reshape(self.nC, CNP)
-                    newp = self.pts + dp[self.nA:].reshape(self.nP, 3)
-                    new_ex = self.cost(newc, newp)
-                    rho = (ex - new_ex) / float(dp @ (mu * dp + g))
-                    log.append([itno, new_ex, rho, mu, 1.0 if rho > 0 else 0.0])
-                    if rho > 0:
-                        tmp = 2 * rho - 1
-                        tmp = 1.0 - tmp * tmp * tmp
-                        mu *= tmp if tmp >= 1.0 / 3.0 else 1.0 / 3.0
-                        nu = 2
-                        self.cams, self.pts = newc, newp
-                        p_L2 = float((newc * newc).sum() + (newp * newp).sum())
-                        ex = new_ex
-                        break
-                else:
-                    log.append([itno, np.nan, np.nan, mu, -1.0])
-                mu *= nu
-                if 2.0 * nu > 1e9:
-                    flag = 2
-                    break
-                nu *= 2
-            if stop_small and ex <= STOP:
-                flag = 3
-            itno += 1
-        res.flag, res.iters, res.tries, res.final_err, res.mu_final = flag, itno, tries, ex, mu
-        return res, np.asarray(log).reshape(-1, 5)
+        x = cholesky_solve(N[np.ix_(f, f)] + mu * np.diag(D[f]), g[f])
+        if x is None:
+            return None
+        dp = np.zeros(self.nT)
+        dp[f] = x
+        return dp
 
 
 def held_ring(seed=7):

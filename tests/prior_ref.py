@@ -1,7 +1,7 @@
 """Host reference of Gaussian priors on cameras and points of the free-intrinsics routes (psba_set_priors, DESIGN 7j;
 no GPU): tests/test_prior_ref.py applies it to plain fp64 evaluations and injected faults, tests/test_gpu_priors.py to
-the kernels.  In the manner of held_ref.py on free_ref.py: nothing of either is edited, their constants are taken as
-they are, and no constant is fitted to a GPU result.
+the kernels.  In the manner of held_ref.py on free_ref.py: their judges and constants are taken as they are, and no
+constant is fitted to a GPU result.
 
 Model.  A camera j may carry a mean m_j [cnp] and an information matrix L_j [cnp, cnp], a point i n_i [3] and G_i
 [3, 3]; with d = m - p the cost is F = sum |e_a|^2 + sum d_j^T L_j d_j + sum d_i^T G_i d_i.  The priors are extra
@@ -14,10 +14,12 @@ fold sums the members' rows and columns.
 
 PriorRoute is held_ref.HeldRoute with a Priors; sums() is held_ref.sums with the prior terms added in extended
 precision to U's diagonal, V, g and the cost, so that every judge of free_ref.py (damp_ref, scale_diag, dpb_residual,
-scalars, solve_judge, check_exact_parts) and of held_ref.py applies unchanged.  schur_blocks restates
-held_ref.schur_blocks with L in U, G in V and L d, G d in g.  The envelopes grow by the prior's own roundings, counted
-from the order of the kernels' sums (kernels_free.hip: prior_row forms t_r = sum_c L_rc (m_c - p_c) from zero in
-ascending c, then s + t_r; an entry of U or V takes s + L_rc):
+scalars, solve_judge, check_exact_parts) and of held_ref.py applies unchanged.  schur_blocks IS
+free_ref.schur_blocks: the route's schur_start hands it L for U, G for V and (L d)_free, (G d)_free for g to start the
+sums from; plain_try is assembled from free_ref's plain_sums, plain_scatter, plain_solve and plain_finish around its own
+fault switches; PriorTwin overrides HeldTwin's cost and normal equations and nothing of the loop.
+The envelopes grow by the prior's own roundings, counted from the order of the kernels' sums (kernels_free.hip:
+prior_row forms t_r = sum_c L_rc (m_c - p_c) from zero in ascending c, then s + t_r; an entry of U or V takes s + L_rc):
   * u |d_c| for each subtraction m_c - p_c, through |L_rc|;
   * gamma(n + 2) sum_c |L_rc| |d_c| for the product row (n = cnp, 3 for a point: n products, n additions);
   * one more rounding, u |s + t|, for the add into s (U, V: u |s_rc + L_rc|).
@@ -59,14 +61,10 @@ class _Prior:
 
     def _prior(self, pri):
         self.pri = pri
-        self.sel = np.arange(CNP) if self.cnp == 16 else fr.SEL11
         hc = np.zeros(self.nA, dtype=bool)
         hc[self.held] = True
         self.free_c = ~hc.reshape(self.nC, self.cnp)          # (a folded-away coordinate counts as free here)
         self.free_p = ~self.held_pts
-
-    def current(self):
-        return self.twin.cams[:, self.sel].copy(), self.twin.pts.copy()
 
     def info_eff(self, fault=None):
         """(L with the held rows and columns dropped [nC, cnp, cnp], G with those of held points dropped).  Fault
@@ -76,6 +74,13 @@ class _Prior:
         L = self.pri.cam_info * rows[:, :, None] * f[:, None, :]
         G = self.pri.pt_info * self.free_p.astype(np.float64)[:, None, None]
         return L, G
+
+    def schur_start(self, dtype, fault=None):
+        """what free_ref.schur_blocks adds the observations' sums to: (L, (L d)_free, G, (G d)_free)"""
+        L, G = self.info_eff(fault)
+        _, LdC, _, GdP = deviations(self)
+        return (L.astype(dtype), np.where(self.free_c, LdC, LD(0)).astype(dtype),
+                G.astype(dtype), np.where(self.free_p[:, None], GdP, LD(0)).astype(dtype))
 
 
 class PriorRoute(_Prior, hr.HeldRoute):
@@ -156,53 +161,7 @@ def sums(rt, coeff=1.0, coeff_g=1.0):
     return sm
 
 
-def schur_blocks(rt, mu, D, camera=True, dtype=np.longdouble, coeff=1.0, fault=None):
-    """held_ref.schur_blocks with the prior rows appended: L in U, G in V, (L d)_free and (G d)_free in g.  Faults for
-    test_prior_ref.py are those of plain_try."""
-    e, A, B, _ = rt.blocks()
-    e, A, B = e.astype(dtype), A.astype(dtype), B.astype(dtype)
-    nC, nP, cnp, nA = rt.nC, rt.nP, rt.cnp, rt.nA
-    D = np.asarray(D, dtype=np.float64).astype(dtype)
-    mu = dtype(mu)
-    L, G = rt.info_eff()
-    dC, LdC, dP, GdP = deviations(rt)
-    U = L.astype(dtype)
-    ga = np.where(rt.free_c, LdC, LD(0)).astype(dtype)
-    np.add.at(U, rt.j, np.einsum("nri,nrk->nik", A, A))
-    np.add.at(ga, rt.j, np.einsum("nri,nr->ni", A, e))
-    V = G.astype(dtype)
-    gb = np.where(rt.free_p[:, None], GdP, LD(0)).astype(dtype)
-    np.add.at(V, rt.i, np.einsum("nri,nrk->nik", B, B))
-    np.add.at(gb, rt.i, np.einsum("nri,nr->ni", B, e))
-    W = np.einsum("nri,nrk->nik", A, B)
-    S = np.zeros((nA, nA), dtype)
-    for j in range(nC):
-        S[cnp * j:cnp * j + cnp, cnp * j:cnp * j + cnp] = U[j]
-    S[rt.held, rt.held] = dtype(coeff)
-    if camera:
-        S[np.arange(nA), np.arange(nA)] += mu * D[:nA]
-    ea = ga.reshape(-1).copy()
-    order = np.argsort(rt.i, kind="stable")
-    ptr = np.searchsorted(rt.i[order], np.arange(nP + 1))
-    for i in range(nP):
-        obs = order[ptr[i]:ptr[i + 1]]
-        if obs.size == 0 or rt.held_pts[i]:
-            continue
-        v = V[i] + np.diag(mu * D[nA + 3 * i:nA + 3 * i + 3])
-        l10, l20 = v[0, 1] / v[0, 0], v[0, 2] / v[0, 0]
-        d1 = v[1, 1] - l10 * v[0, 1]
-        l21 = (v[1, 2] - l20 * v[0, 1]) / d1
-        d2 = v[2, 2] - l20 * v[0, 2] - l21 * l21 * d1
-        Wi = W[obs].reshape(-1, 3)
-        z1 = Wi[:, 1] - l10 * Wi[:, 0]
-        z2 = Wi[:, 2] - l20 * Wi[:, 0] - l21 * z1
-        y2 = z2 / d2
-        y1 = z1 / d1 - l21 * y2
-        Yi = np.stack([Wi[:, 0] / v[0, 0] - l10 * y1 - l20 * y2, y1, y2], 1)
-        rows = (cnp * rt.j[obs][:, None] + np.arange(cnp)[None, :]).reshape(-1)
-        S[np.ix_(rows, rows)] -= Yi @ Wi.T
-        ea[rows] -= Yi @ gb[i]
-    return S, ea
+schur_blocks = fr.schur_blocks      # (the prior terms come in through the route's schur_start)
 
 
 def damp_ref(rt, sm, rule=fr.NO_RULE):
@@ -377,11 +336,11 @@ FAULTS = ("g-dropped", "sign", "held-row", "no-new-cost")
 
 
 def plain_try(rt, mu, rule=fr.NO_RULE, fault=None):
-    """held_ref.plain_try with the priors: one damping try in plain fp64 (what the kernels compute).  Faults:
-    "g-dropped" (the prior kept in U and V, dropped from g), "sign" (d = p - m), "held-row" (a held row of L left in
-    U), "no-new-cost" (the prior missing from the proposal's cost)."""
+    """held_ref.plain_try with the priors, from free_ref's pieces: one damping try in plain fp64 (what the kernels
+    compute).  Faults: "g-dropped" (the prior kept in U and V, dropped from g), "sign" (d = p - m), "held-row" (a held
+    row of L left in U), "no-new-cost" (the prior missing from the proposal's cost)."""
     e, A, B, _ = rt.blocks()
-    nC, nP, cnp, nA = rt.nC, rt.nP, rt.cnp, rt.nA
+    cnp, nA = rt.cnp, rt.nA
     cams, pts = rt.current()
     L, G = rt.info_eff(fault)
     sg = -1.0 if fault == "sign" else 1.0
@@ -390,19 +349,7 @@ def plain_try(rt, mu, rule=fr.NO_RULE, fault=None):
     GdP = np.where(rt.free_p[:, None], np.einsum("irc,ic->ir", rt.pri.pt_info, dP), 0.0)
     if fault == "g-dropped":
         LdC, GdP = 0.0 * LdC, 0.0 * GdP
-    U = np.zeros((nC, cnp, cnp))
-    np.add.at(U, rt.j, np.einsum("ari,ark->aik", A, A))
-    U += L
-    ga = np.zeros((nC, cnp))
-    np.add.at(ga, rt.j, np.einsum("ari,ar->ai", A, e))
-    ga += LdC
-    V = np.zeros((nP, 3, 3))
-    np.add.at(V, rt.i, np.einsum("ari,ark->aik", B, B))
-    V += G
-    gb = np.zeros((nP, 3))
-    np.add.at(gb, rt.i, np.einsum("ari,ar->ai", B, e))
-    gb += GdP
-    W = np.einsum("ark,arc->akc", A, B)
+    U, ga, V, gb, W = fr.plain_sums(rt, e, A, B, prior=(L, LdC, G, GdP))
     hq = np.flatnonzero(rt.held_pts)
     V[hq] = np.eye(3)
     gb[hq] = 0.0
@@ -412,55 +359,26 @@ def plain_try(rt, mu, rule=fr.NO_RULE, fault=None):
     diag = np.concatenate([dU, V[:, k3, k3].reshape(-1)])
     max_diag = float(diag[rt.free_all].max())
     D = rule.clamp(diag) if rule.marquardt else np.ones(rt.nT)
-    Vs = V.copy()
-    Vs[:, k3, k3] += mu * D[nA:].reshape(-1, 3)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        Y = fr.ldl_solve(Vs[rt.i], W)
-    S = np.zeros((nA, nA))
-    for j in range(nC):
-        S[cnp * j:cnp * j + cnp, cnp * j:cnp * j + cnp] = U[j]
-    if fault != "held-row":
-        S[rt.held, :] = 0.0
-        S[:, rt.held] = 0.0
-    S[np.arange(nA), np.arange(nA)] = dU + mu * D[:nA]
-    ea = ga.reshape(-1).copy()
-    order = np.argsort(rt.i, kind="stable")
-    ptr = np.searchsorted(rt.i[order], np.arange(nP + 1))
-    for i in range(nP):
-        obs = order[ptr[i]:ptr[i + 1]]
-        if obs.size == 0:
-            continue
-        rows = (cnp * rt.j[obs][:, None] + np.arange(cnp)[None, :]).reshape(-1)
-        S[np.ix_(rows, rows)] -= Y[obs].reshape(-1, 3) @ W[obs].reshape(-1, 3).T
-        ea[rows] -= Y[obs].reshape(-1, 3) @ gb[i]
+    if fault != "held-row":                                  # the held rows and columns of U's blocks are clear
+        hj, hk = rt.held // cnp, rt.held % cnp
+        U[hj, hk, :] = 0.0
+        U[hj, :, hk] = 0.0
+    S, ea, Vs = fr.plain_scatter(rt, U, dU, ga, V, gb, W, mu, D)
     g = np.concatenate([ga.reshape(-1), gb.reshape(-1)])
     blk = np.arange(nA) // cnp
     upper = blk[:, None] < blk[None, :]
     S[upper] = S.T[upper]                                    # (the mirror of k_free_finalize)
-    d = 1.0 / np.sqrt(np.diag(S))
-    try:
-        Lc = np.linalg.cholesky(d[:, None] * S * d[None, :])
-        dpa = d * np.linalg.solve(Lc.T, np.linalg.solve(Lc, d * ea))
-    except np.linalg.LinAlgError:                            # (a faulted system need not be positive definite)
-        dpa = np.linalg.solve(S, ea)
+    dpa = fr.plain_solve(S, ea, fallback=True)               # (a faulted system need not be positive definite)
     dpa[rt.held] = 0.0
-    eb = gb.copy()
-    np.subtract.at(eb, rt.i, np.einsum("akc,ak->ac", W, dpa.reshape(-1, cnp)[rt.j]))
-    dpb = fr.ldl_solve(Vs, eb[:, None, :])[:, 0, :]
-    dpb[hq] = 0.0
-    dp = np.concatenate([dpa, dpb.reshape(-1)])
-    newcams, newpts = cams + dpa.reshape(-1, cnp), pts + dpb
-    e_new, _ = rt.residuals(newcams, newpts)
-    newp = hr.flat(newcams, newpts)
+    out = fr.plain_finish(rt, S, ea, dict(Vs=Vs, W=W, g=g), dpa, mu, D, hold_b=hq)
 
     def quad(c, p):
         a, b = rt.pri.cam_mean - c, rt.pri.pt_mean - p
         return (float(np.einsum("jr,jrc,jc->", a, rt.pri.cam_info, a)), float(np.einsum("ir,irc,ic->", b, rt.pri.pt_info, b)))
-    prior_cur, prior_new = quad(cams, pts), quad(newcams, newpts)
-    new_cost = float((e_new * e_new).sum()) + (0.0 if fault == "no-new-cost" else sum(prior_new))
-    sc = dict(dp_l2=float(dp @ dp), gain_den=float(dp @ ((mu * D) * dp + g)), newp_l2=float(newp @ newp), new_cost=new_cost)
-    return dict(S=S, ea=ea, g=g, dp=dp, cams=cams, pts=pts, newcams=newcams, newpts=newpts, sc=sc, D=D, max_diag=max_diag,
-                cost=float((e * e).sum()) + sum(prior_cur), prior_cur=prior_cur, prior_new=prior_new)
+    prior_cur, prior_new = quad(cams, pts), quad(out["newcams"], out["newpts"])
+    out["sc"]["new_cost"] += 0.0 if fault == "no-new-cost" else sum(prior_new)
+    return dict(out, g=g, cams=cams, pts=pts, D=D, max_diag=max_diag, cost=float((e * e).sum()) + sum(prior_cur),
+                prior_cur=prior_cur, prior_new=prior_new)
 
 
 def plain_shared_system(rt, mu, fault=None):
@@ -493,8 +411,7 @@ def draw_priors(rt0, seed=3, n_pts=3):
     sm = hr.sums(rt0)
     nC, nP, cnp = rt0.nC, rt0.nP, rt0.cnp
     pri = Priors(nC, cnp, nP)
-    cams = rt0.twin.cams[:, np.arange(CNP) if cnp == 16 else fr.SEL11]
-    pts = rt0.twin.pts
+    cams, pts = rt0.current()
     dU, dV = sm["diagU"].reshape(nC, cnp), sm["diagV"].reshape(nP, 3)
     seen = np.bincount(rt0.j, minlength=nC) > 0
 

@@ -12,7 +12,8 @@ after the solve (a member's entry is a copy of its representative's).
 
 The reference is TwinKD with the members' K and kc set to their representative's (share_problem):
   * SharedTwin.jacobian_shared builds J P in the REDUCED numbering (folded-away columns removed), and
-    SharedTwin.levmar_shared is lm_loop.cpp restated on it -- formulated differently from the kernels on purpose;
+    SharedTwin.levmar_shared is TwinKD.levmar (lm_loop.cpp restated) on it, through the methods that loop asks for --
+    formulated differently from the kernels on purpose;
   * fold(S, ea, ...) folds TwinKD.schur_blocks(mu) (80-bit) in 80-bit, embedded;
   * reduce_sums reduces free_ref.sums (g and its envelope folded; dp and the proposal with the folded-away entries
     dropped), so that assembly_ref.try_scalars, free_ref.dpb_residual (with the expanded dp_a) and free_ref.solve_judge
@@ -38,7 +39,7 @@ import numpy as np
 
 import assembly_ref as ar
 import free_ref as fr
-from freekd_twin import CNP, LmResult, TwinKD, start_kc
+from freekd_twin import CNP, TwinKD, cholesky_solve, start_kc
 
 LD = ar.LD
 EPS = np.finfo(np.float64).eps
@@ -277,7 +278,7 @@ def schur_ref(rt, sm, mu, rule):
 def plain_try_damped(rt, mu, rule, fault=None):
     """plain_try under Marquardt's rule.  fault "rep-own-diag": D of a representative from its own U_kk instead of
     the members' sum"""
-    S1, ea1, pc = fr.plain_schur_damped(rt, mu, rule, camera=False)
+    S1, ea1, pc = fr.plain_schur(rt, mu, rule=rule, camera=False)
     S, ea = plain_fold(S1, ea1, rt.rep, rt.free, 0.0)
     nA = rt.nA
     dU = pc["dU"].copy()
@@ -290,23 +291,7 @@ def plain_try_damped(rt, mu, rule, fault=None):
     f[fixed] = 1.0
     D = np.concatenate([rule.clamp(f), pc["D"][nA:]])
     S[np.arange(nA), np.arange(nA)] += mu * D[:nA]
-    d = 1.0 / np.sqrt(np.diag(S))
-    Lc = np.linalg.cholesky(d[:, None] * S * d[None, :])
-    dpe = d * np.linalg.solve(Lc.T, np.linalg.solve(Lc, d * ea))
-    dpe[rt.held] = 0.0
-    dpe[rt.away] = 0.0
-    dpa = rt.expand(dpe)
-    eb = pc["g"][nA:].reshape(-1, 3).copy()
-    np.subtract.at(eb, rt.i, np.einsum("akc,ak->ac", pc["W"], dpa.reshape(-1, CNP)[rt.j]))
-    dpb = fr.ldl_solve(pc["Vs"], eb[:, None, :])[:, 0, :]
-    dp = np.concatenate([dpa, dpb.reshape(-1)])
-    newcams, newpts = rt.twin.cams + dpa.reshape(-1, CNP), rt.twin.pts + dpb
-    e_new, _ = rt.residuals(newcams, newpts)
-    newp = np.concatenate([newcams.reshape(-1), newpts.reshape(-1)])
-    dr_, nr_ = dp[rt.keep], newp[rt.keep]
-    sc = dict(dp_l2=float(dr_ @ dr_), gain_den=float(dp @ pc["g"] + dr_ @ ((mu * D[rt.keep]) * dr_)),
-              newp_l2=float(nr_ @ nr_), new_cost=float((e_new * e_new).sum()))
-    return dict(S=S, ea=ea, dp=dp, dp_embedded=dpe, newcams=newcams, newpts=newpts, sc=sc, D=D)
+    return dict(_finish(rt, S, ea, pc, mu, D, lambda dp, dr_: dp @ pc["g"] + dr_ @ ((mu * D[rt.keep]) * dr_)), D=D)
 
 
 # ---- a plain fp64 evaluation (what the kernels compute, in numpy) ----------------------------------------------------
@@ -344,27 +329,21 @@ def plain_fold(S, ea, rep, free, mu, coeff=1.0, mu_per_member=False, skip=None, 
     return out, e
 
 
+def _finish(rt, S, ea, pc, mu, D, gain_den):
+    """free_ref's solve and finish on the folded system: the embedded step cleared at held and folded-away
+    coordinates and expanded, the sums over the distinct parameters"""
+    dpe = fr.plain_solve(S, ea)
+    dpe[rt.held] = 0.0
+    dpe[rt.away] = 0.0
+    out = fr.plain_finish(rt, S, ea, pc, rt.expand(dpe), mu, D, keep=rt.keep, gain_den=gain_den)
+    return dict(out, dp_embedded=dpe)
+
+
 def plain_try(rt, mu):
     """free_ref.plain_try with the fold: dp [nT] expanded, the proposal, the four sums over the distinct parameters"""
     S1, ea1, pc = fr.plain_schur(rt, mu)
     S, ea = plain_fold(S1, ea1, rt.rep, rt.free, mu)
-    d = 1.0 / np.sqrt(np.diag(S))
-    Lc = np.linalg.cholesky(d[:, None] * S * d[None, :])
-    dpe = d * np.linalg.solve(Lc.T, np.linalg.solve(Lc, d * ea))
-    dpe[rt.held] = 0.0
-    dpe[rt.away] = 0.0
-    dpa = rt.expand(dpe)
-    eb = pc["g"][rt.nA:].reshape(-1, 3).copy()
-    np.subtract.at(eb, rt.i, np.einsum("akc,ak->ac", pc["W"], dpa.reshape(-1, CNP)[rt.j]))
-    dpb = fr.ldl_solve(pc["Vs"], eb[:, None, :])[:, 0, :]
-    dp = np.concatenate([dpa, dpb.reshape(-1)])
-    newcams, newpts = rt.twin.cams + dpa.reshape(-1, CNP), rt.twin.pts + dpb
-    e_new, _ = rt.residuals(newcams, newpts)
-    newp = np.concatenate([newcams.reshape(-1), newpts.reshape(-1)])
-    dr_, nr_ = dp[rt.keep], newp[rt.keep]
-    sc = dict(dp_l2=float(dr_ @ dr_), gain_den=float(dp @ pc["g"] + mu * (dr_ @ dr_)), newp_l2=float(nr_ @ nr_),
-              new_cost=float((e_new * e_new).sum()))
-    return dict(S=S, ea=ea, dp=dp, dp_embedded=dpe, newcams=newcams, newpts=newpts, sc=sc)
+    return _finish(rt, S, ea, pc, mu, pc["D"], lambda dp, dr_: dp @ pc["g"] + mu * (dr_ @ dr_))
 
 
 # ---- the dense twin in the reduced numbering ------------------------------------------------------------------------
@@ -420,66 +399,30 @@ class SharedTwin(TwinKD):
         full = np.asarray(dp_r)[self.col[src]]
         return full[:self.nA].reshape(self.nC, CNP), full[self.nA:].reshape(self.nP, 3)
 
+    # TwinKD.levmar in the reduced numbering: N, g, D and dp have one entry per distinct parameter
+    system = normal_shared
+
+    def start_mu(self, tau, N):
+        return tau * self.max_diag_shared(N)
+
+    def solve_step(self, N, g, mu, D):
+        dp = cholesky_solve(N + mu * np.diag(D), g)
+        if dp is not None:
+            dp[~self.free_r] = 0.0
+        return dp
+
+    def proposal(self, dp):
+        dc, dq = self.expand(dp)
+        return self.cams + dc, self.pts + dq
+
+    def norm2(self, cams, pts):
+        pr = np.r_[cams.reshape(-1), pts.reshape(-1)][self.keep]
+        return float(pr @ pr)
+
     def levmar_shared(self, max_iter=20, init_mu=0.0, stop_small=True):
         """TwinKD.levmar (lm_loop.cpp restated) on the reduced system: dp_l2, the gain denominator and newp_l2 count
         every distinct parameter once"""
-        STOP, EPS_SQ = 1e-12, 1e-24
-        tau = init_mu if init_mu != 0.0 else 1e-3
-        res, log = LmResult(), []
-        ex, N, g = self.normal_shared()
-        res.init_err = ex
-        nR = N.shape[0]
-        mu, nu, p_L2, first, flag, tries = 0.0, 2, 0.0, True, 0, 0
-        itno = 0
-        while itno < max_iter and flag == 0:
-            if not first:
-                _, N, g = self.normal_shared()
-            else:
-                mu, p_L2, nu, first = tau * self.max_diag_shared(N), 1e3, 2, False
-                res.mu0 = mu
-            while True:
-                tries += 1
-                try:
-                    L = np.linalg.cholesky(N + mu * np.eye(nR))
-                    dp = np.linalg.solve(L.T, np.linalg.solve(L, g))
-                except np.linalg.LinAlgError:
-                    dp = None
-                if dp is not None:
-                    dp[~self.free_r] = 0.0
-                    dp_L2 = float(dp @ dp)
-                    if dp_L2 < p_L2 * STOP * STOP:
-                        flag = 1
-                        break
-                    if dp_L2 >= (p_L2 + STOP) / EPS_SQ:
-                        flag = 2
-                        break
-                    dc, dq = self.expand(dp)
-                    newc, newp = self.cams + dc, self.pts + dq
-                    new_ex = self.cost(newc, newp)
-                    rho = (ex - new_ex) / float(dp @ (mu * dp + g))
-                    log.append([itno, new_ex, rho, mu, 1.0 if rho > 0 else 0.0])
-                    if rho > 0:
-                        tmp = 2 * rho - 1
-                        tmp = 1.0 - tmp * tmp * tmp
-                        mu *= tmp if tmp >= 1.0 / 3.0 else 1.0 / 3.0
-                        nu = 2
-                        self.cams, self.pts = newc, newp
-                        pr = np.r_[newc.reshape(-1), newp.reshape(-1)][self.keep]
-                        p_L2 = float(pr @ pr)
-                        ex = new_ex
-                        break
-                else:
-                    log.append([itno, np.nan, np.nan, mu, -1.0])
-                mu *= nu
-                if 2.0 * nu > 1e9:
-                    flag = 2
-                    break
-                nu *= 2
-            if stop_small and ex <= STOP:
-                flag = 3
-            itno += 1
-        res.flag, res.iters, res.tries, res.final_err, res.mu_final = flag, itno, tries, ex, mu
-        return res, np.asarray(log).reshape(-1, 5)
+        return self.levmar(max_iter, init_mu, stop_small)
 
 
 def shared_ring(labels, seed=7):

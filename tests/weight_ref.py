@@ -1,7 +1,9 @@
 """Host reference of the observation weighting on the free-intrinsics routes (psba_set_obs_weighting; no
 GPU): tests/test_weight_ref.py applies it to plain fp64 evaluations and injected faults, tests/test_gpu_weighting.py to
-the kernels.  In the manner of prior_ref.py on held_ref.py on free_ref.py: nothing of the three is edited, their
-constants, scaled_tol and ETA_MAX are taken as they are, and no constant is fitted to a GPU result.
+the kernels.  In the manner of prior_ref.py on held_ref.py on free_ref.py: their judges, constants, scaled_tol and
+ETA_MAX are taken as they are, and no constant is fitted to a GPU result.  Nothing of their arithmetic is repeated here:
+the Schur restatement is free_ref.schur_blocks and the plain try prior_ref.plain_try, both on the weighted blocks, and
+WeightTwin overrides HeldTwin's cost and Jacobian and nothing of TwinKD's LM loop.
 
 Model.  Observation a may carry a standard deviation sigma_a > 0 (none: 1) and a loss (kind, c) may be set, the kinds
 and formulas of camera_model.h's robust_eval (assembly_ref.rho_ext).  With e_a the route's residual,
