@@ -480,6 +480,16 @@ PSBA_HD void fix_mask(int fx, double *A, double *B) {
   }
 }
 
+// an entry of W_ij = coeff A^T B under the mask: +0.0 when either block is fixed.  The product of the zeroed block is a
+// zero already, but 0 * x keeps x's sign, and the stored W of a fixed block is +0.0 like g and dp (a select)
+template <int LM>
+PSBA_HD double fix_w(int fx, double w) {
+  if constexpr ((LM & LENS_FIXED) != 0)
+    return fx ? 0.0 : w;
+  else
+    return w;
+}
+
 // loads of camera j's kc and observation a's whitening factors (nothing under a model without them)
 template <int LM>
 PSBA_HD void lens_load_kc(const double *src, size_t j, double *kc) {

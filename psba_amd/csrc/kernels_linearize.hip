@@ -94,7 +94,8 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p, RobustLoss rl
       lens_load_w<LM>(p.wl, a, wl);
       const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
       lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
-      fix_mask<LM>(fix_load<LM>(fm, i, j), A, B);
+      const int fx = fix_load<LM>(fm, i, j);
+      fix_mask<LM>(fx, A, B);
       if (DUMP) {
         p.dbg_ex[2 * a] = e[0];
         p.dbg_ex[2 * a + 1] = e[1];
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p, RobustLoss rl
 #pragma unroll
       for (int r = 0; r < 6; r++)
 #pragma unroll
-        for (int c = 0; c < 3; c++) Wv[3 * r + c] = p.coeff * (A[r] * B[c] + A[6 + r] * B[3 + c]);
+        for (int c = 0; c < 3; c++) Wv[3 * r + c] = fix_w<LM>(fx, p.coeff * (A[r] * B[c] + A[6 + r] * B[3 + c]));
       if (tid < TILE_OBS / 2) {
         double *w = sW + 19 * tid;
 #pragma unroll
@@ -273,7 +274,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss r
 #pragma unroll
       for (int r = 0; r < 6; r++)
 #pragma unroll
-        for (int c = 0; c < 3; c++) w[3 * r + c] = p.coeff * (A[r] * B[c] + A[6 + r] * B[3 + c]);
+        for (int c = 0; c < 3; c++) w[3 * r + c] = fix_w<LM>(fx, p.coeff * (A[r] * B[c] + A[6 + r] * B[3 + c]));
       // this observation's terms of V_i (upper triangle) and g_b,i
       int q = 0;
 #pragma unroll
@@ -391,7 +392,8 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const in
     lens_load_w<LM>(p.wl, a, wl);
     const double2 m = reinterpret_cast<const double2 *>(p.impts)[a];
     lens_linearize<LM>(cc, cam, M, kc, wl, rl, m.x, m.y, e, A, B);
-    fix_mask<LM>(fix_load<LM>(fm, i, j), A, B);
+    const int fx = fix_load<LM>(fm, i, j);
+    fix_mask<LM>(fx, A, B);
     if (DUMP) {
       p.dbg_ex[2 * (size_t)a] = e[0];
       p.dbg_ex[2 * (size_t)a + 1] = e[1];
@@ -404,7 +406,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize_long(LinArgs p, const in
 #pragma unroll
     for (int r = 0; r < 6; r++)
 #pragma unroll
-      for (int c = 0; c < 3; c++) w[3 * r + c] = p.coeff * (A[r] * B[c] + A[6 + r] * B[3 + c]);
+      for (int c = 0; c < 3; c++) w[3 * r + c] = fix_w<LM>(fx, p.coeff * (A[r] * B[c] + A[6 + r] * B[3 + c]));
     int k = 0;
 #pragma unroll
     for (int r = 0; r < 3; r++)

@@ -13,11 +13,20 @@ Each case uploads one problem to one handle (two for `ranks`) and runs two layer
     with the K1 accumulation envelope and JACOBIAN_SLACK carried through (the fused instantiations' U, V, W, g are
     not readable).  `ranks`: two point shards with a rank layout and the packed route, their packed sums added on
     the host (r = 2).
-Every entry must satisfy |got - exact| <= its own bound; the module prints the worst bound ratio per route and quantity."""
+Every entry must satisfy |got - exact| <= its own bound; the module prints the worst bound ratio per route and quantity.
+
+Cases with a `fixed=` option run the same two layers under psba_set_fixed (the LENS_FIXED instantiations, k_fixed_diag,
+k_max_diag_fixed): the mask is computed from the problem (tests/fixed_ref.py: mixed, island, long) and printed, the
+reference has the placeholder rule installed (exact values, zero envelopes), and the exact parts -- zeros, placeholders,
+the rows and columns of fixed cameras in S, the bits of fixed blocks in the proposal, camera 0's zero rotation
+coordinates set to -0.0 first -- are compared with no tolerance, on bit patterns where a sign could hide."""
+import contextlib
+
 import numpy as np
 import pytest
 
 import assembly_ref as ar
+import fixed_ref as fr
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not ar.LD_OK, reason="needs an 80-bit long double")]
 
@@ -48,9 +57,52 @@ CASES = {
     "lens-robust-owner": ("lens54", {"PSBA_SCHUR_OWNER": "1"},
                           dict(path=1, lens=True, mirror_label="lens-robust-owner (mirror: atomic)")),
     "tr-coeff": ("7cams", {}, dict(path=0, coeff=(2.0, -2.0))),
+    # ---- fixed blocks (psba_set_fixed): the module's small shapes under the masks of tests/fixed_ref.py ----
+    "fixed-rows-mixed": ("54cams", {}, dict(path=0, fixed="mixed")),
+    "fixed-rows-island": ("54cams", {}, dict(path=0, fixed="island")),
+    "fixed-owner-mixed": ("54cams", {"PSBA_SCHUR_OWNER": "1"},
+                          dict(path=1, fixed="mixed", mirror_label="fixed-owner-mixed (mirror: atomic)")),
+    "fixed-owner-island": ("54cams", {"PSBA_SCHUR_OWNER": "1"},
+                           dict(path=1, fixed="island", mirror_label="fixed-owner-island (mirror: atomic)")),
+    "fixed-atomic-mixed": ("54cams", {"PSBA_SCHUR_ATOMIC": "1"}, dict(path=2, fixed="mixed")),
+    "fixed-atomic-island": ("54cams", {"PSBA_SCHUR_ATOMIC": "1"}, dict(path=2, fixed="island")),
+    "fixed-read-w-mixed": ("54cams", {"PSBA_BACK_READ_W": "1"}, dict(path=0, read_w=True, fixed="mixed")),
+    "fixed-read-w-island": ("54cams", {"PSBA_BACK_READ_W": "1"}, dict(path=0, read_w=True, fixed="island")),
+    "fixed-sparse-mixed": ("sparse60", {}, dict(path=4, solver=1, fixed="mixed")),
+    "fixed-sparse-island": ("sparse60", {}, dict(path=4, solver=1, fixed="island")),
+    "fixed-runs-forced-mixed": ("venice1", {"PSBA_SCHUR_RUNS": "1"}, dict(path=0, plan="runs", fixed="mixed")),
+    "fixed-cam-major-mixed": ("54cams", {"PSBA_LIN_GLOBAL_ACC": "1"}, dict(path=0, fixed="mixed")),
+    "fixed-v1-mixed": ("54cams", {"PSBA_LIN_V1": "1"}, dict(path=0, fixed="mixed")),
+    "fixed-block-ranges-mixed": ("54cams", {"PSBA_SCHUR_BLOCK_GROUPS": "1", "PSBA_SCHUR_SPLIT": "3"},
+                                 dict(path=0, plan="split3", fixed="mixed")),
+    "fixed-tr-coeff-mixed": ("7cams", {}, dict(path=0, coeff=(2.0, -2.0), fixed="mixed")),  # the placeholder is 2
+    "fixed-lens-robust-mixed": ("lens54", {}, dict(path=0, lens=True, fixed="mixed")),
+    "fixed-ranks-mixed": ("54cams", {"PSBA_SCHUR_PACKED": "1"}, dict(path=0, ranks=2, fixed="mixed")),
+    "fixed-long": ("long", {}, dict(path=1, fixed="long", mirror_label="fixed-long (mirror: atomic)")),
+    # 54cams scaled by 2^-22: the largest free diagonal entry lies below the placeholder (test_gpu_fixed_entrywise.py)
+    "fixed-rows-scaled-mixed": ("54cams-scaled", {}, dict(path=0, fixed="mixed")),
 }
 
 WORST = {}  # (route, quantity) -> worst bound ratio
+FINDINGS = []  # the exact parts that did not hold inside the running exact_parts(): all of them, not only the first
+
+
+def exact(cond, msg):
+    if not cond:
+        FINDINGS.append(msg)
+
+
+@contextlib.contextmanager
+def exact_parts():
+    """Collects what exact() finds in its body and reports all of it at the end, also when the body raised."""
+    del FINDINGS[:]
+    try:
+        yield
+    except Exception as err:
+        if FINDINGS:
+            raise AssertionError("\n".join(FINDINGS) + f"\n(and then: {err!r})") from err
+        raise
+    assert not FINDINGS, "\n".join(FINDINGS)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -113,10 +165,46 @@ def problem(name, problems):
     if name == "lens54":  # distortion, covariances and 5 % outliers of the robust tests' default one-try case
         from test_gpu_robust import _one_try_case
         return _one_try_case("default")
+    if name == "54cams-scaled":
+        return fr.scaled_problem(problems["54cams"])
     return problems[name]
 
 
-def _handle(prob, lens, solver=0, rank=None):
+_MASKS = {}  # (problem name, mask name) -> (fc, fp, info)
+
+
+def mask_of(name, kind, prob, lens=None):
+    """The mask `kind` of tests/fixed_ref.py for the problem, computed once on the host and printed.  mixed: the camera
+    with the largest diagonal entry of U = sum A^T A is taken from the numpy twin's Jacobian blocks (with the
+    distortion of a lens case), not from the code under test."""
+    if (name, kind) not in _MASKS:
+        if kind == "mixed":
+            from lens_twin import Twin
+            A = (Twin(prob) if lens is None else Twin(prob, lens[0])).linearize()[1]
+            d = np.zeros((int(prob["nC"]), 6))
+            np.add.at(d, np.asarray(prob["jidx"]), (A * A).sum(axis=1))
+            m = fr.mixed_mask(prob, int(np.argmax(d.max(axis=1))))
+        else:
+            m = {"island": fr.island_mask, "long": fr.long_mask}[kind](prob)
+        assert 0 < int(m[0].sum()) < int(prob["nC"]) and 0 < int(m[1].sum()) < int(prob["nP"])
+        print(f"\n{name} {kind} mask: {m[2]}")
+        _MASKS[(name, kind)] = m
+    return _MASKS[(name, kind)]
+
+
+def minus_zero_rotation(h):
+    """Camera 0 (fixed under every mask): its zero rotation coordinates become -0.0 through psba_set_params, so a
+    proposal formed as cams + 0.0 instead of a select shows as +0.0.  Returns how many were set."""
+    cams, pts = h.get_params()
+    z = cams[0, :3] == 0.0
+    cams[0, :3] = np.where(z, -0.0, cams[0, :3])
+    h.set_params(cams, pts)
+    back = h.get_params()[0]
+    assert fr.same_bits(back, cams)
+    return int(z.sum())
+
+
+def _handle(prob, lens, solver=0, rank=None, fixed=None):
     import psba_amd
     h = psba_amd.Psba(0)
     if solver:
@@ -129,6 +217,9 @@ def _handle(prob, lens, solver=0, rank=None):
         h.set_distortion(kc)
         h.set_obs_covariance(cov)
         h.set_robust_loss(LOSS_HUBER, c)
+    if fixed is not None:
+        h.set_fixed(fixed[0], fixed[1])
+        assert h.fixed_counts() == (int(np.count_nonzero(fixed[0])), int(np.count_nonzero(fixed[1])))
     return h
 
 
@@ -146,8 +237,10 @@ def _jac_slack(es, lens):
     return None if lens is None else ar.robust_jac_slack(es, lens[2])
 
 
-def _mirror_k1(route, h, prob, coeff, coeff_g, lens, cam_major):
-    """K1 through the mirror verbs, judged from the dumped blocks; returns (JA, JB, e, W, g) of the last linearization."""
+def _mirror_k1(route, h, prob, coeff, coeff_g, lens, cam_major, fixed=None, owner=True):
+    """K1 through the mirror verbs, judged from the dumped blocks; returns (JA, JB, e, W, g) of the last linearization.
+    fixed = (fc, fp): the placeholder rule on the reference and the exact parts; owner: this rank owns the camera
+    terms (the placeholder of a fixed camera is written there only)."""
     from psba_amd import capi
     nC, nP = int(prob["nC"]), int(prob["nP"])
     JA, JB = h.compute_jacobiQT()
@@ -155,24 +248,86 @@ def _mirror_k1(route, h, prob, coeff, coeff_g, lens, cam_major):
     es = _slack(prob, ex, lens)
     k1 = ar.k1_sums(JA, JB, ex, prob["iidx"], prob["jidx"], nC, nP, coeff, coeff_g, e_slack=es,
                     recomputed=("U", "ga") if cam_major else (), jac_slack=_jac_slack(es, lens))
-    judge(route, "U", h.compute_U(coeff), *k1["U"])
-    judge(route, "V", h.compute_V(coeff), *k1["V"])
+    if fixed is not None:
+        k1 = fr.install(k1, fixed[0], fixed[1], coeff, owner)
+    U, V = h.compute_U(coeff), h.compute_V(coeff)
+    judge(route, "U", U, *k1["U"])
+    judge(route, "V", V, *k1["V"])
     W = h.compute_Wblks(coeff)
     judge(route, "W", W, *k1["W"])
     g = h.compute_g(coeff_g)  # the last relinearization: K2 and K3 read its U, V, g
     judge(route, "g", g, *k1["g"])
+    if fixed is not None:
+        fc, fp = fr.flags(*fixed)
+        oc, op = fc[np.asarray(prob["jidx"])], fp[np.asarray(prob["iidx"])]
+        exact(fr.plus_zero(JA.reshape(-1, 12)[oc]) and fr.plus_zero(JB.reshape(-1, 6)[op]), f"{route}: masked A, B")
+        assert np.all(np.any(JA.reshape(-1, 12)[~oc] != 0, axis=1)) and np.all(np.any(JB.reshape(-1, 6)[~op] != 0, axis=1))
+        place = coeff if owner else 0.0
+        exact(fr.same_bits(U.reshape(-1, 6, 6)[fc], np.broadcast_to(place * np.eye(6), (int(fc.sum()), 6, 6))),
+              f"{route}: U of a fixed camera is not {place} I")
+        exact(fr.same_bits(V.reshape(-1, 3, 3)[fp], np.broadcast_to(coeff * np.eye(3), (int(fp.sum()), 3, 3))),
+              f"{route}: V of a fixed point is not {coeff} I")
+        exact(fr.plus_zero(W.reshape(-1, 18)[oc | op]), f"{route}: a masked row of W is not +0.0")
+        exact(fr.plus_zero(g[fr.fixed_entries(fc, fp)]), f"{route}: g of a fixed block is not +0.0")
+        # the maximum against the one over the free blocks of these very U, V (the GPU's own; their sums are redone by
+        # compute_g's relinearization in another order of the adds: the relative 1e-12 of tests/test_gpu_fixed.py).
+        # This holds the verb to the blocks it reads; it sees a forgotten mask only where the free entries lie below
+        # the placeholder, i.e. on fixed-rows-scaled-mixed (and in test_gpu_fixed_entrywise.py), not on the others
+        want = fr.free_max(U, V, fc, fp)
+        for what, got in (("psba_max_diag", h.max_diag()), ("psba_maxElmOfUV", h.maxElmOfUV())):
+            assert abs(got - want) <= 1e-12 * want, f"{route}: {what} {got!r}, over the free blocks {want!r}"
     return JA, JB, ex, W, g
 
 
-def _fused_reference(JA, JB, ex, prob, coeff, coeff_g, lens, mu, r=1):
-    """The reference of the fused chain from the dumped blocks, the K1 envelope and JACOBIAN_SLACK carried through."""
+def _exact_dense_S(what, S, fc, d, lower):
+    """Rows and columns of fixed cameras in a dense S: exactly zero off the diagonal block, the block d I on its bit
+    patterns.  lower: only the lower triangle is written (the fused routes)."""
+    S = np.asarray(S)
+    nA = S.shape[0]
+    tri = np.tril(np.ones((6, 6), dtype=bool)) if lower else np.ones((6, 6), dtype=bool)
+    for j in np.flatnonzero(fc):
+        j0 = 6 * j
+        blk = S[j0:j0 + 6, j0:j0 + 6]
+        exact(fr.same_bits(blk[tri], (d * np.eye(6))[tri]),
+              f"{what}: diagonal block of fixed camera {j} is not {d!r} I")
+        exact(fr.plus_zero(S[j0:j0 + 6, :j0]) and fr.plus_zero(S[j0 + 6:, j0:j0 + 6]),
+              f"{what}: row / column of fixed camera {j} is not +0.0 off the diagonal block")
+        if not lower:
+            exact(fr.plus_zero(S[j0:j0 + 6, j0 + 6:]) and fr.plus_zero(S[:j0, j0:j0 + 6]),
+                  f"{what}: row / column of fixed camera {j} is not +0.0 off the diagonal block (upper triangle)")
+    return nA
+
+
+def _exact_block_S(what, jk, blocks, fc, d):
+    """The same on a list of 6 x 6 blocks (block-sparse and packed layouts); of a diagonal block the lower triangle."""
+    tri = np.tril(np.ones((6, 6), dtype=bool))
+    seen = 0
+    for (j, k), B in zip(jk, blocks):
+        if j == k and fc[j]:
+            exact(fr.same_bits(B[tri], (d * np.eye(6))[tri]),
+                  f"{what}: diagonal block of fixed camera {j} is not {d!r} I")
+            seen += 1
+        elif fc[j] or fc[k]:
+            exact(fr.plus_zero(B), f"{what}: block ({j}, {k}) of a fixed camera is not +0.0")
+    assert seen == int(np.count_nonzero(fc)), f"{what}: {seen} diagonal blocks of fixed cameras"
+
+
+def _fused_reference(JA, JB, ex, prob, coeff, coeff_g, lens, mu, r=1, fixed=None):
+    """The reference of the fused chain from the dumped blocks, the K1 envelope and JACOBIAN_SLACK carried through.
+    fixed = (fc, fp): the placeholder rule, (coeff + mu) I once rounded on the fixed blocks (also summed over ranks:
+    only the rank that owns the camera terms writes it)."""
     nC, nP = int(prob["nC"]), int(prob["nP"])
     iidx, jidx = np.asarray(prob["iidx"]), np.asarray(prob["jidx"])
     es = _slack(prob, ex, lens)
     k1 = ar.k1_sums(JA, JB, ex, iidx, jidx, nC, nP, coeff, coeff_g, e_slack=es,
                     recomputed=("U", "ga", "V", "W", "gb"), jac_slack=_jac_slack(es, lens))
-    Ux, eU = ar.damped(*k1["U"], mu)
-    Vx, eV = ar.damped(*k1["V"], mu)
+    if fixed is None:
+        Ux, eU = ar.damped(*k1["U"], mu)
+        Vx, eV = ar.damped(*k1["V"], mu)
+    else:
+        k1 = fr.install(k1, fixed[0], fixed[1], coeff)
+        Ux, eU = fr.damped(*k1["U"], mu, fixed[0], coeff)
+        Vx, eV = fr.damped(*k1["V"], mu, fixed[1], coeff)
     Wx, eW = k1["W"]
     gx, eg = k1["g"]
     ref = ar.schur(Ux, Wx, Vx, gx, iidx, jidx, nC, nP, r=r, envU=eU, envW=eW, envV=eV, envg=eg)
@@ -211,7 +366,6 @@ def _pin_route(case, opt, h, prob):
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_assembly_entrywise(case, problems, monkeypatch):
-    from psba_amd import capi
     name, env, opt = CASES[case]
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -220,117 +374,210 @@ def test_assembly_entrywise(case, problems, monkeypatch):
     if opt.get("lens"):
         prob, kc, cov = prob
         lens = (kc, cov, 2.0)  # the robust tests' Huber scale (whitened pixels)
+    fixed = mask_of(name, opt["fixed"], prob, lens)[:2] if "fixed" in opt else None
     if opt.get("ranks"):
-        return _ranks_case(case, opt, prob)
+        with exact_parts():
+            _ranks_case(case, opt, prob, fixed)
+        return
     coeff, coeff_g = opt.get("coeff", (1.0, 1.0))
-    read_w = opt.get("read_w", False)
     sparse = opt.get("solver", 0) == 1
+    cam_major = CAM_ACC * 8 * int(prob["nC"]) > CAM_LDS_MAX or "PSBA_LIN_GLOBAL_ACC" in env
+    h = _handle(prob, lens, opt.get("solver", 0), fixed=fixed)
+    with contextlib.ExitStack() as stack:  # (left in reverse: the exact parts are reported, then the handle closed)
+        stack.callback(h.close)
+        stack.enter_context(exact_parts())
+        _pin_route(case, opt, h, prob)
+        if fixed is not None:
+            print(f"\n{case}: {minus_zero_rotation(h)} rotation coordinates of camera 0 set to -0.0")
+        JA, JB, ex, mu, W, g = mirror_layer(opt.get("mirror_label", case), h, prob, coeff, coeff_g, lens, cam_major,
+                                            opt.get("read_w", False), sparse, fixed)
+        fused_layer(case, h, prob, JA, JB, ex, mu, coeff, coeff_g, lens, opt.get("read_w", False), sparse, fixed)
+        if fixed is not None and opt["fixed"] == "island":
+            _island_properties(case, h, prob, mask_of(name, "island", prob)[2], sparse, W, g, mu)
+
+
+def mirror_layer(route, h, prob, coeff, coeff_g, lens, cam_major, read_w, sparse, fixed=None):
+    """Every sba_func.h verb from the GPU's own dumped inputs; returns the dumped (JA, JB, e), mu = 1e-3 max diag and
+    the W and g of the last linearization."""
+    from psba_amd import capi
     nC, nP = int(prob["nC"]), int(prob["nP"])
     nA = 6 * nC
     iidx, jidx = np.asarray(prob["iidx"]), np.asarray(prob["jidx"])
-    cam_major = CAM_ACC * 8 * nC > CAM_LDS_MAX or "PSBA_LIN_GLOBAL_ACC" in env
-    h = _handle(prob, lens, opt.get("solver", 0))
-    try:
-        _pin_route(case, opt, h, prob)
-        # ---- mirror layer ----
-        route = opt.get("mirror_label", case)
-        JA, JB, ex, W, g = _mirror_k1(route, h, prob, coeff, coeff_g, lens, cam_major)
-        mu = 1e-3 * h.max_diag()
-        if not sparse:
-            Us, Vs = h.update_UV(mu)
-            Us, Vs = Us.reshape(-1, 6, 6), Vs.reshape(-1, 3, 3)
-            Uc, Vc = h.update_UV(0.0)
-            h.update_UV(mu)
-            for what, got, base in (("U*", Us, Uc.reshape(-1, 6, 6)), ("V*", Vs, Vc.reshape(-1, 3, 3))):
-                x, e = ar.damped(base, np.zeros(base.shape), mu)
-                judge(route, what, got, x, e)
-            rc, Vinv = h.compute_Vinv()
-            assert rc == capi.PSBA_OK
-            ref = ar.schur(Us, W, Vs, g, iidx, jidx, nC, nP)
-            judge(route, "Vinv", Vinv, ref["Vinv"], ref["Vinv_env"])
-            judge(route, "Y", h.compute_Yblks(), ref["Y"], ref["Y_env"])
-            S = h.compute_S()
-            blk, _ = ar.dense_to_blocks(S, ref["jk"])
-            judge(route, "S", blk, ref["S"], ref["S_env"])
-            assert not np.any(ar.outside_blocks(S, ref["jk"], nC)), f"{case}: S has entries outside its blocks"
-            judge(route, "ea", h.compute_ea(), ref["ea"], ref["ea_env"])
-            rc, dpa = h.SPDinv_matVec()
-            assert rc == capi.PSBA_OK
-            eb = h.compute_eb()
-            want = ar.eb_ref(g, dpa, iidx, jidx, nC, nP, W=W) if read_w else \
-                ar.eb_ref(g, dpa, iidx, jidx, nC, nP, JA=JA, JB=JB, coeff=coeff,
-                          jac_slack=_jac_slack(_slack(prob, ex, lens), lens))
-            judge(route, "eb", eb, *want)
-            dp = h.compute_dpb()
-            assert np.array_equal(dp[:nA], dpa)
-            judge(route, "dpb", dp[nA:], *ar.dpb_ref(ref["Vinv"], ref["Vinv_env"], eb))
-            h.restore_UVdiag()
-        # ---- fused layer ----
-        route = case
-        ref, Wx, eW, gx, eg = _fused_reference(JA, JB, ex, prob, coeff, coeff_g, lens, mu)
+    JA, JB, ex, W, g = _mirror_k1(route, h, prob, coeff, coeff_g, lens, cam_major, fixed)
+    mu = 1e-3 * h.max_diag()
+    if sparse:
+        return JA, JB, ex, mu, W, g
+    Us, Vs = h.update_UV(mu)
+    Us, Vs = Us.reshape(-1, 6, 6), Vs.reshape(-1, 3, 3)
+    Uc, Vc = h.update_UV(0.0)
+    h.update_UV(mu)
+    for what, got, base in (("U*", Us, Uc.reshape(-1, 6, 6)), ("V*", Vs, Vc.reshape(-1, 3, 3))):
+        x, e = ar.damped(base, np.zeros(base.shape), mu)
+        judge(route, what, got, x, e)
+    if fixed is not None:  # the placeholders after update_UV: coeff I, and the once-rounded (coeff + mu) I
+        fc, fp = fr.flags(*fixed)
+        fx = fr.fixed_entries(fc, fp)
+        d = np.float64(coeff) + np.float64(mu)
+        for got, f, n, v in ((Uc, fc, 6, coeff), (Vc, fp, 3, coeff), (Us, fc, 6, d), (Vs, fp, 3, d)):
+            exact(fr.same_bits(got.reshape(-1, n, n)[f], np.broadcast_to(v * np.eye(n), (int(f.sum()), n, n))),
+                  f"{route}: a fixed block of update_UV is not {v!r} I")
+    rc, Vinv = h.compute_Vinv()
+    assert rc == capi.PSBA_OK
+    ref = ar.schur(Us, W, Vs, g, iidx, jidx, nC, nP)
+    judge(route, "Vinv", Vinv, ref["Vinv"], ref["Vinv_env"])
+    judge(route, "Y", h.compute_Yblks(), ref["Y"], ref["Y_env"])
+    S = h.compute_S()
+    blk, _ = ar.dense_to_blocks(S, ref["jk"])
+    judge(route, "S", blk, ref["S"], ref["S_env"])
+    assert not np.any(ar.outside_blocks(S, ref["jk"], nC)), f"{route}: S has entries outside its blocks"
+    ea = h.compute_ea()
+    judge(route, "ea", ea, ref["ea"], ref["ea_env"])
+    rc, dpa = h.SPDinv_matVec()
+    assert rc == capi.PSBA_OK
+    eb = h.compute_eb()
+    want = ar.eb_ref(g, dpa, iidx, jidx, nC, nP, W=W) if read_w else \
+        ar.eb_ref(g, dpa, iidx, jidx, nC, nP, JA=JA, JB=JB, coeff=coeff,
+                  jac_slack=_jac_slack(_slack(prob, ex, lens), lens))
+    judge(route, "eb", eb, *want)
+    dp = h.compute_dpb()
+    assert np.array_equal(dp[:nA], dpa)
+    judge(route, "dpb", dp[nA:], *ar.dpb_ref(ref["Vinv"], ref["Vinv_env"], eb))
+    if fixed is not None:
+        _exact_dense_S(f"{route} S", S, fc, d, lower=False)
+        exact(fr.plus_zero(ea[fx[:nA]]), f"{route}: e_a of a fixed camera is not +0.0")
+        exact(fr.plus_zero(dp[fx]), f"{route}: dp of a fixed block is not +0.0")
+    h.restore_UVdiag()
+    return JA, JB, ex, mu, W, g
+
+
+def fused_layer(route, h, prob, JA, JB, ex, mu, coeff, coeff_g, lens, read_w, sparse, fixed=None, linearize=True):
+    """psba_linearize ... psba_get_dp against the reference built from the dumped blocks (JA, JB, e).  linearize=False:
+    the handle already holds the linearization to judge (the one psba_linearize_ahead queued and psba_accept kept)."""
+    from psba_amd import capi
+    nC, nP = int(prob["nC"]), int(prob["nP"])
+    nA = 6 * nC
+    ref, Wx, eW, gx, eg = _fused_reference(JA, JB, ex, prob, coeff, coeff_g, lens, mu, fixed=fixed)
+    if fixed is not None:
+        fc, fp = fr.flags(*fixed)
+        fx = fr.fixed_entries(fc, fp)
+        d = np.float64(coeff) + np.float64(mu)
+        cur = np.concatenate([x.reshape(-1) for x in h.get_params(capi.PARAMS_CUR)])
+    if linearize:
         h.linearize(coeff, coeff_g)
-        h.schur_assemble(mu)
-        if sparse:
-            jk, val, ea = h.get_sparse_S()
-            slot = np.searchsorted(ref["jk"][:, 0] * nC + ref["jk"][:, 1], jk[:, 0] * nC + jk[:, 1])
-            assert np.array_equal(ref["jk"][slot], jk), f"{case}: a block outside the pattern"
-            diag = jk[:, 0] == jk[:, 1]
-            mask = np.ones(val.shape, dtype=bool)
-            mask[diag] &= np.tril(np.ones((6, 6), dtype=bool))
-            judge(route, "S", val, ref["S"][slot], ref["S_env"][slot], mask)
-            # every block of the pattern is held, as (j, k) or as (k, j)
-            held = jk[:, 0] * nC + jk[:, 1]
-            jr, kr = ref["jk"][:, 0], ref["jk"][:, 1]
-            assert np.all(np.isin(jr * nC + kr, held) | np.isin(kr * nC + jr, held)), \
-                f"{case}: the block-sparse S misses blocks"
-        else:
-            buf = h.get_reduce_buffer()
-            n32 = (nA + 31) // 32 * 32
-            S = buf[:n32 * n32].reshape(n32, n32)[:nA, :nA]
-            ea = buf[n32 * n32:n32 * n32 + nA]
-            blk, mask = ar.dense_to_blocks(S, ref["jk"], lower=True)
-            judge(route, "S", blk, ref["S"], ref["S_env"], mask)
-            assert not np.any(ar.outside_blocks(S, ref["jk"], nC, lower=True)), \
-                f"{case}: the lower triangle of S has entries outside its blocks"
-        judge(route, "ea", ea, ref["ea"], ref["ea_env"])
-        h.schur_reduce()
-        rc = h.schur_solve()
-        assert rc == capi.PSBA_OK
-        sc = h.backsub(mu)
-        assert sc.status == 0
-        dp = h.get_dp()
-        cams, pts = h.get_params(capi.PARAMS_NEW)
-        newp = np.r_[cams.reshape(-1), pts.reshape(-1)]
-        e_new = h.compute_exQT(capi.PARAMS_NEW)
-        s_new = h.obs_sq_residuals(capi.PARAMS_NEW) if lens is not None else \
-            (ar.ld(e_new).reshape(-1, 2) ** 2).sum(axis=1)
-        sums = {k: getattr(sc, k) for k in ("dp_l2", "gain_den", "new_cost", "newp_l2")}
-        _judge_k3(route, prob, ref, dp, JA, JB, ex, Wx, eW, gx, eg, coeff, read_w, sums, newp, s_new, e_new, mu, lens)
-    finally:
-        h.close()
+    if fixed is not None:
+        exact(fr.plus_zero(h.get_gradient()[fx]), f"{route}: the gradient of a fixed block is not +0.0")
+    h.schur_assemble(mu)
+    if sparse:
+        jk, val, ea = h.get_sparse_S()
+        slot = np.searchsorted(ref["jk"][:, 0] * nC + ref["jk"][:, 1], jk[:, 0] * nC + jk[:, 1])
+        assert np.array_equal(ref["jk"][slot], jk), f"{route}: a block outside the pattern"
+        diag = jk[:, 0] == jk[:, 1]
+        mask = np.ones(val.shape, dtype=bool)
+        mask[diag] &= np.tril(np.ones((6, 6), dtype=bool))
+        judge(route, "S", val, ref["S"][slot], ref["S_env"][slot], mask)
+        # every block of the pattern is held, as (j, k) or as (k, j)
+        held = jk[:, 0] * nC + jk[:, 1]
+        jr, kr = ref["jk"][:, 0], ref["jk"][:, 1]
+        assert np.all(np.isin(jr * nC + kr, held) | np.isin(kr * nC + jr, held)), \
+            f"{route}: the block-sparse S misses blocks"
+        if fixed is not None:
+            _exact_block_S(f"{route} S", jk, val, fc, d)
+    else:
+        buf = h.get_reduce_buffer()
+        n32 = (nA + 31) // 32 * 32
+        S = buf[:n32 * n32].reshape(n32, n32)[:nA, :nA]
+        ea = buf[n32 * n32:n32 * n32 + nA]
+        blk, mask = ar.dense_to_blocks(S, ref["jk"], lower=True)
+        judge(route, "S", blk, ref["S"], ref["S_env"], mask)
+        assert not np.any(ar.outside_blocks(S, ref["jk"], nC, lower=True)), \
+            f"{route}: the lower triangle of S has entries outside its blocks"
+        if fixed is not None:
+            _exact_dense_S(f"{route} S", S, fc, d, lower=True)
+    judge(route, "ea", ea, ref["ea"], ref["ea_env"])
+    if fixed is not None:
+        exact(fr.plus_zero(ea[fx[:nA]]), f"{route}: e_a of a fixed camera is not +0.0")
+    h.schur_reduce()
+    rc = h.schur_solve()
+    assert rc == capi.PSBA_OK
+    sc = h.backsub(mu)
+    assert sc.status == 0
+    dp = h.get_dp()
+    cams, pts = h.get_params(capi.PARAMS_NEW)
+    newp = np.r_[cams.reshape(-1), pts.reshape(-1)]
+    if fixed is not None:
+        exact(fr.plus_zero(dp[fx]), f"{route}: dp of a fixed block is not +0.0")
+        exact(fr.same_bits(newp[fx], cur[fx]), f"{route}: the proposal's fixed blocks are not the current bits")
+        assert not np.array_equal(newp[~fx], cur[~fx])
+    e_new = h.compute_exQT(capi.PARAMS_NEW)
+    s_new = h.obs_sq_residuals(capi.PARAMS_NEW) if lens is not None else \
+        (ar.ld(e_new).reshape(-1, 2) ** 2).sum(axis=1)
+    sums = {k: getattr(sc, k) for k in ("dp_l2", "gain_den", "new_cost", "newp_l2")}
+    _judge_k3(route, prob, ref, dp, JA, JB, ex, Wx, eW, gx, eg, coeff, read_w, sums, newp, s_new, e_new, mu, lens)
+    return sc, dp
 
 
-def _ranks_case(case, opt, prob):
+def _island_properties(case, h, prob, info, sparse, W, g, mu):
+    """The island mask on an assembled try: every W of the free point that sees only fixed cameras is +0.0 (and its
+    g_b is not), and the free camera that sees only fixed points has no entry in S off its diagonal block (the block
+    itself is U*_j: the reference of the judge above has no other term in it)."""
+    iidx = np.asarray(prob["iidx"])
+    nA = 6 * int(prob["nC"])
+    pt, cam = info["island_point"], info["island_cam"]
+    assert fr.plus_zero(W.reshape(-1, 18)[iidx == pt]) and np.all(g[nA + 3 * pt:nA + 3 * pt + 3] != 0.0), \
+        f"{case}: the island point {pt}"
+    h.linearize(1.0, 1.0)
+    h.schur_assemble(mu)
+    if sparse:
+        jk, val, _ = h.get_sparse_S()
+        off = ((jk[:, 0] == cam) | (jk[:, 1] == cam)) & (jk[:, 0] != jk[:, 1])
+        assert not np.any(val[off]), f"{case}: the island camera {cam} has entries off its diagonal block"
+        assert np.all(np.diagonal(val[(jk[:, 0] == cam) & (jk[:, 1] == cam)][0]) > 0)
+    else:
+        n32 = (nA + 31) // 32 * 32
+        S = h.get_reduce_buffer()[:n32 * n32].reshape(n32, n32)[:nA, :nA]
+        c0 = 6 * cam
+        assert not np.any(S[c0:c0 + 6, :c0]) and not np.any(S[c0 + 6:, c0:c0 + 6]), \
+            f"{case}: the island camera {cam} has entries off its diagonal block"
+        assert np.all(np.diagonal(S[c0:c0 + 6, c0:c0 + 6]) > 0)
+
+
+def _ranks_case(case, opt, prob, fixed=None):
     """Two point shards (capi.shard_problem), one handle each with a rank layout; PSBA_SCHUR_PACKED makes them take
     the packed route, whose buffers (the lower block triangle in canonical order, e_a in six upper slots of each
-    diagonal block) are added on the host, as the all-reduce would."""
+    diagonal block) are added on the host, as the all-reduce would.  fixed: camera flags replicated, point flags
+    sharded with the points; only rank 0 writes the placeholder of a fixed camera, so the summed diagonal block is
+    (coeff + mu) I exactly, as on a single handle."""
     from psba_amd import capi
     nr = opt["ranks"]
     nC = int(prob["nC"])
     nA = 6 * nC
+    if fixed is not None:
+        prob = capi.Problem(prob, fixed_cams=fixed[0], fixed_pts=fixed[1])
     shards = [capi.shard_problem(prob, nr, r) for r in range(nr)]
-    hs = [_handle(sh, None, rank=(nr, r)) for r, sh in enumerate(shards)]
+    masks = [(sh["fixed_cams"], sh["fixed_pts"]) if fixed is not None else None for sh in shards]
+    hs = [_handle(sh, None, rank=(nr, r), fixed=m) for r, (sh, m) in enumerate(zip(shards, masks))]
     try:
         for h, sh in zip(hs, shards):
             _pin_route(case, opt, h, sh)
+            if fixed is not None:
+                minus_zero_rotation(h)
+        if fixed is not None:
+            assert sum(int(np.count_nonzero(m[1])) for m in masks) == int(np.count_nonzero(fixed[1]))
         # mirror: K1 of each shard against its own sums
-        parts = [_mirror_k1(f"{case} (rank {r})", h, sh, 1.0, 1.0, None, False)[:3] for r, (h, sh) in
-                 enumerate(zip(hs, shards))]
+        parts = [_mirror_k1(f"{case} (rank {r})", h, sh, 1.0, 1.0, None, False, m, owner=r == 0)[:3]
+                 for r, (h, sh, m) in enumerate(zip(hs, shards, masks))]
         JA, JB, ex = (np.concatenate([p[k] for p in parts]) for k in range(3))
         ref0 = ar.k1_sums(JA, JB, ex, prob["iidx"], prob["jidx"], nC, int(prob["nP"]))
-        mu = 1e-3 * max(float(np.max(np.diagonal(ref0["U"][0], axis1=1, axis2=2))),
-                        float(np.max(np.diagonal(ref0["V"][0], axis1=1, axis2=2))))
-        ref, Wx, eW, gx, eg = _fused_reference(JA, JB, ex, prob, 1.0, 1.0, None, mu, r=nr)
+        if fixed is None:
+            mu = 1e-3 * max(float(np.max(np.diagonal(ref0["U"][0], axis1=1, axis2=2))),
+                            float(np.max(np.diagonal(ref0["V"][0], axis1=1, axis2=2))))
+        else:
+            mu = 1e-3 * fr.free_max(ref0["U"][0].astype(np.float64), ref0["V"][0].astype(np.float64), *fixed)
+        ref, Wx, eW, gx, eg = _fused_reference(JA, JB, ex, prob, 1.0, 1.0, None, mu, r=nr, fixed=fixed)
+        if fixed is not None:
+            fc, fp = fr.flags(*fixed)
+            fx = fr.fixed_entries(fc, fp)
+            cur = np.concatenate([hs[0].get_params()[0].reshape(-1)] + [h.get_params()[1].reshape(-1) for h in hs])
         for h in hs:
             h.linearize(1.0, 1.0)
             h.schur_assemble(mu)
@@ -350,6 +597,12 @@ def _ranks_case(case, opt, prob):
         dslot = np.arange(nC) * (np.arange(nC) + 1) // 2 + np.arange(nC)
         ea = P[dslot].reshape(nC, 36)[:, EA_SLOT].reshape(-1)
         judge(case, "ea", ea, ref["ea"], ref["ea_env"])
+        if fixed is not None:
+            d = np.float64(1.0) + np.float64(mu)
+            offd = P[canon].copy()
+            offd[j[low] == k[low]] = np.tril(offd[j[low] == k[low]])  # (the upper slots of a diagonal block carry e_a)
+            _exact_block_S(f"{case} summed packed S", ref["jk"][low], offd, fc, d)
+            exact(fr.plus_zero(ea[fx[:nA]]), f"{case}: e_a of a fixed camera is not +0.0")
         sums = dict.fromkeys(("dp_l2", "gain_den", "new_cost", "newp_l2"), 0.0)
         dps, props, e_new = [], [], []
         for h in hs:
@@ -365,6 +618,10 @@ def _ranks_case(case, opt, prob):
         assert all(np.array_equal(d[:nA], dps[0][:nA]) for d in dps)  # cameras are replicated
         dp = np.concatenate([dps[0][:nA]] + [d[nA:] for d in dps])
         newp = np.concatenate([props[0][0].reshape(-1)] + [p.reshape(-1) for _, p in props])
+        if fixed is not None:
+            exact(fr.plus_zero(dp[fx]), f"{case}: dp of a fixed block is not +0.0")
+            exact(fr.same_bits(newp[fx], cur[fx]), f"{case}: the proposal's fixed blocks are not the current bits")
+            assert all(fr.same_bits(c[fc], props[0][0][fc]) for c, _ in props)
         e_new = np.concatenate(e_new)
         s_new = (ar.ld(e_new).reshape(-1, 2) ** 2).sum(axis=1)
         _judge_k3(case, prob, ref, dp, JA, JB, ex, Wx, eW, gx, eg, 1.0, False, sums, newp, s_new, e_new, mu, None,
