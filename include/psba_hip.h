@@ -614,6 +614,22 @@ typedef struct {
 void psba_lm_default_options(psba_lm_options *o);
 /* log rows: (itno, new ||e||^2, rho, mu, accepted{1,0,-1=solve failed}) per damping try */
 int psba_levmar(psba_handle h, const psba_lm_options *opts, psba_lm_result *res, double *log);
+/* The linearizations psba_levmar queues ahead take a lean form on an eligible handle: K1 stores the Jacobian factors
+ * (A | B | e, 160 bytes per observation) and neither W nor the per-camera sums, and the Schur assembly forms S, e_a
+ * and g_a from them.  Eligible: six-parameter camera blocks, one rank without a communicator, the LDS-partition
+ * Schur route in its rows layout (psba_schur_path 0), the dense solver, K3 in its recompute form, no lens model,
+ * covariance weights, robust loss, fixed blocks or priors, no point seen by more than 256 cameras; PSBA_LEAN_LIN=0
+ * (read at upload) forces the standard form.  Every other handle takes the standard form.  When psba_levmar returns,
+ * every linearization a later verb can reach is a standard one.  *lean = 1: the last psba_levmar of this handle
+ * queued lean linearizations, 0: standard ones (or none yet). */
+int psba_lm_ran_lean(psba_handle h, int *lean);
+/* For tests of the lean assembly at a chosen mu and chosen coefficients: linearizes the CURRENT parameters once more,
+ * in the lean form, behind a psba_linearize with the handle's coefficients.  W, U and g_a of that psba_linearize stay
+ * valid; psba_schur_assemble then takes the lean route (and its reduce rewrites g_a from the lean sums) until the
+ * next linearization.  The sba_func.h mirror verbs that assemble S (they dump Y and V^-1, which the lean route does
+ * not form) return PSBA_E_STATE until then.  PSBA_E_STATE on a handle that is not eligible, or that could not
+ * allocate the records. */
+int psba_linearize_lean(psba_handle h);
 
 /* ---- the trust-region caller, PSBA/trust_region.cpp:49-595, and its extra operators -------
  * (B = 2 J^T J, g = -2 J^T e through psba_linearize(h, 2, -2); with a communicator the points may be

@@ -85,6 +85,8 @@ SIGNATURES = [
     ("psba_get_params", C.c_int, [_h, C.c_int, _dp, _dp]),
     ("psba_get_dims", C.c_int, [_h, _ip, _ip, _ip]),
     ("psba_schur_path", C.c_int, [_h, C.POINTER(C.c_int)]),
+    ("psba_lm_ran_lean", C.c_int, [_h, C.POINTER(C.c_int)]),
+    ("psba_linearize_lean", C.c_int, [_h]),
     ("psba_residual", C.c_int, [_h, C.c_int, _dp]),
     ("psba_linearize", C.c_int, [_h, C.c_double, C.c_double]),
     ("psba_max_diag", C.c_int, [_h, _dp]),
@@ -730,6 +732,18 @@ class Psba:
         v = C.c_int()
         self._ck(lib.psba_schur_path(self._h, C.byref(v)))
         return v.value
+
+    def lm_ran_lean(self):
+        """True: the last levmar of this handle queued its look-ahead linearizations in the lean form (Jacobian factors
+        to the Schur assembly, no W and no per-camera sums); False: in the standard form (psba_lm_ran_lean)."""
+        v = C.c_int()
+        self._ck(lib.psba_lm_ran_lean(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def linearize_lean(self):
+        """Test hook: the current parameters linearized once more in the lean form, behind linearize(); the next
+        schur_assemble takes the lean route (psba_linearize_lean)."""
+        self._ck(lib.psba_linearize_lean(self._h))
 
     def residual(self, which=PARAMS_CUR):
         v = C.c_double()

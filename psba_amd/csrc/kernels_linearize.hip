@@ -37,6 +37,8 @@ struct LinArgs {
   // LENS_DIST / LENS_COV instantiations.  The robust loss is every kernel's last argument (read only by the
   // LENS_ROBUST instantiations; behind the others, so that their offsets stay put).
   const double *kc, *wl;
+  // lean form (k_linearize2<.., LEAN>): [nO][LEAN_REC] A (2 x 6) | B (2 x 3) | e per observation, behind everything else
+  double *R;
 };
 
 // GACC: many cameras -- the 27 sums per camera do not fit the LDS.  They are then formed by a
@@ -208,9 +210,14 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p, RobustLoss rl
 //  * the LDS that B / e needed holds the second half of W: one staging, one barrier, one flush per tile;
 //  * the NEXT tile's indices and the eighteen parameter doubles they lead to are fetched as soon as this tile's
 //    Jacobian is done, so their latency runs under the camera atomics, the scan and the W flush.
-template <bool DUMP, bool GACC, int LM>
+// LEAN (psba_levmar's look-ahead linearizations): the observation's Jacobian factors leave as they are, one
+// record A (12) | B (6) | e (2) through the same staging, and K2 forms everything per camera from them -- no W, no
+// camera table in the LDS, no atomics, no slab, no k_cam_reduce behind this kernel.  V_i, g_b,i and the scalar publish
+// are the standard form's, instruction for instruction.
+template <bool DUMP, bool GACC, int LM, bool LEAN = false>
 __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss rl, FixedMask fm) {
-  __shared__ double sW[TILE_OBS * 19];          // W blocks of the tile (row stride 19 doubles: odd, conflict-free stores)
+  constexpr int ROW = LEAN ? LEAN_REC + 1 : 19, REC = LEAN ? LEAN_REC : 18;  // staged row stride (odd) and doubles stored
+  __shared__ double sW[TILE_OBS * ROW];         // W blocks (records) of the tile (odd row stride: conflict-free stores)
   __shared__ double sCarV[TILE_OBS / 64][9];    // a wave's last lane: its scan values (the tail of its last segment)
   __shared__ int sCarP[TILE_OBS / 64][3];       // point of the wave's first lane, of its last lane, whole wave one point?
   extern __shared__ double sAcc[];              // [nC][27]
@@ -221,7 +228,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss r
     __syncthreads();
     if (tid == 0) p.pub_dst[NSCAL] = p.pub_stamp;
   }
-  const int nAcc = GACC ? 0 : p.nC * CAM_ACC;
+  const int nAcc = GACC || LEAN ? 0 : p.nC * CAM_ACC;
   for (int t = tid; t < nAcc; t += TILE_OBS) sAcc[t] = 0.0;
   __syncthreads();
 
@@ -270,11 +277,20 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss r
         for (int k = 0; k < 6; k++) p.dbg_JB[6 * (size_t)a + k] = B[k];
       }
       // W_ij = coeff * A^T B, 6x3 row-major, staged (row stride 19) and flushed as contiguous runs below
-      double *w = sW + 19 * tid;
+      double *w = sW + ROW * tid;
+      if (LEAN) {
 #pragma unroll
-      for (int r = 0; r < 6; r++)
+        for (int k = 0; k < 12; k++) w[k] = A[k];
 #pragma unroll
-        for (int c = 0; c < 3; c++) w[3 * r + c] = fix_w<LM>(fx, p.coeff * (A[r] * B[c] + A[6 + r] * B[3 + c]));
+        for (int k = 0; k < 6; k++) w[12 + k] = B[k];
+        w[18] = e[0];
+        w[19] = e[1];
+      } else {
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+          for (int c = 0; c < 3; c++) w[3 * r + c] = fix_w<LM>(fx, p.coeff * (A[r] * B[c] + A[6 + r] * B[3 + c]));
+      }
       // this observation's terms of V_i (upper triangle) and g_b,i
       int q = 0;
 #pragma unroll
@@ -284,7 +300,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss r
 #pragma unroll
       for (int r = 0; r < 3; r++) v[6 + r] = B[r] * e[0] + B[3 + r] * e[1];
       // camera sums: upper triangle of A^T A, then A^T e
-      if (p.mode != 1 && !GACC) {
+      if (p.mode != 1 && !GACC && !LEAN) {
         double *acc = sAcc + CAM_ACC * (size_t)jc;
         int k = 0;
 #pragma unroll
@@ -337,9 +353,9 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss r
     __syncthreads();
     // W out: contiguous runs from the staged rows
     if (p.mode != 2) {
-      double *dst = p.W + 18 * (size_t)o0;
-      const int n = 18 * (o1 - o0);
-      for (int t = tid; t < n; t += TILE_OBS) dst[t] = sW[19 * (t / 18) + t % 18];
+      double *dst = (LEAN ? p.R : p.W) + REC * (size_t)o0;
+      const int n = REC * (o1 - o0);
+      for (int t = tid; t < n; t += TILE_OBS) dst[t] = sW[ROW * (t / REC) + t % REC];
     }
     // the last lane of a point's run stores V_i | g_b,i; a run that began in earlier waves collects their tails
     if (act && p.mode != 3) {
@@ -361,7 +377,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss r
     dsc = dn;
     __syncthreads();  // sW and the carry rows are free again
   }
-  if (GACC) return;
+  if (GACC || LEAN) return;
   double *slab = p.campart + (size_t)blockIdx.x * nAcc;
   for (int t = tid; t < nAcc; t += TILE_OBS) slab[t] = sAcc[t];
 }
@@ -712,8 +728,11 @@ static void enqueue_linearize(psba_ctx *h, const LinArgs &a, const RobustLoss &r
   }
 }
 
-int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
+int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish, bool lean) {
   if (h->cnp != 6) return dump ? mirror_refused(h) : launch_linearize_free(h, ahead, publish);
+  // lean: the caller has asked lean_eligible() (psba_api.cpp) -- no lens model, loss or mask, the camera table in the LDS,
+  // no long points, no dump; the set's flag tells K2 which form it finds there
+  (ahead ? h->lean_alt : h->lean_cur) = lean;
   const Dims &d = h->d;
   LinArgs a;
   a.camconst = h->camconst;
@@ -743,8 +762,16 @@ int launch_linearize(psba_ctx *h, bool dump, bool ahead, bool publish) {
   a.pub_stamp = h->pub_seq;
   a.kc = h->lens_kc;
   a.wl = h->lens_w;
+  a.R = ahead ? h->R_alt : h->R;
   const RobustLoss rl = make_robust_loss(h->loss_kind, h->loss_c);
   const FixedMask fm = {h->fix_cams, h->fix_pts};
+  if (lean) {  // one launch: PV and the records of this set; U and g_a of the set are not written (K2's reduce forms g_a)
+    a.mode = 0;
+    ProfScope ps(h, PSBA_K_LINEARIZE);
+    hipLaunchKernelGGL((k_linearize2<false, false, LENS_PLAIN, true>), dim3(h->nPart), dim3(TILE_OBS), 0, h->stream, a, rl, fm);
+    PSBA_HIP(h, hipGetLastError());
+    return PSBA_OK;
+  }
   {
     const char *m = getenv("PSBA_LIN_MODE");
     a.mode = m ? atoi(m) : 0;

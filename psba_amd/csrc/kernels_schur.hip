@@ -251,11 +251,96 @@ __device__ __forceinline__ void schur_block_add(double *blk, const double (&Y)[1
   }
 }
 
+// The same product from the observations' Jacobian factors (lean form).  W = coeff A^T B has rank 2, so
+//   -W_a V*^-1 W_b^T = A_a^T M A_b,   M = -coeff^2 B_a V*^-1 B_b^T   (2 x 2)
+// and the self-product's M + coeff I makes the block the observation's whole term of S_jj, U_j included.  The self
+// item also carries, in upper-triangle slots of the diagonal block, the e_a term -Y_a g_b,i = -coeff A_a^T B_a V*^-1 g_b,i
+// (EA_SLOT, as on the standard form) and the g_a term coeff_g A_a^T e_a (GA_SLOT): no atomic more than the standard form's 36.
+// ra / rb: the records A (2 x 6) | B (2 x 3) | e of a and of its partner.
+__device__ __forceinline__ void schur_lean_item(const SchurLdsArgs &p, double *blk, const double *pv, const double2 *ra,
+                                                const double2 *rb, bool self) {
+  double v[6], vi[6], A[12], B[6], Ab[12], Bb[6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) v[k] = pv[k];
+  const double g0 = pv[6], g1 = pv[7], g2 = pv[8];
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    const double2 q = ra[k];
+    A[2 * k] = q.x;
+    A[2 * k + 1] = q.y;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double2 q = ra[6 + k];
+    B[2 * k] = q.x;
+    B[2 * k + 1] = q.y;
+  }
+  const double2 ee = ra[9];
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    const double2 q = rb[k];
+    Ab[2 * k] = q.x;
+    Ab[2 * k + 1] = q.y;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double2 q = rb[6 + k];
+    Bb[2 * k] = q.x;
+    Bb[2 * k + 1] = q.y;
+  }
+  v[0] += p.mu;
+  v[3] += p.mu;
+  v[5] += p.mu;
+  if (sym3_inverse(v, vi)) p.status[0] = p.try_id;
+  // M[q][s] = -coeff^2 B_a,q . (V*^-1 B_b,s); the self-product's diagonal takes U's coeff
+  double M[2][2];
+  const double c2 = -p.coeff * p.coeff;
+#pragma unroll
+  for (int s = 0; s < 2; s++) {
+    const double b0 = Bb[3 * s], b1 = Bb[3 * s + 1], b2 = Bb[3 * s + 2];
+    const double t0 = vi[0] * b0 + vi[1] * b1 + vi[2] * b2;
+    const double t1 = vi[1] * b0 + vi[3] * b1 + vi[4] * b2;
+    const double t2 = vi[2] * b0 + vi[4] * b1 + vi[5] * b2;
+#pragma unroll
+    for (int q = 0; q < 2; q++) M[q][s] = c2 * (B[3 * q] * t0 + B[3 * q + 1] * t1 + B[3 * q + 2] * t2);
+  }
+  M[0][0] += self ? p.coeff : 0.0;
+  M[1][1] += self ? p.coeff : 0.0;
+  // the two vectors the self item's riders are A_a^T of: u = -coeff B_a V*^-1 g_b,i (e_a term), coeff_g e (g_a term)
+  const double h0 = vi[0] * g0 + vi[1] * g1 + vi[2] * g2;
+  const double h1 = vi[1] * g0 + vi[3] * g1 + vi[4] * g2;
+  const double h2 = vi[2] * g0 + vi[4] * g1 + vi[5] * g2;
+  const double u0 = -p.coeff * (B[0] * h0 + B[1] * h1 + B[2] * h2), u1 = -p.coeff * (B[3] * h0 + B[4] * h1 + B[5] * h2);
+  const double f0 = p.coeff_g * ee.x, f1 = p.coeff_g * ee.y;
+  // a row of the block at a time, as in schur_block_add: P_r = (A_a^T M)_r, then its six values side by side
+#pragma unroll
+  for (int r = 0; r < 6; r++) {
+    const double P0 = A[r] * M[0][0] + A[6 + r] * M[1][0], P1 = A[r] * M[0][1] + A[6 + r] * M[1][1];
+    double val[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) val[c] = P0 * Ab[c];
+#pragma unroll
+    for (int c = 0; c < 6; c++) val[c] = fma(P1, Ab[6 + c], val[c]);
+    // the riders of the self item: slot 6 r + c holds term (c - 1 | 5 | c - 3 | c) of e_a resp. g_a
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      if (r == 0 && c >= 1) val[c] = self ? A[c - 1] * u0 + A[6 + c - 1] * u1 : val[c];
+      if (r == 1 && c == 2) val[c] = self ? A[5] * u0 + A[11] * u1 : val[c];
+      if (r == 1 && c >= 3) val[c] = self ? A[c - 3] * f0 + A[6 + c - 3] * f1 : val[c];
+      if (r == 2 && c >= 3) val[c] = self ? A[c] * f0 + A[6 + c] * f1 : val[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 6; c++) atomicAdd(&blk[6 * r + c], val[c]);
+  }
+}
+
 // one item = one product Y_a W_b^T of one point; see the schedule above
-template <bool DUMP>
+template <bool DUMP, bool LEAN = false>
 __global__ __launch_bounds__(SCHUR_THREADS) void k_schur_lds(SchurLdsArgs p) {
   extern __shared__ double sPart[];  // [nblk][37]
   const int tid = threadIdx.x;
+  if (LEAN && blockIdx.x == 0)  // the reduce adds the EA and the GA sums of an entry into e_a, in either order
+    for (int t = tid; t < p.nA; t += SCHUR_THREADS) p.ea[t] = 0.0;
   int w = blockIdx.x;
   if ((p.nWg & 7) == 0) w = (blockIdx.x & 7) * (p.nWg >> 3) + (blockIdx.x >> 3);
   const SchurWg wg = p.wg[w];
@@ -327,6 +412,11 @@ __global__ __launch_bounds__(SCHUR_THREADS) void k_schur_lds(SchurLdsArgs p) {
     const int pos = (int)(item >> (ITEM_OBS_BITS + ITEM_PT_BITS + ITEM_BOFF_BITS));
     // every address is known now: issue all loads of the product together
     const double *pv = p.PV + 9 * (size_t)i;
+    if (LEAN) {
+      schur_lean_item(p, sPart + BLK_STRIDE * pos, pv, reinterpret_cast<const double2 *>(p.R + LEAN_REC * (size_t)a),
+                      reinterpret_cast<const double2 *>(p.R + LEAN_REC * (size_t)(a - boff)), boff == 0);
+      continue;
+    }
     const double2 *wa = reinterpret_cast<const double2 *>(p.W + 18 * (size_t)a);
     const double2 *wb2 = reinterpret_cast<const double2 *>(p.W + 18 * (size_t)(a - boff));
     double v[6], w[18], wb[18];
@@ -766,6 +856,13 @@ static int launch_schur_lds(psba_ctx *h, double mu, bool dump) {
   a.mu = mu;
   a.nWg = h->nWg;
   a.try_id = h->try_id;
+  // the current set was linearized lean (psba_levmar, lean_eligible: rows layout, one rank, not packed, no dump)
+  const bool lean = h->lean_cur;
+  a.R = h->R;
+  a.coeff = h->coeff;
+  a.coeff_g = h->coeff_g;
+  a.ea = h->red + (size_t)h->n32 * h->n32;
+  a.nA = d.nA;
   // the first diagonal block can be factored beside the S-reduce only if S is complete on this rank
   // (PSBA_SCHUR_NO_FLUSH_DIAG: test hook -- a single-rank communicator then takes the multi-rank
   // route, where k_schur_expand factors the block after the all-reduce)
@@ -800,6 +897,8 @@ static int launch_schur_lds(psba_ctx *h, double mu, bool dump) {
   r.linv = h->chol_ws;
   r.ring_copies = 0;
   r.ring_stride = 0;
+  r.lean = lean ? 1 : 0;
+  r.ga_out = h->ga;
   int worst = 0;
   long long npos = 0;
   for (int g = 0; g < h->nGroups; g++) {
@@ -841,7 +940,9 @@ static int launch_schur_lds(psba_ctx *h, double mu, bool dump) {
 #endif
       (void)mode;
       if (launched) {
-      } else if (dump)
+      } else if (lean)
+        hipLaunchKernelGGL((k_schur_lds<false, true>), G, B, lds, h->stream, a);
+      else if (dump)
         hipLaunchKernelGGL((k_schur_lds<true>), G, B, lds, h->stream, a);
       else
         hipLaunchKernelGGL((k_schur_lds<false>), G, B, lds, h->stream, a);
@@ -895,6 +996,9 @@ static int launch_schur_sparse(psba_ctx *h, double mu) {
 
 int launch_schur(psba_ctx *h, double mu, bool dump) {
   if (h->cnp != 6) return dump ? mirror_refused(h) : launch_schur_free(h, mu);
+  // (reachable behind psba_linearize_lean only: psba_levmar leaves no lean set behind)
+  if (dump && h->lean_cur)
+    return fail(h, PSBA_E_STATE, "the sba_func.h mirror verbs need a standard linearization: psba_linearize first (the current one is lean)");
   h->try_id++;
   h->diag_done = false;
   h->packed_pending = false;  // status words are generation stamps: nothing to zero
@@ -911,6 +1015,7 @@ int launch_schur(psba_ctx *h, double mu, bool dump) {
       const auto attr = hipFuncAttributeMaxDynamicSharedMemorySize;
       PSBA_HIP(h, hipFuncSetAttribute((const void *)k_schur_lds<true>, attr, dyn));
       PSBA_HIP(h, hipFuncSetAttribute((const void *)k_schur_lds<false>, attr, dyn));
+      PSBA_HIP(h, hipFuncSetAttribute((const void *)k_schur_lds<false, true>, attr, dyn));
       PSBA_HIP(h, hipFuncSetAttribute((const void *)k_schur_lds_runs<true>, attr, dyn));
       PSBA_HIP(h, hipFuncSetAttribute((const void *)k_schur_lds_runs<false>, attr, dyn));
       h->lds_attr_set = true;

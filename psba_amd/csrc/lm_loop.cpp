@@ -31,10 +31,14 @@ int psba_levmar(psba_handle h, const psba_lm_options *opts, psba_lm_result *res,
   *res = psba_lm_result();
   auto t_begin = std::chrono::steady_clock::now();
   int rc;
-#define LM_TRY(x)          \
-  do {                     \
-    rc = (x);              \
-    if (rc < 0) return rc; \
+  // on every way out, the handle holds standard linearizations only (lean_restore, psba_api.cpp)
+#define LM_TRY(x)                  \
+  do {                             \
+    rc = (x);                      \
+    if (rc < 0) {                  \
+      (void)psba::lean_restore(h); \
+      return rc;                   \
+    }                              \
   } while (0)
 
   double ex_L2 = 0, new_ex_L2 = 0, p_L2 = 0, dp_L2 = 0, mu = 0, rho = 0;
@@ -47,6 +51,10 @@ int psba_levmar(psba_handle h, const psba_lm_options *opts, psba_lm_result *res,
   double maxdiag0 = 0;
   LM_TRY(psba_begin(h, 1.0, 1.0, &ex_L2, &maxdiag0));
   res->init_err = ex_L2;
+  // the linearizations queued ahead leave their Jacobian factors to the Schur assembly where the handle
+  // allows it; psba_begin's own stays standard (max_diag reads U)
+  const bool lean = psba::lean_prepare(h);
+  h->lm_lean = lean;
 
   for (; itno < opts->max_iter && flag == PSBA_ITER_CONTINUE; itno++) {  // :100
     LM_TRY(psba_linearize(h, 1.0, 1.0));                                  // :103-108
@@ -82,7 +90,7 @@ int psba_levmar(psba_handle h, const psba_lm_options *opts, psba_lm_result *res,
       // per failed try -- its results are dropped with the rejected step, nothing else depends on
       // them, and skipping the launch would need the status on the host first, i.e. the very
       // round trip the look-ahead exists to hide)
-      if (itno + 1 < opts->max_iter) LM_TRY(psba_linearize_ahead(h));  // no iteration left to use it otherwise
+      if (itno + 1 < opts->max_iter) LM_TRY(psba::linearize_ahead(h, lean));  // no iteration left to use it otherwise
       LM_TRY(psba_backsub_wait(h, &sc));
       if (!(sc.status & PSBA_NOT_SPD)) {
         dp_L2 = sc.dp_l2;
@@ -141,6 +149,7 @@ int psba_levmar(psba_handle h, const psba_lm_options *opts, psba_lm_result *res,
 #undef LM_TRY
   // nothing of this call is left on the device when it returns (a linearization computed ahead
   // for a step that was then not taken may still be running)
+  if ((rc = psba::lean_restore(h)) < 0) return rc;
   if (hipStreamSynchronize(h->stream) != hipSuccess) return PSBA_E_HIP;
   res->flag = flag;
   res->iters = itno;

@@ -23,6 +23,7 @@ void model_changed(psba_ctx *h) {
   h->free_obs = false;
   h->damp_ok = false;
   h->cov_ok = h->cov_pts_ok = false;
+  h->lean_cur = h->lean_alt = false;  // (the linearizations they describe are gone)
 }
 
 void params_changed(psba_ctx *h) {

@@ -626,6 +626,12 @@ int psba_upload_problem(psba_handle h, int nCams, int n3Dpts, int n2Dprojs, cons
   TRY(alloc_work_buffers(h));
   if (h->cam_global || h->cnp != 6) TRY(upload_camera_index(h, u));
   TRY(plan_schur(h, u));
+  // the lean form of psba_levmar's look-ahead linearizations: what the problem's shape and the switch
+  // PSBA_LEAN_LIN=0 decide is decided here; lean_eligible() adds what can change after the upload, and the record
+  // buffers come with the first psba_levmar that can use them (lean_prepare)
+  h->lean_ok = h->cnp == 6 && h->solver != PSBA_SOLVER_PCG && h->nGroups > 0 && h->ring_nWg == 0 && !h->schur_runs &&
+               !h->schur_pairs && !h->cam_global && h->nLong == 0;
+  if (const char *e = getenv("PSBA_LEAN_LIN")) h->lean_ok = h->lean_ok && atoi(e) != 0;
   TRY(copy_inputs(h, u));
   // the blocking copies went through the null stream, which this handle's non-blocking stream does not wait for:
   // everything on the device is done before the first kernel can be queued
@@ -892,18 +898,87 @@ int psba_backsub_async(psba_handle h, double mu) {
   return PSBA_OK;
 }
 
-int psba_linearize_ahead(psba_handle h) {
+extern "C++" {
+namespace psba {
+
+// May psba_levmar queue its look-ahead linearizations in the lean form?  Everything the lean kernels leave out: a lens
+// model, covariance weights or a robust loss (h->lens), fixed blocks, priors, more than one rank or a communicator,
+// the packed reduce, any K2 route but the LDS partitions in the rows layout (lean_ok, PSBA_SCHUR_ATOMIC), K3 reading W,
+// the development forms of K1 and K2.  Anything else takes the standard form, silently.
+bool lean_eligible(psba_ctx *h) {
+  return h->lean_ok && h->uploaded && h->solver == PSBA_SOLVER_DENSE && h->lens == 0 && !h->has_fixed && !h->has_prior &&
+         !h->comm && h->nranks == 1 && !getenv("PSBA_SCHUR_ATOMIC") && !getenv("PSBA_BACK_READ_W") && !getenv("PSBA_LIN_V1") &&
+         !getenv("PSBA_LIN_MODE") && !getenv("PSBA_SCHUR_MODE");
+}
+
+// lean_eligible, and the record buffers exist: they are allocated by the first call that can use them, so a handle that
+// never runs psba_levmar lean does not hold them, and a handle that cannot have them (no memory) takes the standard
+// form from then on like any other ineligible one
+bool lean_prepare(psba_ctx *h) {
+  if (!lean_eligible(h)) return false;
+  if (h->R.get() && h->R_alt.get()) return true;
+  const size_t n = (size_t)LEAN_REC * h->d.nO;
+  if (h->R.alloc(h, n) < 0 || h->R_alt.alloc(h, n) < 0) {
+    h->R.reset();
+    h->R_alt.reset();
+    (void)hipGetLastError();  // (the failed hipMalloc is not this call's error)
+    h->err.clear();
+    h->lean_ok = false;
+    return false;
+  }
+  return true;
+}
+
+int linearize_ahead(psba_ctx *h, bool lean) {
   CHECK_H_NOJOIN(h);  // K1 reads and writes nothing the scalar collective touches
   NEED(h, h->backsub_pending || h->backsubbed, "psba_backsub_async / psba_backsub first");
   const bool carry = h->backsub_pending && h->publish_deferred;
   if (carry) h->pub_seq += 1.0;
   h->free_obs = false;  // (free_Be is about to hold the blocks at the proposal, W those at the current parameters)
-  TRY(launch_linearize(h, false, true, carry));
+  TRY(launch_linearize(h, false, true, carry, lean));
   if (carry) {
     h->publish_deferred = false;
     h->publish_in_k1 = true;
   }
   h->ahead = true;
+  return PSBA_OK;
+}
+
+// Before psba_levmar returns: a lean linearization that a later verb could still reach -- the current set while it
+// counts as linearized or spares the next psba_linearize, the set queued ahead while psba_accept may still take it --
+// is replaced by a standard one at the same parameters and coefficients, so that W, U and g_a are what every other
+// verb expects.  (One K1 where the call ends on an accepted step with its look-ahead queued, two -- the set queued
+// ahead and the current one -- where it ends after a rejected try or on an error, none where it ends on an accepted
+// step without a look-ahead, as through max_iter; PV is rewritten with the same values.)
+// Because no lean set outlives psba_levmar, and psba_levmar linearizes with (1, 1) throughout, the coefficients
+// launch_schur_lds takes from the handle when it assembles are the ones the set's K1 was launched with (PV carries
+// them); the test hook below keeps to that by taking them over from the psba_linearize in front of it.
+int lean_restore(psba_ctx *h) {
+  if (h->cnp != 6) return PSBA_OK;
+  if (h->lean_alt && h->ahead) TRY(launch_linearize(h, false, true, false, false));
+  if (h->lean_cur && (h->linearized || h->lin_is_ahead)) TRY(launch_linearize(h, false, false, false, false));
+  h->lean_cur = h->lean_alt = false;
+  return PSBA_OK;
+}
+
+}  // namespace psba
+}  // extern "C++"
+
+int psba_linearize_ahead(psba_handle h) { return linearize_ahead(h, false); }
+
+int psba_linearize_lean(psba_handle h) {
+  CHECK_H(h);
+  NEED(h, h->linearized, "psba_linearize first");
+  NEED(h, !h->backsub_pending, "a damping try is in flight (psba_backsub_wait first)");
+  NEED(h, lean_prepare(h), "this handle takes the standard form only (psba_lm_ran_lean in include/psba_hip.h lists what the lean form needs)");
+  TRY(launch_linearize(h, false, false, false, true));
+  h->assembled = h->solved = h->backsubbed = false;
+  return PSBA_OK;
+}
+
+int psba_lm_ran_lean(psba_handle h, int *lean) {
+  CHECK_H(h);
+  if (lean) *lean = h->lm_lean ? 1 : 0;
   return PSBA_OK;
 }
 
@@ -966,7 +1041,7 @@ int psba_backsub(psba_handle h, double mu, psba_try_scalars *out) {
 int psba_accept(psba_handle h) {
   CHECK_H(h);
   NEED(h, h->backsubbed, "psba_backsub first");
-  const bool ahead = h->ahead;
+  const bool ahead = h->ahead, lean = h->ahead && h->lean_alt;
   h->cur = 1 - h->cur;
   params_changed(h);  // what was derived belonged to the parameters that were current: both covariances among it
   h->ahead = ahead;  // (what the linearization queued ahead keeps alive is set again below)
@@ -977,6 +1052,8 @@ int psba_accept(psba_handle h) {
     std::swap(h->U, h->U_alt);
     std::swap(h->ga, h->ga_alt);
     std::swap(h->damp_D, h->damp_D_alt);
+    std::swap(h->R, h->R_alt);
+    h->lean_cur = lean;  // (the set that held the old parameters is dead until K1 writes it again)
   }
   h->damp_ok = h->ahead && h->damp_kind == PSBA_DAMPING_MARQUARDT;
   // only a linearization that was computed ahead for THIS proposal spares the next psba_linearize

@@ -17,6 +17,7 @@ constexpr int TILE_OBS = 256;   // observations per point-aligned tile (= thread
 constexpr int TILE_PTS = 128;   // points per tile (bounds the per-point LDS rows)
 constexpr int MAX_GROUPS = 128; // row-aligned groups of the LDS-resident S partition (K2) are tried up to this count, then ranges of blocks
 constexpr int CAM_ACC = 27;     // per-camera accumulators: 21 (sym U) + 6 (g_a)
+constexpr int LEAN_REC = 20;    // doubles of an observation's record in the lean form: A (2 x 6) | B (2 x 3) | e (2); 160 bytes
 constexpr int NSCAL = 104;      // device scalar block (doubles)
 constexpr int SC_NPART = 16;    // K3's four sums arrive in 16 partial sets (same-address atomics serialise)
 
@@ -205,6 +206,13 @@ struct ProblemState {
   // second set of linearization outputs, written by psba_linearize_ahead for the proposed
   // parameters while the host decides about the step; psba_accept swaps the sets
   psba::DevBuf<double> W_alt, PV_alt, U_alt, ga_alt;
+  // the lean form of a linearization (psba_levmar's look-ahead linearizations on an eligible handle):
+  // K1 stores one record (A | B | e) per observation instead of W, U and g_a, and K2 and its reduce form S, e_a and g_a
+  // from the records.  A set written lean holds PV and R; its W and U are stale.  lean_ok: decided at upload (the
+  // record buffers come with the first use, lean_prepare); lean_cur / lean_alt: the form of the current set and of the one queued ahead (written by
+  // launch_linearize, swapped by psba_accept); lm_lean: the last psba_levmar queued lean linearizations
+  psba::DevBuf<double> R, R_alt;  // [nO][LEAN_REC]
+  bool lean_ok = false, lean_cur = false, lean_alt = false, lm_lean = false;
   bool ahead = false;           // the alternate set holds the linearization at the proposed parameters
   bool lin_is_ahead = false;    // the current set was computed ahead: the next psba_linearize is a no-op
   bool scal_side = false;       // side-stream work the main stream has not been ordered behind yet
@@ -436,6 +444,13 @@ namespace psba {
 
 // error helpers (psba_api.cpp)
 int fail(psba_ctx *h, int code, const char *fmt, ...);
+// the lean form of the linearization, for psba_levmar (psba_api.cpp): may this handle take it now; psba_linearize_ahead
+// in either form; and, before psba_levmar returns, a standard linearization in the place of every lean one a later
+// verb could still reach
+bool lean_eligible(psba_ctx *h);
+bool lean_prepare(psba_ctx *h);  // lean_eligible, with the record buffers allocated on first use
+int linearize_ahead(psba_ctx *h, bool lean);
+int lean_restore(psba_ctx *h);
 #define PSBA_HIP(h, call)                                                              \
   do {                                                                                 \
     hipError_t e__ = (call);                                                           \
@@ -453,7 +468,7 @@ struct ProfScope {
 
 // ---- kernel launchers (one per .hip file) ----
 // kernels_linearize.hip
-int launch_linearize(psba_ctx *h, bool dump, bool ahead = false, bool publish = false);
+int launch_linearize(psba_ctx *h, bool dump, bool ahead = false, bool publish = false, bool lean = false);
 int launch_residual(psba_ctx *h, int which, double *ex_out_dev, double *s_out_dev = nullptr);
 int launch_max_diag(psba_ctx *h);
 // kernels_schur.hip

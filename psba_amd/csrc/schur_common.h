@@ -9,6 +9,8 @@ namespace psba {
 
 // slots (6 r + c, c > r) of a diagonal block that carry e_a[0..5]
 static __device__ __constant__ const int EA_SLOT[6] = {1, 2, 3, 4, 5, 8};
+// lean form: six more upper-triangle slots of a diagonal block carry the self-products' g_a terms coeff_g A^T e
+static __device__ __constant__ const int GA_SLOT[6] = {9, 10, 11, 15, 16, 17};
 
 __device__ __forceinline__ int tri(int j) { return j * (j + 1) / 2; }
 
@@ -59,6 +61,10 @@ struct SchurReduceArgs {
   // ring_stride doubles); posblock is the canonical table.  0: the LDS-partition route's slabs
   int ring_copies;
   size_t ring_stride;
+  // lean form: the diagonal blocks arrive with U_j in them (mu I is all that is added); e_a = (sum of the GA slots) +
+  // (sum of the EA slots), two atomic adds per entry into the row K2 zeroed; the GA sums are g_a, written to ga_out for K3
+  int lean;
+  double *ga_out;
 };
 
 // sums the slabs of each group of blocks (fixed order: eight interleaved slab sequences, then
@@ -97,7 +103,7 @@ __device__ __forceinline__ void reduce_first_diag_block(const SchurReduceArgs &p
     if (j >= nC || row >= GB || col >= GB || (j == k && c > r)) continue;
     double acc = sum;
     if (j == k) {
-      acc += p.U[36 * j + rc];
+      if (!p.lean) acc += p.U[36 * j + rc];
       if (r == c) acc += p.mu_add;
     }
     s.D[row][col] = acc;
@@ -122,6 +128,26 @@ __device__ __forceinline__ void reduce_scatter(const SchurReduceArgs &p, long lo
 #pragma unroll
     for (int t = 0; t < 6; t++)
       if (rc == EA_SLOT[t]) ea_slot = t;
+  }
+  if (p.lean) {  // (single rank, never packed)
+    int ga_slot = -1;
+    if (jk >= 0 && j == jb && c > r) {
+#pragma unroll
+      for (int t = 0; t < 6; t++)
+        if (rc == GA_SLOT[t]) ga_slot = t;
+    }
+    if (jk < 0 || (j == jb && c > r && ea_slot < 0 && ga_slot < 0)) return;
+    if (ea_slot >= 0) {
+      atomicAdd(&p.ea[6 * j + ea_slot], sum);
+    } else if (ga_slot >= 0) {
+      p.ga_out[6 * j + ga_slot] = sum;
+      atomicAdd(&p.ea[6 * j + ga_slot], sum);
+    } else {
+      if (j == jb && r == c) sum += p.mu_add;
+      p.S[(size_t)(6 * jb + c) * p.n32 + 6 * j + r] = sum;
+      p.S[(size_t)(6 * j + r) * p.n32 + 6 * jb + c] = sum;
+    }
+    return;
   }
   const bool unused = jk < 0 || (j == jb && c > r && ea_slot < 0);
   if (!unused) {

@@ -22,6 +22,12 @@ struct SchurLdsArgs {
   // kernel can factor that block without gathering it from all the slabs
   double *diag0;           // nullptr: off
   int diag_grp[21], diag_pos[21];
+  // lean form (k_schur_lds<.., LEAN>): the observations' records A | B | e (K1 lean) in the place of W, the coefficients
+  // K1 would have folded into W, U and g_a, and the e_a row, which workgroup 0 zeroes for the reduce's two adds per entry
+  const double *R;
+  double coeff, coeff_g;
+  double *ea;
+  int nA;
 };
 
 }  // namespace psba
