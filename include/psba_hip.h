@@ -129,7 +129,8 @@ int psba_camera_block(psba_handle h, int *cnp); /* 6, 11 or 16 */
  * entries, row and column of S are zero off the diagonal with coeff + mu on it, and e_a is 0.
  * Route (kernels_free.hip, psba_schur_path = 5): camera-major linearization and S assembly on
  * v_mfma_f64_16x16x4_f64, no floating-point atomics -- two runs give bit-identical reduce buffers and logs.  Single
- * rank, dense solver.  The fused verbs, psba_levmar, psba_get_dp, psba_get_gradient and psba_get / set_reduce_buffer
+ * rank; the dense solver, or PSBA_SOLVER_SPARSE (psba_set_solver: the same assembly into a block-sparse S,
+ * psba_schur_path = 6).  The fused verbs, psba_levmar, psba_get_dp, psba_get_gradient and psba_get / set_reduce_buffer
  * work; covariances, robust losses, psba_set_fixed, PSBA_SOLVER_PCG, rank layouts, the sba_func.h mirror, the
  * trust-region operators, psba_solve and psba_obs_sq_residuals return PSBA_E_STATE with a text that names
  * PSBA_CAMERA_FREE_KD.  The reference has no arithmetic for this: PARITY UNPINNED -- checked against a numpy twin,
@@ -496,7 +497,8 @@ int psba_free_covariance_times(psba_handle h, double ms3[3]);
  * fp64 atomics straight into S (the
  * first-generation kernel, kept for cross-checks: PSBA_SCHUR_ATOMIC=1), 3 = the ring route (opt-in
  * experiment, PSBA_SCHUR_RING=1), 4 = block-sparse S (PSBA_SOLVER_PCG), 5 = the free-intrinsics route (blocks of 11
- * and 16: products sorted by block, one MFMA per product).  The reference has one
+ * and 16: products sorted by block, one MFMA per product), 6 = the same assembly into a block-sparse S of those
+ * blocks (PSBA_SOLVER_SPARSE).  The reference has one
  * route for every size (CL_files/compute_S.cl:6-78). */
 int psba_schur_path(psba_handle h, int *path);
 
@@ -818,13 +820,27 @@ int psba_algorithmic_bytes(psba_handle h, int kernel, double *bytes);
  * handle), ORs the flags, and hands them to psba_set_sparse_pattern before psba_upload_problem; between
  * psba_schur_assemble and psba_schur_solve it then sums psba_get_sparse_S over the ranks and returns the
  * sums with psba_set_sparse_S (the conjugate gradients themselves run replicated on every rank).
- * psba_set_solver: before psba_upload_problem; tol <= 0 / max_iter <= 0 keep 1e-10 / 500. */
+ * psba_set_solver: before psba_upload_problem; tol <= 0 / max_iter <= 0 keep 1e-10 / 500.
+ * PSBA_SOLVER_SPARSE is the block-sparse mode for whatever camera block the handle has.  With six-parameter blocks
+ * it is PSBA_SOLVER_PCG itself (same code path, same bits).  Under PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD, where
+ * PSBA_SOLVER_PCG stays refused at the upload, it selects the route of kernels_free_pcg.hip (psba_schur_path = 6):
+ * the blocks are cnp x cnp (val[cnp cnp blocks] row-major, k <= j, every diagonal block present, also that of a
+ * camera without observations), the assembly writes them with the fixed-order MFMA kernels, and the conjugate
+ * gradients sum every inner product from per-workgroup partial sums in a fixed order -- no floating-point atomics, so
+ * two solves of the same blocks give the same bits.  Nothing of size nA^2 is allocated.  psba_pcg_info,
+ * psba_get_sparse_S, psba_set_sparse_S, psba_sparse_S_times, psba_schur_solve and psba_levmar work as under
+ * PSBA_SOLVER_PCG; the intrinsics mask, held poses and points, observation weighting, priors and Marquardt damping
+ * compose with it.  psba_set_intrinsics_groups, psba_free_covariance_compute and its getters, psba_get / set_reduce_buffer,
+ * psba_SPDinv_matVec, psba_chol_dist_* and psba_get_cholmod_factor return PSBA_E_STATE with a text that names
+ * PSBA_SOLVER_SPARSE, before any copy or launch. */
 #define PSBA_SOLVER_DENSE 0
 #define PSBA_SOLVER_PCG 1
+#define PSBA_SOLVER_SPARSE 2   /* block-sparse S of cnp x cnp blocks + block-Jacobi PCG, whatever the camera block */
 int psba_set_solver(psba_handle h, int solver, double tol, int max_iter);
 /* iterations and ||r|| / ||e_a|| of the last solve; blocks stored / blocks of the dense lower triangle */
 int psba_pcg_info(psba_handle h, int *iters, double *relres, long long *blocks, long long *dense_blocks);
-/* the assembled blocks: jk[2 blocks] = (j, k), k <= j; val[36 blocks] row-major; ea[nA]; any pointer may be NULL */
+/* the assembled blocks: jk[2 blocks] = (j, k), k <= j; val[cnp cnp blocks] row-major (36 doubles per block
+ * with six-parameter blocks, 121 / 256 under PSBA_SOLVER_SPARSE on blocks of 11 / 16); ea[nA]; any pointer may be NULL */
 int psba_get_sparse_S(psba_handle h, int *jk, double *val, double *ea);
 int psba_set_sparse_S(psba_handle h, const double *val, const double *ea);
 /* ---- mirror verb: y[nA] = S x[nA] on the stored blocks, formed by the kernel that forms the products of the solve
@@ -920,6 +936,13 @@ psba_blockprod_plan_t psba_blockprod_plan_create(int nCams, int n3Dpts, int n2Dp
                                                  int seg_len);
 int psba_blockprod_plan_info(psba_blockprod_plan_t p, long long info[4]);
 int psba_blockprod_plan_copy(psba_blockprod_plan_t p, int *blocks, int *segs, int *prods);
+/* The block list and row walk PSBA_SOLVER_SPARSE derives from the plan on these camera blocks: the plan's blocks plus a
+ * diagonal block for every camera without a product, ascending by (j, k).  info[0..2] = stored blocks, diagonal blocks
+ * added, row entries.  jk[stored][2]; diag_slot[nCams]; rowptr[nCams + 1]; rowent[entries][2] = (slot, other camera |
+ * how << 28) with how 0 = as stored, 1 = transposed, 2 = the diagonal block (read through its lower triangle).  Any
+ * pointer may be NULL. */
+int psba_blockprod_plan_rows_info(psba_blockprod_plan_t p, long long info[3]);
+int psba_blockprod_plan_rows(psba_blockprod_plan_t p, int *jk, int *diag_slot, int *rowptr, int *rowent);
 void psba_blockprod_plan_destroy(psba_blockprod_plan_t p);
 
 #ifdef PSBA_BUILD_EXPERIMENTS

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["psba_api.cpp", "problem_options.cpp", "covariance.cpp", "schur_plan.cpp", "lm_loop.cpp", "tr_loop.cpp", "sba_io.cpp", "kernels_linearize.hip",
            "kernels_tr.hip",
-           "kernels_schur.hip", "kernels_free.hip", "blockprod_plan.cpp", "kernels_chol.hip", "kernels_pcg.hip", "kernels_chol_graph.hip", "kernels_backsub.hip",
+           "kernels_schur.hip", "kernels_free.hip", "kernels_free_pcg.hip", "blockprod_plan.cpp", "kernels_chol.hip", "kernels_pcg.hip", "kernels_chol_graph.hip", "kernels_backsub.hip",
            "kernels_cov.hip"]
 # PSBA_BUILD_EXPERIMENTS=1: also the rejected experiments (round 3's K2 ring route) and their test hooks
 EXPERIMENTS = bool(os.environ.get("PSBA_BUILD_EXPERIMENTS"))

@@ -18,6 +18,7 @@ PSBA_OK, PSBA_NOT_SPD, PSBA_SINGULAR_V = 0, 1, 2
 PARAMS_CUR, PARAMS_NEW = 0, 1
 LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY, LOSS_SOFT_L1 = 0, 1, 2, 3
 CAMERA_FIXED_K, CAMERA_FREE_K, CAMERA_FREE_KD = 0, 1, 2
+SOLVER_DENSE, SOLVER_PCG, SOLVER_SPARSE = 0, 1, 2
 INTRINSICS_BAL = (1, 0, 0, 0, 0, 1, 1, 0, 0, 0)  # the free intrinsics of Bundle Adjustment in the Large: f, k1, k2
 DAMPING_IDENTITY, DAMPING_MARQUARDT = 0, 1
 ITER_TURN_TO_LM, ITER_TURN_TO_TR, ITER_CONTINUE, ITER_ERR = 1, 2, 3, 4
@@ -200,6 +201,8 @@ SIGNATURES = [
     ("psba_blockprod_plan_create", C.c_void_p, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_int]),
     ("psba_blockprod_plan_info", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
     ("psba_blockprod_plan_copy", C.c_int, [C.c_void_p, _ip, _ip, _ip]),
+    ("psba_blockprod_plan_rows_info", C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    ("psba_blockprod_plan_rows", C.c_int, [C.c_void_p, _ip, _ip, _ip, _ip]),
     ("psba_blockprod_plan_destroy", None, [C.c_void_p]),
     ("psba_covariance_compute", C.c_int, [_h, C.c_double, C.c_double, C.c_int]),
     ("psba_get_camera_covariance", C.c_int, [_h, C.c_int, _ip, _dp]),
@@ -389,7 +392,9 @@ def owner_plan(n_cams, n_pts, iidx, jidx, pattern=None):
 
 def blockprod_plan(n_cams, n_pts, iidx, jidx, seg_len):
     """The S-assembly schedule of the 16-parameter camera block (host only, no device): dict with blocks [nb, 2] =
-    (j, k), segs [ns, 3] = (block, first, end product), prods [np, 2] = observations (a, b), tiles."""
+    (j, k), segs [ns, 3] = (block, first, end product), prods [np, 2] = observations (a, b), tiles; and the stored blocks and
+    row walk PSBA_SOLVER_SPARSE derives from it: jk [stored, 2], diag_added, diag_slot [nC], rowptr [nC + 1], rowent
+    [entries, 2] = (slot, other camera | how << 28)."""
     iidx = _c(iidx, np.int32)
     jidx = _c(jidx, np.int32)
     p = lib.psba_blockprod_plan_create(int(n_cams), int(n_pts), int(iidx.size), _i(iidx), _i(jidx), int(seg_len))
@@ -403,9 +408,17 @@ def blockprod_plan(n_cams, n_pts, iidx, jidx, seg_len):
         segs = np.zeros((ns, 3), dtype=np.int32)
         prods = np.zeros((npr, 2), dtype=np.int32)
         lib.psba_blockprod_plan_copy(p, _i(blocks), _i(segs), _i(prods))
+        rinfo = (C.c_longlong * 3)()
+        lib.psba_blockprod_plan_rows_info(p, rinfo)
+        jk = np.zeros((int(rinfo[0]), 2), dtype=np.int32)
+        diag_slot = np.zeros(int(n_cams), dtype=np.int32)
+        rowptr = np.zeros(int(n_cams) + 1, dtype=np.int32)
+        rowent = np.zeros((int(rinfo[2]), 2), dtype=np.int32)
+        lib.psba_blockprod_plan_rows(p, _i(jk), _i(diag_slot), _i(rowptr), _i(rowent))
     finally:
         lib.psba_blockprod_plan_destroy(p)
-    return dict(blocks=blocks, segs=segs, prods=prods, tiles=tiles)
+    return dict(blocks=blocks, segs=segs, prods=prods, tiles=tiles, jk=jk, diag_added=int(rinfo[1]), diag_slot=diag_slot,
+                rowptr=rowptr, rowent=rowent)
 
 
 def chol_dist_exchange_plan(n32, NB, nranks, JE):
@@ -871,7 +884,8 @@ class Psba:
 
     # ---- block-sparse S + PCG ----
     def set_solver(self, solver, tol=0.0, max_iter=0):
-        """solver: 0 dense Cholesky, 1 block-sparse S + preconditioned CG (before upload_problem)."""
+        """solver: 0 dense Cholesky, 1 block-sparse S + preconditioned CG (six-parameter blocks), SOLVER_SPARSE = 2 the
+        block-sparse mode of whatever camera block the handle has (before upload_problem)."""
         self._ck(lib.psba_set_solver(self._h, int(solver), float(tol), int(max_iter)))
 
     def pcg_info(self):
@@ -882,8 +896,9 @@ class Psba:
     def get_sparse_S(self):
         nb = self.pcg_info()[2]
         jk = np.empty((nb, 2), dtype=np.int32)
-        val = np.empty((nb, 6, 6))
-        ea = np.empty(6 * self.nC)
+        cnp = self.camera_block()
+        val = np.empty((nb, cnp, cnp))
+        ea = np.empty(cnp * self.nC)
         self._ck(lib.psba_get_sparse_S(self._h, _i(jk), _d(val), _d(ea)))
         return jk, val, ea
 
@@ -895,9 +910,10 @@ class Psba:
     def sparse_S_times(self, x):
         """psba_sparse_S_times: y = S x [nA] on the stored blocks, by the solve's own product kernel."""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-        if x.size != 6 * self.nC:
-            raise PsbaError(-1, f"sparse_S_times: {x.size} entries for {6 * self.nC} unknowns")
-        y = np.empty(6 * self.nC)
+        n = self.camera_block() * self.nC
+        if x.size != n:
+            raise PsbaError(-1, f"sparse_S_times: {x.size} entries for {n} unknowns")
+        y = np.empty(n)
         self._ck(lib.psba_sparse_S_times(self._h, _d(x), _d(y)))
         return y
 

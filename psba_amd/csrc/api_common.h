@@ -31,9 +31,14 @@
 #define SIX_ONLY "six-parameter camera blocks only (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD: the fused verbs and psba_levmar)"
 #define NEED_SIX(h) NEED(h, (h)->cnp == 6, SIX_ONLY)
 // the verbs that read or write the dense reduce buffer or the Cholesky chain's factor: under PSBA_SOLVER_PCG neither
-// exists (one double each is allocated), so they refuse on the host before any copy or launch
-#define NEED_DENSE(h) \
-  NEED(h, (h)->solver != PSBA_SOLVER_PCG, "no dense S and no Cholesky chain with PSBA_SOLVER_PCG (psba_schur_solve, psba_get_sparse_S)")
+// exists (one double each is allocated), so they refuse on the host before any copy or launch.  FREE_SPARSE: the handle
+// runs PSBA_SOLVER_SPARSE on camera blocks of 11 / 16 (kernels_free_pcg.hip), where the text names that solver
+#define FREE_SPARSE(h) ((h)->cnp != 6 && (h)->solver == PSBA_SOLVER_PCG && (h)->sparse_any_block)
+#define NEED_DENSE(h)                                                                                                   \
+  do {                                                                                                                  \
+    NEED(h, !FREE_SPARSE(h), "no dense S and no Cholesky chain with PSBA_SOLVER_SPARSE (psba_schur_solve, psba_get_sparse_S)"); \
+    NEED(h, (h)->solver != PSBA_SOLVER_PCG, "no dense S and no Cholesky chain with PSBA_SOLVER_PCG (psba_schur_solve, psba_get_sparse_S)"); \
+  } while (0)
 #define RCCL(h, call)                                                                   \
   do {                                                                                  \
     ncclResult_t r__ = (call);                                                          \

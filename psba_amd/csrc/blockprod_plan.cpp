@@ -49,10 +49,52 @@ int build_blockprod_plan(int nCams, int nObs, const int *iidx, const int *jidx, 
   return PSBA_OK;
 }
 
+// the stored blocks of the block-sparse S: a merge of the plan's blocks (ascending) with the diagonal of every camera;
+// then the row walk as upload_bsr_rows builds it for the blocks of 6 -- a block serves its row as stored and its
+// column's row transposed, a diagonal block through its lower triangle; a row's entries ascend by slot
+void build_block_rows(int nCams, const BlockProdPlanHost &plan, BlockRowsHost &out) {
+  out = BlockRowsHost();
+  out.diag_slot.assign((size_t)nCams, -1);
+  out.added.assign((size_t)nCams, 0);
+  out.slot_of.resize(plan.blocks.size());
+  size_t b = 0;
+  for (int j = 0; j < nCams; j++) {
+    for (; b < plan.blocks.size() && plan.blocks[b].x == j; b++) {  // row j of the lower triangle ends with (j, j)
+      if (plan.blocks[b].y == j) out.diag_slot[(size_t)j] = (int)out.jk.size();
+      out.slot_of[b] = (int)out.jk.size();
+      out.jk.push_back(plan.blocks[b]);
+    }
+    if (out.diag_slot[(size_t)j] < 0) {
+      out.diag_slot[(size_t)j] = (int)out.jk.size();
+      out.added[(size_t)j] = 1;
+      out.nadded++;
+      out.jk.push_back(make_int2(j, j));
+    }
+  }
+  out.rowptr.assign((size_t)nCams + 1, 0);
+  for (const int2 &e : out.jk) {
+    out.rowptr[(size_t)e.x + 1]++;
+    if (e.x != e.y) out.rowptr[(size_t)e.y + 1]++;
+  }
+  for (int j = 0; j < nCams; j++) out.rowptr[(size_t)j + 1] += out.rowptr[(size_t)j];
+  out.rowent.resize((size_t)out.rowptr[(size_t)nCams]);
+  std::vector<int> at(out.rowptr.begin(), out.rowptr.end() - 1);
+  for (size_t sl = 0; sl < out.jk.size(); sl++) {
+    const int2 e = out.jk[sl];
+    if (e.x == e.y) {
+      out.rowent[(size_t)at[(size_t)e.x]++] = make_int2((int)sl, e.x | (2 << 28));
+    } else {
+      out.rowent[(size_t)at[(size_t)e.x]++] = make_int2((int)sl, e.y);
+      out.rowent[(size_t)at[(size_t)e.y]++] = make_int2((int)sl, e.x | (1 << 28));
+    }
+  }
+}
+
 }  // namespace psba
 
 struct psba_blockprod_plan {
   psba::BlockProdPlanHost plan;
+  psba::BlockRowsHost rows;
 };
 
 extern "C" {
@@ -74,7 +116,34 @@ psba_blockprod_plan_t psba_blockprod_plan_create(int nCams, int n3Dpts, int n2Dp
     delete p;
     return nullptr;
   }
+  psba::build_block_rows(nCams, p->plan, p->rows);
   return p;
+}
+
+int psba_blockprod_plan_rows_info(psba_blockprod_plan_t p, long long info[3]) {
+  if (!p || !info) return PSBA_E_INVALID;
+  info[0] = (long long)p->rows.jk.size();
+  info[1] = p->rows.nadded;
+  info[2] = (long long)p->rows.rowent.size();
+  return PSBA_OK;
+}
+
+int psba_blockprod_plan_rows(psba_blockprod_plan_t p, int *jk, int *diag_slot, int *rowptr, int *rowent) {
+  if (!p) return PSBA_E_INVALID;
+  const psba::BlockRowsHost &r = p->rows;
+  if (jk)
+    for (size_t b = 0; b < r.jk.size(); b++) {
+      jk[2 * b] = r.jk[b].x;
+      jk[2 * b + 1] = r.jk[b].y;
+    }
+  if (diag_slot) std::copy(r.diag_slot.begin(), r.diag_slot.end(), diag_slot);
+  if (rowptr) std::copy(r.rowptr.begin(), r.rowptr.end(), rowptr);
+  if (rowent)
+    for (size_t e = 0; e < r.rowent.size(); e++) {
+      rowent[2 * e] = r.rowent[e].x;
+      rowent[2 * e + 1] = r.rowent[e].y;
+    }
+  return PSBA_OK;
 }
 
 int psba_blockprod_plan_info(psba_blockprod_plan_t p, long long info[4]) {

@@ -32,6 +32,7 @@ const char *const COMPUTE_VERB[2] = {"psba_covariance_compute", "psba_free_covar
 
 // behind both compute verbs, which have checked the upload, the try in flight and the camera block
 int covariance_compute(psba_ctx *h, const char *verb, double mu, double scale, int reassemble) {
+  NEED_V(h, verb, !FREE_SPARSE(h), "the dense solver only: PSBA_SOLVER_SPARSE assembles no dense S to invert");
   NEED_V(h, verb, h->solver != PSBA_SOLVER_PCG, "the dense solver only: PSBA_SOLVER_PCG assembles no dense S to invert");
   NEED_V(h, verb, !h->comm && h->nranks == 1, "single rank only: not under a rank layout or a communicator");
   if (!(std::isfinite(mu) && mu >= 0.0)) return fail(h, PSBA_E_INVALID, "%s: mu must be finite and >= 0 (got %.17g)", verb, mu);
@@ -77,6 +78,7 @@ int need_cov(psba_ctx *h, const char *verb, Family f, bool points = false) {
   NEED_V(h, verb, (h->cnp == 6) == (f == SIX),
          f == SIX ? "six-parameter camera blocks only (free intrinsics: the psba_get_free_* getters)"
                   : "free-intrinsics camera blocks only (six-parameter blocks: psba_get_camera_covariance and its kin)");
+  NEED_V(h, verb, !FREE_SPARSE(h), "the dense solver only: PSBA_SOLVER_SPARSE assembles no dense S to invert");
   if (!h->cov_ok)
     return fail(h, PSBA_E_STATE, "%s: %s first (whatever moves the parameters or the model invalidates the covariance)", verb, COMPUTE_VERB[f]);
   if (points && !h->cov_pts_ok)

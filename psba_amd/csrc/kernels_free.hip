@@ -488,8 +488,10 @@ __global__ __launch_bounds__(64) void k_free_Y(const double *W, const double *PV
 }
 
 // S assembly: one wave per segment of a block's product list, one MFMA per product (A = Y_a, B = W_b^T, K = 3 of 4).
-// The only segment of a block stores -sum straight into S; the others store partial tiles (CNP x CNP each)
-template <class T>
+// The only segment of a block stores -sum straight into S; the others store partial tiles (CNP x CNP each).
+// LIST (PSBA_SOLVER_SPARSE): S is the list of stored blocks, blocks[b].x the slot of the plan's block b, and the
+// destination is S + CNP^2 slot with row stride CNP; the dense instantiation is the code as it was
+template <class T, bool LIST = false>
 __global__ __launch_bounds__(256) void k_free_schur(const double *Y, const double *W, const int2 *prods, const int4 *segs,
                                                     const int2 *blocks, int nsegs, double *S, int ld, double *tiles) {
   constexpr int CNP = T::CNP, WB = 3 * CNP;
@@ -522,10 +524,11 @@ __global__ __launch_bounds__(256) void k_free_schur(const double *Y, const doubl
   }
   if (s.w < 0) {
     const int2 b = blocks[s.x];
-    double *dst = S + (size_t)(CNP * b.x) * ld + CNP * b.y;
+    double *dst = LIST ? S + (size_t)(CNP * CNP) * b.x : S + (size_t)(CNP * b.x) * ld + CNP * b.y;
+    const size_t rs = LIST ? (size_t)CNP : (size_t)ld;
 #pragma unroll
     for (int r = 0; r < 4; r++)
-      if (live && (CNP == 16 || k + 4 * r < CNP)) dst[(size_t)(k + 4 * r) * ld + col] = -acc[r];
+      if (live && (CNP == 16 || k + 4 * r < CNP)) dst[(size_t)(k + 4 * r) * rs + col] = -acc[r];
   } else {
     double *dst = tiles + CNP * CNP * (size_t)s.w;
 #pragma unroll
@@ -534,8 +537,8 @@ __global__ __launch_bounds__(256) void k_free_schur(const double *Y, const doubl
   }
 }
 
-// the blocks with several segments: their partial tiles in segment order
-template <class T>
+// the blocks with several segments: their partial tiles in segment order (LIST: multi[].x is the block's slot)
+template <class T, bool LIST = false>
 __global__ __launch_bounds__(256) void k_free_combine(const int4 *multi, const double *tiles, double *S, int ld) {
   constexpr int CNP = T::CNP;
   const int4 m = multi[blockIdx.x];
@@ -543,7 +546,10 @@ __global__ __launch_bounds__(256) void k_free_combine(const int4 *multi, const d
   if (CNP < 16 && e >= CNP * CNP) return;
   double s = 0.0;
   for (int t = 0; t < m.w; t++) s += tiles[CNP * CNP * (size_t)(m.z + t) + e];
-  S[(size_t)(CNP * m.x + e / CNP) * ld + CNP * m.y + e % CNP] = -s;
+  if (LIST)
+    S[(size_t)(CNP * CNP) * m.x + e] = -s;
+  else
+    S[(size_t)(CNP * m.x + e / CNP) * ld + CNP * m.y + e % CNP] = -s;
 }
 
 // S += blockdiag(U) + mu I (mu D with D set) on the lower block triangle, mirrored to the upper; e_a = g_a - the
@@ -1012,6 +1018,19 @@ static int schur_free(psba_ctx *h, double mu) {
   const FreeDamp dm = free_damp(h);
   h->try_id++;  // (the status words are generation stamps, as in launch_schur)
   h->diag_done = false;
+  if (h->solver == PSBA_SOLVER_PCG) {  // PSBA_SOLVER_SPARSE: the same two kernels into the list of stored blocks
+    ProfScope ps(h, PSBA_K_SCHUR);
+    hipLaunchKernelGGL(k_free_Y<T>, dim3(h->nCamUnits), dim3(64), 0, h->stream, h->W, h->PV, h->iidx, h->cam_obs, h->cam_units,
+                       h->free_Y, h->free_eapart, mu, dm, h->status, h->try_id);
+    hipLaunchKernelGGL((k_free_schur<T, true>), dim3((unsigned)((h->free_nsegs + 3) / 4)), dim3(256), 0, h->stream, h->free_Y,
+                       h->W, h->free_prods, h->free_segs, h->free_blocks, h->free_nsegs, h->bs_val, T::CNP, h->free_tiles);
+    if (h->free_nmulti)
+      hipLaunchKernelGGL((k_free_combine<T, true>), dim3(h->free_nmulti), dim3(256), 0, h->stream, h->free_multi,
+                         h->free_tiles, h->bs_val, T::CNP);
+    PSBA_HIP(h, hipGetLastError());
+    h->packed_pending = false;
+    return launch_fbsr_finalize(h, mu, dm.D);
+  }
   double *S = h->red, *ea = h->red + (size_t)h->n32 * h->n32;
   PSBA_HIP(h, hipMemsetAsync(h->red, 0, sizeof(double) * (size_t)(h->n32 + 1) * h->n32, h->stream));
   {

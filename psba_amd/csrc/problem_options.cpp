@@ -279,6 +279,7 @@ int psba_intrinsics_mask(psba_handle h, unsigned char *out10) {
 int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam) {
   CHECK_H(h);
   TRY(settable(h, __func__, FREE_KD));
+  NEED(h, !FREE_SPARSE(h), "not under PSBA_SOLVER_SPARSE: the fold sums rows and columns of a dense S");
   const int nC = h->d.nC;
   // the representative of a label is the first camera that carries it
   std::vector<int> rep((size_t)nC), order((size_t)nC);

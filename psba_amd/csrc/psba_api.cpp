@@ -172,7 +172,7 @@ int psba_destroy(psba_handle h) {
 int psba_schur_path(psba_handle h, int *path) {
   CHECK_H(h);
   NEED(h, h->uploaded, "no problem uploaded");
-  if (path) *path = h->cnp != 6 ? 5 : h->solver == PSBA_SOLVER_PCG ? 4 : getenv("PSBA_SCHUR_ATOMIC") ? 2 : h->ring_nWg > 0 ? 3 : h->nGroups > 0 ? 0 : 1;
+  if (path) *path = FREE_SPARSE(h) ? 6 : h->cnp != 6 ? 5 : h->solver == PSBA_SOLVER_PCG ? 4 : getenv("PSBA_SCHUR_ATOMIC") ? 2 : h->ring_nWg > 0 ? 3 : h->nGroups > 0 ? 0 : 1;
   return PSBA_OK;
 }
 
@@ -220,10 +220,12 @@ static int build_point_csr(psba_ctx *h, Upload &u) {
   if (u.nC <= 0 || u.nP <= 0 || u.nO <= 0 || !u.Kparas || !u.impts || !u.initrot || !u.camsEx || !u.pts3D || !u.iidx ||
       !u.jidx)
     return fail(h, PSBA_E_INVALID, "psba_upload_problem: null pointer or non-positive size");
-  if (h->cnp == KD_CNP && (h->solver == PSBA_SOLVER_PCG || h->nranks > 1 || h->comm))
-    return fail(h, PSBA_E_STATE, "PSBA_CAMERA_FREE_KD: dense solver, single rank only");
-  if (h->cnp != 6 && (h->solver == PSBA_SOLVER_PCG || h->nranks > 1 || h->comm))
-    return fail(h, PSBA_E_INVALID, "free intrinsics: dense solver, single rank only");
+  // (PSBA_SOLVER_PCG is the mode of the six-parameter blocks; PSBA_SOLVER_SPARSE is stored as it with the flag set)
+  const bool pcg6 = h->solver == PSBA_SOLVER_PCG && !h->sparse_any_block;
+  if (h->cnp == KD_CNP && (pcg6 || h->nranks > 1 || h->comm))
+    return fail(h, PSBA_E_STATE, "PSBA_CAMERA_FREE_KD: dense solver or PSBA_SOLVER_SPARSE, single rank only");
+  if (h->cnp != 6 && (pcg6 || h->nranks > 1 || h->comm))
+    return fail(h, PSBA_E_INVALID, "free intrinsics: dense solver or PSBA_SOLVER_SPARSE, single rank only");
   u.ptr.assign((size_t)u.nP + 1, 0);
   for (int a = 0; a < u.nO; a++) {
     const int i = u.iidx[a], j = u.jidx[a];
@@ -561,8 +563,60 @@ static int plan_schur_blockprod(psba_ctx *h, const Upload &u) {
   return PSBA_OK;
 }
 
+// PSBA_SOLVER_SPARSE on these blocks: the same plan, with the tables of the two assembly kernels carrying the slot of the
+// stored block in place of (j, k); the stored list, its row walk and the buffers of the conjugate gradients
+// (kernels_free_pcg.hip).  Nothing here is of size nA^2
+static int plan_schur_blockprod_sparse(psba_ctx *h, const Upload &u) {
+  const Dims &d = h->d;
+  const size_t c2 = (size_t)h->cnp * h->cnp;
+  int seg = KD_SEG_DEFAULT;
+  if (const char *e = getenv("PSBA_FKD_SEG"))
+    if (atoi(e) > 0) seg = atoi(e);
+  BlockProdPlanHost plan;
+  if (build_blockprod_plan(u.nC, u.nO, u.iidx, u.jidx, u.ptr.data(), seg, plan) != PSBA_OK)
+    return fail(h, PSBA_E_INVALID, "%s: more than 2^31 products Y_a W_b^T", h->cnp == KD_CNP ? "PSBA_CAMERA_FREE_KD" : "PSBA_CAMERA_FREE_K");
+  BlockRowsHost rows;
+  build_block_rows(u.nC, plan, rows);
+  std::vector<int2> slots(plan.blocks.size());
+  for (size_t b = 0; b < plan.blocks.size(); b++) slots[b] = make_int2(rows.slot_of[b], 0);
+  std::vector<int4> multi(plan.multi);
+  {
+    size_t b = 0;  // (multi follows the order of blocks)
+    for (int4 &m : multi) {
+      while (plan.blocks[b].x != m.x || plan.blocks[b].y != m.y) b++;
+      m.x = rows.slot_of[b];
+      m.y = 0;
+    }
+  }
+  TRY(upload(h, h->free_blocks, slots));
+  TRY(upload(h, h->free_segs, plan.segs));
+  TRY(upload(h, h->free_prods, plan.prods));
+  if (!multi.empty()) TRY(upload(h, h->free_multi, multi));
+  TRY(h->free_tiles.alloc(h, c2 * (plan.ntiles ? plan.ntiles : 1)));
+  h->free_nsegs = (int)plan.segs.size();
+  h->free_nmulti = (int)multi.size();
+  h->bs_nblk = (long long)rows.jk.size();
+  TRY(h->bs_val.alloc(h, c2 * rows.jk.size() + (size_t)d.nA));
+  h->bs_ea = h->bs_val + c2 * rows.jk.size();
+  TRY(upload(h, h->bs_jk, rows.jk));
+  std::vector<int> diag(rows.diag_slot);
+  for (int j = 0; j < u.nC; j++)
+    if (rows.added[(size_t)j]) diag[(size_t)j] |= FBSR_ADDED;
+  TRY(upload(h, h->bs_diag, diag));
+  TRY(upload(h, h->bs_rowptr, rows.rowptr));
+  TRY(upload(h, h->bs_rowent, rows.rowent));
+  TRY(h->pcg_vec.alloc(h, (size_t)5 * d.nA));  // r, z, p, q, and r's second buffer
+  TRY(h->pcg_minv.alloc(h, c2 * d.nC));
+  TRY(h->pcg_scal.alloc(h, (size_t)(16 + 13 * FPCG_CAP)));  // scalars + the partial sums (kernels_free_pcg.hip)
+  if (!h->pcg_host) TRY(h->pcg_host.alloc(h, 16));
+  if (getenv("PSBA_SCHUR_PLAN_INFO"))
+    fprintf(stderr, "[psba] block-sparse S, blocks of %d: %lld of %lld blocks of the lower block triangle, %lld diagonal blocks added\n",
+            h->cnp, h->bs_nblk, (long long)u.nC * (u.nC + 1) / 2, rows.nadded);
+  return PSBA_OK;
+}
+
 static int plan_schur(psba_ctx *h, const Upload &u) {
-  if (h->solver == PSBA_SOLVER_PCG) return plan_schur_sparse(h, u);
+  if (h->solver == PSBA_SOLVER_PCG) return h->cnp != 6 ? plan_schur_blockprod_sparse(h, u) : plan_schur_sparse(h, u);
 #ifdef PSBA_BUILD_EXPERIMENTS
   TRY(plan_schur_ring(h, u));
   if (h->ring_nWg) return PSBA_OK;
@@ -834,7 +888,7 @@ int psba_schur_solve(psba_handle h) {
   if (h->packed_pending) TRY(allreduce_schur(h));  // psba_schur_reduce was skipped
   h->cholmod_factor = false;
   if (h->solver == PSBA_SOLVER_PCG) {
-    TRY(launch_pcg_solve(h));
+    TRY(h->cnp != 6 ? launch_fpcg_solve(h) : launch_pcg_solve(h));
     h->assembled = false;
     h->solved = true;
     return h->pcg_exhausted ? PSBA_PCG_MAXIT : PSBA_OK;
@@ -1161,9 +1215,16 @@ int psba_jmul_dots(psba_handle h, const double *x1, const double *x2, double dot
 
 int psba_set_solver(psba_handle h, int solver, double tol, int max_iter) {
   CHECK_H(h);
-  if (solver != PSBA_SOLVER_DENSE && solver != PSBA_SOLVER_PCG) return fail(h, PSBA_E_INVALID, "unknown solver %d", solver);
-  NEED(h, !h->uploaded || solver == h->solver, "psba_set_solver before psba_upload_problem (the buffers depend on it)");
+  if (solver != PSBA_SOLVER_DENSE && solver != PSBA_SOLVER_PCG && solver != PSBA_SOLVER_SPARSE)
+    return fail(h, PSBA_E_INVALID, "unknown solver %d", solver);
+  // PSBA_SOLVER_SPARSE is PSBA_SOLVER_PCG with the flag: with six-parameter blocks nothing else reads the flag, on
+  // blocks of 11 / 16 the upload and the dispatch do
+  const bool any_block = solver == PSBA_SOLVER_SPARSE;
+  if (any_block) solver = PSBA_SOLVER_PCG;
+  NEED(h, !h->uploaded || (solver == h->solver && (h->cnp == 6 || any_block == h->sparse_any_block)),
+       "psba_set_solver before psba_upload_problem (the buffers depend on it)");
   h->solver = solver;
+  if (!h->uploaded) h->sparse_any_block = any_block;
   if (tol > 0) h->pcg_tol = tol;
   if (max_iter > 0) h->pcg_maxit = max_iter;
   return PSBA_OK;
@@ -1185,7 +1246,7 @@ int psba_get_sparse_S(psba_handle h, int *jk, double *val, double *ea) {
   NEED(h, h->assembled && h->solver == PSBA_SOLVER_PCG, "psba_schur_assemble with PSBA_SOLVER_PCG first");
   NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");
   if (jk) TRY(d2h(h, jk, h->bs_jk, sizeof(int2) * (size_t)h->bs_nblk));
-  if (val) TRY(d2h(h, val, h->bs_val, sizeof(double) * 36 * (size_t)h->bs_nblk));
+  if (val) TRY(d2h(h, val, h->bs_val, sizeof(double) * (size_t)(h->cnp * h->cnp) * (size_t)h->bs_nblk));
   if (ea) TRY(d2h(h, ea, h->bs_ea, sizeof(double) * (size_t)h->d.nA));
   return PSBA_OK;
 }
@@ -1195,7 +1256,7 @@ int psba_set_sparse_S(psba_handle h, const double *val, const double *ea) {
   CHECK_H(h);
   NEED(h, h->assembled && h->solver == PSBA_SOLVER_PCG, "psba_schur_assemble with PSBA_SOLVER_PCG first");
   NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");
-  if (val) PSBA_HIP(h, hipMemcpyAsync(h->bs_val, val, sizeof(double) * 36 * (size_t)h->bs_nblk, hipMemcpyHostToDevice, h->stream));
+  if (val) PSBA_HIP(h, hipMemcpyAsync(h->bs_val, val, sizeof(double) * (size_t)(h->cnp * h->cnp) * (size_t)h->bs_nblk, hipMemcpyHostToDevice, h->stream));
   if (ea) PSBA_HIP(h, hipMemcpyAsync(h->bs_ea, ea, sizeof(double) * (size_t)h->d.nA, hipMemcpyHostToDevice, h->stream));
   PSBA_HIP(h, hipStreamSynchronize(h->stream));
   h->solved = h->backsubbed = false;
@@ -1209,7 +1270,7 @@ int psba_sparse_S_times(psba_handle h, const double *x, double *y) {
   NEED(h, h->assembled && h->solver == PSBA_SOLVER_PCG, "psba_schur_assemble with PSBA_SOLVER_PCG first");
   NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");
   if (!x || !y) return fail(h, PSBA_E_INVALID, "%s: null pointer", __func__);
-  return launch_bsr_times(h, x, y);
+  return h->cnp != 6 ? launch_fbsr_times(h, x, y) : launch_bsr_times(h, x, y);
 }
 
 // host only: which blocks of the lower block triangle a (shard of a) problem produces
@@ -1350,6 +1411,7 @@ int psba_cholmod_lambda(psba_handle h, int reassemble, double *lambda, double *i
 int psba_get_cholmod_factor(psba_handle h, double *L) {
   CHECK_H(h);
   NEED(h, h->uploaded, "no problem uploaded");
+  NEED(h, !FREE_SPARSE(h), "no Cholesky chain and no modified Cholesky factor with PSBA_SOLVER_SPARSE");
   NEED(h, h->solver != PSBA_SOLVER_PCG, "no modified Cholesky factor with PSBA_SOLVER_PCG (the estimate is a Gershgorin shift)");
   NEED(h, h->cholmod_factor, "psba_cholmod_lambda first (every verb that factors or assembles S overwrites the factor)");
   if (!L) return fail(h, PSBA_E_INVALID, "psba_get_cholmod_factor: null pointer");
@@ -1680,6 +1742,7 @@ int psba_get_reduce_buffer(psba_handle h, double *out) {
   CHECK_H(h);
   NEED(h, h->assembled, "psba_schur_assemble first");
   NEED(h, !h->comm, "the reduce-buffer verbs are for handles without a communicator");
+  NEED(h, !FREE_SPARSE(h), "no dense reduce buffer with PSBA_SOLVER_SPARSE (psba_get_sparse_S)");
   NEED(h, h->solver != PSBA_SOLVER_PCG, "no dense reduce buffer with PSBA_SOLVER_PCG (psba_get_sparse_S)");
   NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");
   if (packed_hook(h)) return d2h(h, out, h->redp, sizeof(double) * h->packed_doubles);

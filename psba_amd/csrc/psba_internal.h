@@ -154,6 +154,20 @@ struct BlockProdPlanHost {
   int ntiles = 0;            // partial tiles (a camera block squared each)
   int seg_len = 0;
 };
+// the block-sparse S of these camera blocks (PSBA_SOLVER_SPARSE, kernels_free_pcg.hip): the plan's blocks plus a
+// diagonal block for every camera without a product, ascending by (j, k), and the symmetric row walk of the product
+struct BlockRowsHost {
+  std::vector<int2> jk;        // the stored blocks
+  std::vector<int> slot_of;    // [plan.blocks] slot of each of the plan's blocks in jk
+  std::vector<int> diag_slot;  // [nC] slot of block (j, j)
+  std::vector<char> added;     // [nC] 1: no product stores block (j, j)
+  std::vector<int> rowptr;     // [nC + 1]
+  std::vector<int2> rowent;    // (slot, other camera | how << 28), how as in bs_rowent; a row ascending by slot
+  long long nadded = 0;
+};
+void build_block_rows(int nCams, const BlockProdPlanHost &plan, BlockRowsHost &out);  // blockprod_plan.cpp
+constexpr int FBSR_ADDED = 1 << 30;  // flag in bs_diag on this route
+constexpr int FPCG_CAP = 128;        // workgroups of the persistent grids = partial sums per inner product
 constexpr int KD_UNIT = 64;        // observations of a camera unit on this route: one wave, one observation per lane
 constexpr int KD_SEG_DEFAULT = 64; // products per segment (PSBA_FKD_SEG overrides)
 constexpr int KD_RED = 4 * 520;    // doubles of the reduction scratch: camera terms | up to 512 workgroups x 4 sums
@@ -278,17 +292,18 @@ struct ProblemState {
   double pcg_relres = 0.0;
   bool pcg_exhausted = false;   // the last solve used up max_iter without reaching tol
   long long bs_nblk = 0;
-  psba::DevBuf<double> bs_val;  // [bs_nblk][36] | e_a [nA] right behind (one all-reduce)
-  double *bs_ea = nullptr;      // = bs_val + 36 bs_nblk (not owned)
+  psba::DevBuf<double> bs_val;  // [bs_nblk][cnp^2] | e_a [nA] right behind (one all-reduce)
+  double *bs_ea = nullptr;      // = bs_val + cnp^2 bs_nblk (not owned)
   psba::DevBuf<int2> bs_jk;     // [bs_nblk] (j, k)
-  psba::DevBuf<int> bs_diag;    // [nC] index of block (j, j)
+  psba::DevBuf<int> bs_diag;    // [nC] index of block (j, j) (PSBA_SOLVER_SPARSE on blocks of 11 / 16: | FBSR_ADDED where
+                                // no product stores the block and k_fbsr_finalize writes it whole)
   // the full symmetric pattern by block row, for the product S p without atomics: row j's entries
   // [bs_rowptr[j], bs_rowptr[j + 1]) = (slot of the stored block, other camera | how to read it << 28:
   // 0 as stored (j is the block's row), 1 transposed (j is its column), 2 the diagonal block)
   psba::DevBuf<int> bs_rowptr;
   psba::DevBuf<int2> bs_rowent;
   psba::DevBuf<double> pcg_vec;   // r | z | p | q, nA each
-  psba::DevBuf<double> pcg_minv;  // [nC][36] inverses of the diagonal blocks
+  psba::DevBuf<double> pcg_minv;  // [nC][cnp^2] inverses of the diagonal blocks
   psba::DevBuf<double> pcg_scal;  // device scalars (their pinned mirror pcg_host lives with the handle)
   // K2 owner route (many cameras): see OwnerPlanHost
   psba::DevBuf<int2> own_prod;
@@ -411,6 +426,9 @@ struct psba_ctx : ProblemState {
   std::vector<hipEvent_t> chol_events;  // the look-ahead of the blocked Cholesky chain (two per super-panel)
 
   int solver = 0;               // PSBA_SOLVER_* (block-sparse S + preconditioned CG: psba_set_solver, kernels_pcg.hip)
+  // PSBA_SOLVER_SPARSE was asked for: stored as PSBA_SOLVER_PCG (with six-parameter blocks it is that mode), and on
+  // blocks of 11 / 16 the upload takes the route of kernels_free_pcg.hip instead of refusing
+  bool sparse_any_block = false;
   int cnp = 6;  // parameters per camera: 6 (fixed intrinsics, the reference's kernels), 11 (psba_set_camera_model: free intrinsics) or 16 (free intrinsics and distortion)
   double pcg_tol = 1e-10;
   int pcg_maxit = 500;
@@ -504,6 +522,10 @@ int launch_bsr_finalize(psba_ctx *h, double mu);
 int launch_pcg_solve(psba_ctx *h);
 int launch_bsr_gershgorin(psba_ctx *h, double *lambda, double *info3);
 int launch_bsr_times(psba_ctx *h, const double *x_host, double *y_host);
+// the same three on blocks of 11 / 16 (kernels_free_pcg.hip)
+int launch_fbsr_finalize(psba_ctx *h, double mu, const double *D);
+int launch_fpcg_solve(psba_ctx *h);
+int launch_fbsr_times(psba_ctx *h, const double *x_host, double *y_host);
 // kernels_chol_graph.hip
 int launch_chol_graph(psba_ctx *h);
 int chol_dist_shape(psba_ctx *h, int *NB, int *blocked);
