@@ -138,6 +138,32 @@ int psba_camera_block(psba_handle h, int *cnp); /* 6, 11 or 16 */
 int psba_set_intrinsics_mask(psba_handle h, const unsigned char free10[10]);
 int psba_intrinsics_mask(psba_handle h, unsigned char out10[10]);
 
+/* ---- per-camera masks of the ten intrinsics (PSBA_CAMERA_FREE_KD) ------------------------------
+ * Mixed jobs: some cameras calibrated (a rig, a lab calibration), some not; new images added to a finished
+ * reconstruction; images that must stay where they are.  free10_per_cam [10 nCams], row j = camera j, order (fu, u0,
+ * v0, ar, s, k1..k5), non-zero = optimised.  Intrinsic k of camera j is optimised iff psba_set_intrinsics_mask frees k
+ * AND row j frees k; psba_intrinsics_mask keeps returning the global ten flags.  NULL, or a table with no zero entry,
+ * is no table: the handle then runs the code of one that never called this and produces the same bits.
+ * A coordinate that is not optimised is, bit for bit, what a coordinate masked by psba_set_intrinsics_mask is: the
+ * column of A is zero; W, U off the diagonal, g_a, e_a and dp are exactly 0; the placeholder coeff is on the diagonal
+ * of U and coeff + mu (coeff + mu D) on that of S; psba_max_diag / psba_begin skip it; its row and column of a camera
+ * prior are dropped while the gradient of the free coordinates takes the whole d; the proposal carries the current
+ * bits; the cost is untouched.  A camera with no free intrinsic and a held pose (psba_set_held) is a wholly fixed
+ * camera; nothing else is needed for one.  Under PSBA_SOLVER_SPARSE its diagonal block and the inverse the
+ * preconditioner keeps are diagonal.  psba_free_covariance_compute returns exact zeros in the rows and columns of a
+ * masked coordinate, and sigma 0.
+ * Groups: the members of a group with more than one camera carry equal rows -- whichever of psba_set_camera_masks and
+ * psba_set_intrinsics_groups is called second checks it before it touches the device and returns PSBA_E_INVALID with
+ * the first offending camera and coordinate.  A shared coordinate is then free or masked for the whole group.
+ * The table composes in either order with the global mask, held poses and points, priors, the observation weighting,
+ * the damping rule and both solvers.  After psba_upload_problem (a new upload resets to no table); PSBA_E_STATE under
+ * another camera model (blocks of 11 have no mask) and while a try is in flight; a refused call changes nothing;
+ * setting the table discards a linearization queued ahead and invalidates psba_get_free_obs_blocks and
+ * psba_get_damping_diag.  No floating-point atomics: two runs stay bit-identical.  psba_camera_masks: the table as
+ * set, 0 / 1 per entry; all ones when there is none. */
+int psba_set_camera_masks(psba_handle h, const unsigned char *free10_per_cam /* 10 nCams */);
+int psba_camera_masks(psba_handle h, unsigned char *out10_per_cam /* 10 nCams */);
+
 /* ---- intrinsics shared between cameras (PSBA_CAMERA_FREE_KD) ----------------------------------
  * One physical camera takes many images: group_of_cam[j] is any int, cameras with equal labels share their ten
  * intrinsics (fu, u0, v0, ar, s, k1..k5).  The representative rep(j) of a group is its lowest camera index; P maps
@@ -679,8 +705,8 @@ int psba_get_cholmod_factor(psba_handle h, double *L);
  * row-major) | e (2).  Either pointer may be null.  A device-to-host copy, no kernel.  Valid after a psba_linearize
  * (or psba_begin) at the current parameters until something overwrites the buffers or moves the parameters:
  * psba_linearize_ahead (it reuses the B | e buffer), psba_accept of a proposal that was not linearized ahead,
- * psba_set_params, psba_reset_params, psba_set_distortion, psba_set_intrinsics_mask, psba_set_intrinsics_groups,
- * psba_upload_problem -- PSBA_E_STATE then, as before any linearization and for six-parameter camera blocks (whose
+ * psba_set_params, psba_reset_params, psba_set_distortion, psba_set_intrinsics_mask, psba_set_camera_masks,
+ * psba_set_intrinsics_groups, psba_upload_problem -- PSBA_E_STATE then, as before any linearization and for six-parameter camera blocks (whose
  * blocks the sba_func.h mirror reads: psba_compute_jacobiQT, psba_compute_Wblks). */
 int psba_get_free_obs_blocks(psba_handle h, double *W, double *Be);
 /* ---- test hook: D[nT] = [cnp per camera ; 3 per point] of the current linearization under PSBA_DAMPING_MARQUARDT
@@ -688,7 +714,7 @@ int psba_get_free_obs_blocks(psba_handle h, double *W, double *Be);
  * after a psba_linearize or psba_begin under Marquardt -- and after the psba_accept of a proposal that was linearized
  * ahead, whose D comes with it -- until the parameters or the model change: psba_accept of a proposal that was not
  * linearized ahead, psba_set_params, psba_reset_params, psba_set_distortion, psba_set_intrinsics_mask,
- * psba_set_intrinsics_groups, psba_set_damping, psba_upload_problem -- PSBA_E_STATE then, as under
+ * psba_set_camera_masks, psba_set_intrinsics_groups, psba_set_damping, psba_upload_problem -- PSBA_E_STATE then, as under
  * PSBA_DAMPING_IDENTITY and for six-parameter camera blocks.  (psba_linearize_ahead writes the second set: the
  * diagonal of a rejected step's current parameters stays readable.) */
 int psba_get_damping_diag(psba_handle h, double *D);

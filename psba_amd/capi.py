@@ -193,6 +193,8 @@ SIGNATURES = [
     ("psba_owner_plan_destroy", None, [C.c_void_p]),
     ("psba_set_intrinsics_mask", C.c_int, [_h, C.POINTER(C.c_ubyte)]),
     ("psba_intrinsics_mask", C.c_int, [_h, C.POINTER(C.c_ubyte)]),
+    ("psba_set_camera_masks", C.c_int, [_h, C.POINTER(C.c_ubyte)]),
+    ("psba_camera_masks", C.c_int, [_h, C.POINTER(C.c_ubyte)]),
     ("psba_set_intrinsics_groups", C.c_int, [_h, C.POINTER(C.c_int)]),
     ("psba_intrinsics_groups", C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("psba_set_damping", C.c_int, [_h, C.c_int, C.c_double, C.c_double]),
@@ -535,6 +537,22 @@ class Psba:
         m = np.zeros(10, dtype=np.uint8)
         self._ck(lib.psba_intrinsics_mask(self._h, m.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return tuple(int(v) for v in m)
+
+    def set_camera_masks(self, free=None):
+        """psba_set_camera_masks: [nC, 10] flags, row j = camera j, order (fu, u0, v0, ar, s, k1..k5), non-zero =
+        optimised (ANDed with the global mask); None, or a table without a zero, = no table.  CAMERA_FREE_KD only."""
+        if free is None:
+            return self._ck(lib.psba_set_camera_masks(self._h, None))
+        m = np.ascontiguousarray((np.asarray(free).reshape(-1) != 0).astype(np.uint8))
+        if self.nC and m.size != 10 * self.nC:  # (before an upload nC is 0: the library refuses, nothing is read)
+            raise PsbaError(-1, f"set_camera_masks: {m.size} flags for {self.nC} cameras of 10 intrinsics")
+        self._ck(lib.psba_set_camera_masks(self._h, m.ctypes.data_as(C.POINTER(C.c_ubyte))))
+
+    def camera_masks(self):
+        """psba_camera_masks -> [nC, 10] uint8, the table as set; all ones when there is none"""
+        m = np.zeros((self.nC, 10), dtype=np.uint8)
+        self._ck(lib.psba_camera_masks(self._h, m.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return m
 
     def set_intrinsics_groups(self, group_of_cam=None):
         """psba_set_intrinsics_groups: one label (any int) per camera, equal labels share their ten intrinsics;

@@ -1,6 +1,6 @@
 // free_blocks.h -- what the kernel files that serve the free-intrinsics route share (kernels_free.hip, kernels_cov.hip):
 // the two camera blocks the kernels are templated on, and the groups' tables with the predicate of a folded-away
-// coordinate.
+// coordinate, and the free bits of a camera under the per-camera masks.
 #pragma once
 #include "camera_model.h"
 #include "psba_internal.h"
@@ -32,6 +32,16 @@ struct FreeKD {
     residual_obs_dist(cam, q0, cam + 10, M, cam + 5, mx, my, e0, e1);
   }
 };
+// ---- per-camera masks (psba_set_camera_masks) ----
+// cmask [nC]: one word per camera, bit k set = row j of the table frees intrinsic k.  Null: no table, and the branch
+// (uniform: the pointer is a kernel argument) leaves the global mask as it is, with no load -- the idiom of FreeDamp::D.
+// Every kernel that asks "is intrinsic k of camera j optimised" asks these bits; a coordinate they mask is what a
+// coordinate masked by psba_set_intrinsics_mask is.  The members of a group carry equal rows (the setters see to it),
+// so the kernels of the groups take the bits of any member for the group.
+__device__ __forceinline__ unsigned kd_free_bits(unsigned mask, const unsigned short *cmask, int j) {
+  return cmask ? mask & cmask[j] : mask;
+}
+
 // ---- intrinsics shared between cameras (psba_set_intrinsics_groups): the tables of the groups ----
 struct KdGroups {
   const int *rep;   // [nC] representative of each camera
@@ -40,10 +50,11 @@ struct KdGroups {
   const int *gmem;  // members, ascending; the first of a group is its representative
   int nmg;
   unsigned mask;
+  const unsigned short *cmask;  // [nC] per-camera masks, null: none (kd_free_bits)
 };
 __device__ __forceinline__ bool kd_folded(const KdGroups &G, int t) {  // t: coordinate of the camera part
   const int k = t % KD_CNP;
-  return k < 10 && ((G.mask >> k) & 1u) && G.rep[t / KD_CNP] != t / KD_CNP;
+  return k < 10 && ((kd_free_bits(G.mask, G.cmask, t / KD_CNP) >> k) & 1u) && G.rep[t / KD_CNP] != t / KD_CNP;
 }
 // the handle's tables as a kernel argument
 inline KdGroups kd_groups(const psba_ctx *h) {
@@ -54,6 +65,7 @@ inline KdGroups kd_groups(const psba_ctx *h) {
   G.gmem = h->kd_gmem;
   G.nmg = h->kd_nmg;
   G.mask = h->kd_mask;
+  G.cmask = h->kd_cmask;
   return G;
 }
 

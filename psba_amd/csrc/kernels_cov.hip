@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_cov_map_free(KdGroups G, const unsigned
   if (t >= nA) return;
   const int j = t / T::CNP, k = t % T::CNP;
   int s = t;
-  if (k < T::NI ? !((G.mask >> k) & 1u) : (held_pose && held_pose[j]))
+  if (k < T::NI ? !((kd_free_bits(G.mask, G.cmask, j) >> k) & 1u) : (held_pose && held_pose[j]))
     s = -1;
   else if (T::CNP == KD_CNP && G.rep && kd_folded(G, t))
     s = KD_CNP * G.rep[j] + k;

@@ -51,6 +51,7 @@ struct FreeArgs {
   const unsigned char *held_pose, *held_pt;  // read by the HELD instantiations only (last: the other offsets stay)
   const double *isig;                        // read by the WGT instantiations only (below)
   RobustLoss rl;
+  const unsigned short *cmask;               // per-camera masks, null: none (kd_free_bits)
 };
 
 // ---- observation weighting (psba_set_obs_weighting) ----
@@ -152,13 +153,14 @@ __global__ __launch_bounds__(64) void k_free_linearize(FreeArgs p) {
   }
   const int4 u = p.cam_units[blockIdx.x];
   const int n = u.z - u.y;
+  const unsigned mask = kd_free_bits(p.mask, p.cmask, u.x);  // (the unit's camera: one load per wave, none without a table)
   if (lane < n) {
     const int a = p.cam_obs[u.y + lane];
     int i, j;
     double cam[CNP], q0[4], M[3], e[2], A[2 * CNP], B[6];
     double2 m;
     free_load<T>(p, a, i, j, cam, q0, M, m);
-    T::linearize(cam, q0, M, m.x, m.y, e, A, B, p.mask);
+    T::linearize(cam, q0, M, m.x, m.y, e, A, B, mask);
     if (WGT) {  // e, A, B by 1 / sigma_a, then by omega_a of the scaled e (before anything is stored)
       const double is = p.isig[a];
       double s, rho, om;
@@ -227,12 +229,14 @@ __global__ __launch_bounds__(64) void k_free_linearize(FreeArgs p) {
 // has zero sums
 template <class T, bool HELD, bool PRIOR>
 __global__ __launch_bounds__(256) void k_free_finish_cams(const double *upart, const int *cuptr, int nC, double coeff,
-                                                          double coeff_g, unsigned mask, const unsigned char *held_pose,
-                                                          double *U, double *ga, FreePriors pr, const double *cams) {
+                                                          double coeff_g, unsigned mask0, const unsigned short *cmask,
+                                                          const unsigned char *held_pose, double *U, double *ga, FreePriors pr,
+                                                          const double *cams) {
   constexpr int CNP = T::CNP, UP = CNP * CNP + CNP;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)nC * UP) return;
   const int j = (int)(t / UP), e = (int)(t % UP);
+  const unsigned mask = kd_free_bits(mask0, cmask, j);
   double s = 0.0;
   for (int u = cuptr[j]; u < cuptr[j + 1]; u++) s += upart[UP * (size_t)u + e];
   if (PRIOR) {  // (a held row or column of the information matrix is dropped; the gradient takes the whole d)
@@ -377,15 +381,15 @@ __global__ __launch_bounds__(256) void k_free_prior_cost(const int *list, const 
 // the largest diagonal entry of U and V over the free parameters (a maximum does not depend on the order)
 template <class T, bool HELD>
 __global__ __launch_bounds__(1024) void k_free_max_diag(const double *U, const double *PV, int nC, int nP, unsigned mask,
-                                                        const unsigned char *held_pose, const unsigned char *held_pt,
-                                                        double *out) {
+                                                        const unsigned short *cmask, const unsigned char *held_pose,
+                                                        const unsigned char *held_pt, double *out) {
   constexpr int CNP = T::CNP;
   __shared__ double sRed[16];
   double m = 0.0;
   for (int t = threadIdx.x; t < CNP * nC; t += blockDim.x) {
     const int r = t % CNP;
     if (HELD && r >= T::NI && held_pose[t / CNP]) continue;
-    if (r >= T::NI || ((mask >> r) & 1u)) m = fmax(m, U[(size_t)CNP * CNP * (t / CNP) + (CNP + 1) * r]);
+    if (r >= T::NI || ((kd_free_bits(mask, cmask, t / CNP) >> r) & 1u)) m = fmax(m, U[(size_t)CNP * CNP * (t / CNP) + (CNP + 1) * r]);
   }
   for (int i = threadIdx.x; i < nP; i += blockDim.x) {
     if (HELD && held_pt[i]) continue;
@@ -416,8 +420,9 @@ struct FreeDamp {
 // folded-away one coeff, as a masked coordinate.  Points: the diagonal of V_i
 template <class T>
 __global__ __launch_bounds__(256) void k_free_damp_diag(const double *U, const double *PV, const int *rep, const int *gidx,
-                                                        const int *gptr, const int *gmem, unsigned mask, double coeff,
-                                                        int nA, int nT, double dmin, double dmax, double *D) {
+                                                        const int *gptr, const int *gmem, unsigned mask,
+                                                        const unsigned short *cmask, double coeff, int nA, int nT, double dmin,
+                                                        double dmax, double *D) {
   constexpr int CNP = T::CNP;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nT) return;
@@ -425,7 +430,7 @@ __global__ __launch_bounds__(256) void k_free_damp_diag(const double *U, const d
   if (t < nA) {
     const int j = t / CNP, r = t % CNP;
     n = U[(size_t)CNP * CNP * j + (CNP + 1) * r];
-    const int g = (rep && r < 10 && ((mask >> r) & 1u)) ? gidx[j] : -1;
+    const int g = (rep && r < 10 && ((kd_free_bits(mask, cmask, j) >> r) & 1u)) ? gidx[j] : -1;
     if (g >= 0 && rep[j] == j) {
       n = 0.0;
       for (int q = gptr[g]; q < gptr[g + 1]; q++) n += U[(size_t)CNP * CNP * gmem[q] + (CNP + 1) * r];
@@ -600,6 +605,7 @@ struct FreeBackArgs {
   FreePriors pr;                             // read by the PRIOR instantiations only
   const double *isig;                        // read by the WGT instantiations only
   RobustLoss rl;
+  const unsigned short *cmask;               // per-camera masks, null: none (kd_free_bits)
 };
 // the camera priors' cost at the proposal, from the newcams this workgroup has just written (behind a barrier): the
 // try's `new cost` slot, thread per coordinate r: d_r (sum_c L[r][c] d[c])
@@ -636,7 +642,7 @@ __global__ __launch_bounds__(256) void k_free_backsub_cams(FreeBackArgs p) {  //
   for (int t = threadIdx.x; t < p.nA; t += blockDim.x) {
     const int r = t % T::CNP;
     const bool hp = HELD && r >= T::NI && p.held_pose[t / T::CNP];
-    const bool held = hp || (r < T::NI && !((p.mask >> r) & 1u));
+    const bool held = hp || (r < T::NI && !((kd_free_bits(p.mask, p.cmask, t / T::CNP) >> r) & 1u));
     double d = p.dp[t];
     if (held) p.dp[t] = d = 0.0;  // (already zero to rounding: S decouples the entry; exactly zero by definition)
     const double c = hp ? p.cams[t] : p.cams[t] + d;  // (a held pose keeps its bits: -0.0 + 0.0 would be +0.0)
@@ -763,8 +769,8 @@ __global__ __launch_bounds__(256) void k_kd_fold_rows(double *S, KdGroups G, int
   if (t >= (size_t)G.nmg * 10 * nA) return;
   const int c = (int)(t % nA), gk = (int)(t / nA);
   const int g = gk / 10, k = gk % 10;
-  if (!((G.mask >> k) & 1u)) return;
   const int m0 = G.gptr[g], m1 = G.gptr[g + 1];
+  if (!((kd_free_bits(G.mask, G.cmask, G.gmem[m0]) >> k) & 1u)) return;  // (the members carry equal rows)
   double s = 0.0;
   for (int q = m0; q < m1; q++) s += S[(size_t)(KD_CNP * G.gmem[q] + k) * n32 + c];
   S[(size_t)(KD_CNP * G.gmem[m0] + k) * n32 + c] = s;
@@ -778,9 +784,9 @@ __global__ __launch_bounds__(256) void k_kd_fold_cols(double *S, KdGroups G, int
   const int k = (int)(t % 10);
   const size_t u = t / 10;
   const int r = (int)(u % (nA + 1)), g = (int)(u / (nA + 1));
-  if (!((G.mask >> k) & 1u)) return;
-  double *row = S + (size_t)(r == nA ? n32 : r) * n32;
   const int m0 = G.gptr[g], m1 = G.gptr[g + 1];
+  if (!((kd_free_bits(G.mask, G.cmask, G.gmem[m0]) >> k) & 1u)) return;
+  double *row = S + (size_t)(r == nA ? n32 : r) * n32;
   double s = 0.0;
   for (int q = m0; q < m1; q++) s += row[KD_CNP * G.gmem[q] + k];
   row[KD_CNP * G.gmem[m0] + k] = s;
@@ -818,7 +824,7 @@ __global__ __launch_bounds__(1024) void k_kd_max_diag_groups(const double *U, co
   double m = 0.0;
   for (int t = threadIdx.x; t < KD_CNP * nC; t += blockDim.x) {
     const int j = t / KD_CNP, r = t % KD_CNP;
-    if (r < 10 && !((G.mask >> r) & 1u)) continue;
+    if (r < 10 && !((kd_free_bits(G.mask, G.cmask, j) >> r) & 1u)) continue;
     if (HELD && r >= 10 && held_pose[j]) continue;
     const int g = r < 10 ? G.gidx[j] : -1;
     if (g < 0) {
@@ -858,7 +864,7 @@ __global__ __launch_bounds__(256) void k_kd_backsub_cams_groups(FreeBackArgs p, 
   for (int t = threadIdx.x; t < p.nA; t += blockDim.x) {
     const int j = t / KD_CNP, r = t % KD_CNP;
     const bool hp = HELD && r >= 10 && p.held_pose[j];
-    const bool held = hp || (r < 10 && !((p.mask >> r) & 1u));
+    const bool held = hp || (r < 10 && !((kd_free_bits(p.mask, p.cmask, j) >> r) & 1u));
     const bool copy = r < 10 && !held && rep[j] != j;
     double d = copy ? p.dp[KD_CNP * (size_t)rep[j] + r] : p.dp[t];
     if (held) d = 0.0;
@@ -903,6 +909,7 @@ static FreeArgs free_args(psba_ctx *h, int set) {
   a.pub_stamp = 0.0;
   a.isig = h->obs_isig;
   a.rl = make_robust_loss(h->wgt_kind, h->wgt_c);
+  a.cmask = h->kd_cmask;
   return a;
 }
 static FreePriors free_priors(psba_ctx *h) {
@@ -934,13 +941,14 @@ static int linearize_free(psba_ctx *h, bool ahead, bool publish) {
   const long long nfin = (long long)d.nC * (T::CNP * T::CNP + T::CNP);
   const FreePriors pr = free_priors(h);
   hipLaunchKernelGGL((k_free_finish_cams<T, HELD, PRIOR>), dim3((unsigned)((nfin + 255) / 256)), dim3(256), 0, h->stream,
-                     h->free_upart, h->free_cuptr, d.nC, h->coeff, h->coeff_g, h->kd_mask, a.held_pose, Uo, gao, pr, a.cams);
+                     h->free_upart, h->free_cuptr, d.nC, h->coeff, h->coeff_g, h->kd_mask, a.cmask, a.held_pose, Uo, gao, pr,
+                     a.cams);
   hipLaunchKernelGGL((k_free_point_sums<HELD, PRIOR>), dim3((unsigned)((d.nP + 255) / 256)), dim3(256), 0, h->stream,
                      h->free_Be, h->ptr, d.nP, h->coeff, h->coeff_g, a.held_pt, PVo, pr, a.pts);
   if (h->damp_kind == PSBA_DAMPING_MARQUARDT)  // D of this set, behind the two kernels whose sums it reads
     hipLaunchKernelGGL(k_free_damp_diag<T>, dim3((unsigned)((d.nT + 255) / 256)), dim3(256), 0, h->stream, (const double *)Uo,
                        (const double *)PVo, (const int *)h->kd_rep, (const int *)h->kd_gidx, (const int *)h->kd_gptr,
-                       (const int *)h->kd_gmem, h->kd_mask, h->coeff, d.nA, d.nT, h->damp_dmin, h->damp_dmax,
+                       (const int *)h->kd_gmem, h->kd_mask, a.cmask, h->coeff, d.nA, d.nT, h->damp_dmin, h->damp_dmax,
                        (double *)(ahead ? h->damp_D_alt : h->damp_D));
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
@@ -998,7 +1006,7 @@ static int max_diag_free(psba_ctx *h) {
                        kd_groups(h), hp, hq, h->scal + SC_MAXDIAG);
   else
     hipLaunchKernelGGL((k_free_max_diag<T, HELD>), dim3(1), dim3(1024), 0, h->stream, h->U, h->PV, h->d.nC, h->d.nP,
-                       h->kd_mask, hp, hq, h->scal + SC_MAXDIAG);
+                       h->kd_mask, (const unsigned short *)h->kd_cmask, hp, hq, h->scal + SC_MAXDIAG);
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }
@@ -1089,6 +1097,7 @@ static int backsub_free(psba_ctx *h, double mu) {
   a.mu = mu;
   a.dm = free_damp(h);
   a.mask = h->kd_mask;
+  a.cmask = h->kd_cmask;
   a.nA = d.nA;
   a.nP = d.nP;
   const int grid = free_grid(d.nP, KD_RED / 4 - 8);

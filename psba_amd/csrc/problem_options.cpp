@@ -1,5 +1,5 @@
 // problem_options.cpp -- the settings of an uploaded problem (include/psba_hip.h): camera model, lens model,
-// robust loss, fixed blocks, the mask and the groups of the intrinsics, held poses and points, priors, the observation weighting, the damping rule,
+// robust loss, fixed blocks, the mask, the per-camera masks and the groups of the intrinsics, held poses and points, priors, the observation weighting, the damping rule,
 // and their getters.  Every setter is built from the same three pieces: settable() says whether it may run now,
 // stage() puts new device tables in place all or nothing, model_changed() / params_changed() drop what was derived.
 #include <algorithm>
@@ -275,6 +275,54 @@ int psba_intrinsics_mask(psba_handle h, unsigned char *out10) {
   return PSBA_OK;
 }
 
+// ---- per-camera masks of the ten intrinsics (PSBA_CAMERA_FREE_KD) ----
+// the members of a group carry equal rows: whichever of the two setters comes second checks it on the host tables
+static int masks_split(psba_ctx *h, const char *who, const std::vector<int> &rep, const std::vector<unsigned short> &cm) {
+  static const char *names[10] = {"fu", "u0", "v0", "ar", "s", "k1", "k2", "k3", "k4", "k5"};
+  for (int j = 0; j < (int)rep.size() && !cm.empty(); j++) {
+    const unsigned diff = (unsigned)(cm[j] ^ cm[rep[j]]);
+    if (!diff) continue;
+    int k = 0;
+    while (!((diff >> k) & 1u)) k++;
+    return fail(h, PSBA_E_INVALID, "%s: camera %d and camera %d, the representative of its group, differ in coordinate %d "
+                "(%s) of their rows of psba_set_camera_masks: the members of a group carry equal rows",
+                who, j, rep[j], k, names[k]);
+  }
+  return PSBA_OK;
+}
+
+int psba_set_camera_masks(psba_handle h, const unsigned char *free10_per_cam) {
+  CHECK_H(h);
+  TRY(settable(h, __func__, FREE_KD, "; blocks of 11 (PSBA_CAMERA_FREE_K) have no mask"));
+  const int nC = h->d.nC;
+  std::vector<unsigned short> cm;
+  bool any_zero = false;
+  if (free10_per_cam) {
+    cm.assign((size_t)nC, 0);
+    for (int j = 0; j < nC; j++)
+      for (int k = 0; k < 10; k++) {
+        if (free10_per_cam[10 * (size_t)j + k])
+          cm[j] |= (unsigned short)(1u << k);
+        else
+          any_zero = true;
+      }
+  }
+  if (!any_zero) cm.clear();  // a table without a zero entry is no table: no buffer, the kernels read the global mask alone
+  if (!h->kd_rep_h.empty()) TRY(masks_split(h, __func__, h->kd_rep_h, cm));
+  TRY(stage(h, Staged(h->kd_cmask, cm)));
+  h->kd_cmask_h = std::move(cm);
+  model_changed(h);
+  return PSBA_OK;
+}
+
+int psba_camera_masks(psba_handle h, unsigned char *out10_per_cam) {
+  CHECK_H(h);
+  TRY(settable(h, __func__, FREE_KD, "; blocks of 11 (PSBA_CAMERA_FREE_K) have no mask", ANY_TIME));
+  for (int j = 0; out10_per_cam && j < h->d.nC; j++)
+    for (int k = 0; k < 10; k++) out10_per_cam[10 * (size_t)j + k] = h->kd_cmask_h.empty() ? 1 : (h->kd_cmask_h[j] >> k) & 1u;
+  return PSBA_OK;
+}
+
 // ---- intrinsics shared between cameras (PSBA_CAMERA_FREE_KD) ----
 int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam) {
   CHECK_H(h);
@@ -294,6 +342,7 @@ int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam) {
   }
   std::vector<int> gidx, gptr, gmem;
   if (ngroups < nC) {
+    TRY(masks_split(h, __func__, rep, h->kd_cmask_h));  // (host tables: before anything is read from the device)
     std::vector<double> c((size_t)h->d.nA);
     const double *src[2] = {h->cams[h->cur], h->params0};
     const char *who[2] = {"psba_set_intrinsics_groups (current parameters)", "psba_set_intrinsics_groups (the psba_reset_params copy)"};

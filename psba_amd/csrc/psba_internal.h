@@ -324,6 +324,11 @@ struct ProblemState {
   psba::DevBuf<double> free_red;     // [KD_RED] per-workgroup partial sums (cost; the try's four sums)
   // blocks of 16 only (the setters refuse the others, which so keep every intrinsic free and no groups)
   unsigned kd_mask = 0x3FFu;       // psba_set_intrinsics_mask: bit k set = intrinsic k is optimised
+  // per-camera masks (psba_set_camera_masks): one word per camera, bit k set = the camera's row frees
+  // intrinsic k; the free bits of camera j are kd_mask & kd_cmask[j].  Empty / null = no table (a table without a
+  // zero entry is none): the kernels then read kd_mask alone, with no load; an upload resets to none
+  std::vector<unsigned short> kd_cmask_h;
+  psba::DevBuf<unsigned short> kd_cmask;  // [nC] kd_cmask_h on the device
   // shared intrinsics (psba_set_intrinsics_groups): empty / null = no grouping, the ungrouped launches
   std::vector<int> kd_rep_h;       // [nC] representative (lowest member) of each camera's group; empty: none
   int kd_ngroups = 0;              // groups in all (singletons included) while kd_rep_h is set
