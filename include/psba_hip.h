@@ -876,6 +876,47 @@ int psba_set_sparse_S(psba_handle h, const double *val, const double *ea);
  * psba_schur_assemble and psba_schur_solve, PSBA_SOLVER_PCG, no structure-only try; PSBA_E_STATE otherwise);
  * changes neither the blocks nor e_a nor a later solve.  Synchronises. */
 int psba_sparse_S_times(psba_handle h, const double *x, double *y);
+/* ---- covariance of chosen cameras under PSBA_SOLVER_SPARSE on camera blocks of 11 / 16 -------------
+ * psba_free_covariance_compute inverts an nA x nA square that this route never allocates, and keeps refusing a sparse
+ * handle.  Here the object is the joint covariance of a chosen set of cameras: C = scale (S(mu)^-1)[sel, sel], from
+ * solving S X = E_sel -- every chosen camera contributes cnp right-hand sides, one panel of 16 columns
+ * (kernels_free_pcg_many.hip).
+ *   * The linearization is psba_linearize(h, 1, 1) at the current parameters, as for psba_free_covariance_compute: the
+ *     mask, the per-camera masks, held poses and points, priors, observation weighting and the damping rule are in S.
+ *   * A coordinate is live if it is neither masked nor a held pose coordinate (groups cannot be set on this route).
+ *   * For a live chosen coordinate q the column x_q solves S(mu) x_q = e_q by the route's conjugate gradients: block-
+ *     Jacobi preconditioning, psba_set_solver's tol and max_iter, the stop rule of psba_schur_solve on this route.
+ *   * For a masked or held chosen coordinate nothing is solved: its row and column of C and its row of cols are exactly
+ *     +0.0, not the inverse of the placeholder.
+ *   * C is taken from the solved columns: block (a, b) of the chosen list with position a >= b from the columns solved
+ *     for camera sel[b], rows of camera sel[a], written to both sides; inside a diagonal block the lower triangle is the
+ *     matrix.  So C is bit-symmetric.
+ *   * C = scale (...); cols is not scaled.
+ *   * mu = 0 needs a gauge, held poses or priors; mu > 0 gives a regularised inverse and NOT a covariance.
+ * Columns are independent: a column's bits, iteration count and relres depend neither on which other cameras are
+ * chosen nor on their order; every inner product is summed in a fixed order and there are no floating-point atomics, so
+ * two calls on the same state return the same bits.
+ * reassemble != 0: linearizes with (1, 1) unless that linearization is current, then runs psba_schur_assemble(mu); the
+ * handle is left as after that call (a psba_schur_solve may follow).  reassemble == 0: works on the blocks as they
+ * stand, in the state of psba_get_sparse_S -- so also on the blocks of psba_set_sparse_S.  The verb uses buffers of its
+ * own (six vectors of 16 nA doubles per panel, at most 8 panels at a time, allocated at first use and dropped at an
+ * upload): a later psba_schur_solve, psba_backsub or psba_levmar runs as on a handle that never called it.
+ * Returns PSBA_OK, PSBA_NOT_SPD (a bad pivot of a diagonal block, p.Sp <= 0 in any column, a residual that is not
+ * finite) or PSBA_PCG_MAXIT (some column used up max_iter: iters and relres say which; C is still written), and
+ * synchronises.  PSBA_E_STATE before an upload, while a try is in flight and on every handle that does not run
+ * PSBA_SOLVER_SPARSE on blocks of 11 / 16 (dense free-intrinsics handles: psba_free_covariance_compute; six-parameter
+ * blocks: psba_covariance_compute); PSBA_E_INVALID for a mu that is not finite and >= 0, a scale that is not finite
+ * and > 0, n_sel < 1, an index out of range or listed twice, C == NULL.  A refused call changes nothing.
+ * Not here: point covariances, shared intrinsics, rank layouts. */
+int psba_sparse_camera_covariance(psba_handle h, double mu, double scale, int reassemble, int n_sel, const int *sel,
+                                  double *C      /* (n_sel cnp)^2 row-major, may not be NULL */,
+                                  double *cols   /* [n_sel cnp][nA]: row q = the column of S(mu)^-1 of chosen coordinate q, NOT scaled; may be NULL */,
+                                  int *iters     /* [n_sel cnp], may be NULL */,
+                                  double *relres /* [n_sel cnp], may be NULL */);
+/* mirror verb of the product kernel of psba_sparse_camera_covariance: Y = S X for n_panels panels [nA][16] (column
+ * n of panel m at X[(m nA + r) 16 + n]), in the state of psba_sparse_S_times.  A panel's result does not depend on its
+ * position. */
+int psba_sparse_S_times_many(psba_handle h, int n_panels, const double *X /* [n_panels][nA][16] */, double *Y);
 /* The verbs that work on the dense reduce buffer or the Cholesky chain -- psba_SPDinv_matVec,
  * psba_get_reduce_buffer, psba_set_reduce_buffer, psba_chol_dist_begin / _superpanel / _block / _finish,
  * psba_get_cholmod_factor, psba_covariance_compute -- return PSBA_E_STATE under PSBA_SOLVER_PCG before they copy or

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["psba_api.cpp", "problem_options.cpp", "covariance.cpp", "schur_plan.cpp", "lm_loop.cpp", "tr_loop.cpp", "sba_io.cpp", "kernels_linearize.hip",
            "kernels_tr.hip",
-           "kernels_schur.hip", "kernels_free.hip", "kernels_free_pcg.hip", "blockprod_plan.cpp", "kernels_chol.hip", "kernels_pcg.hip", "kernels_chol_graph.hip", "kernels_backsub.hip",
+           "kernels_schur.hip", "kernels_free.hip", "kernels_free_pcg.hip", "kernels_free_pcg_many.hip", "blockprod_plan.cpp", "kernels_chol.hip", "kernels_pcg.hip", "kernels_chol_graph.hip", "kernels_backsub.hip",
            "kernels_cov.hip"]
 # PSBA_BUILD_EXPERIMENTS=1: also the rejected experiments (round 3's K2 ring route) and their test hooks
 EXPERIMENTS = bool(os.environ.get("PSBA_BUILD_EXPERIMENTS"))
@@ -18,6 +18,9 @@ HEADERS = ["psba_internal.h", "api_common.h", "dev_buf.h", "camera_model.h", "fr
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-result", "-x", "hip"] + (["-DPSBA_BUILD_EXPERIMENTS"] if EXPERIMENTS else [])
+
+# per-file flags: the multi-column kernels may not use scratch, so their build prints registers, LDS and scratch per kernel
+EXTRA = {"kernels_free_pcg_many.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 
 
 def _stale(obj, deps):
@@ -38,7 +41,7 @@ def build(force=False, verbose=False):
         obj = os.path.join(objdir, s + ".o")
         objs.append(obj)
         if force or _stale(obj, [src] + hdrs):
-            cmd = [hipcc] + FLAGS + ["-c", src, "-o", obj]
+            cmd = [hipcc] + FLAGS + EXTRA.get(s, []) + ["-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.check_call(cmd)

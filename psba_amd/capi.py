@@ -153,6 +153,8 @@ SIGNATURES = [
     ("psba_get_sparse_S", C.c_int, [_h, _ip, _dp, _dp]),
     ("psba_set_sparse_S", C.c_int, [_h, _dp, _dp]),
     ("psba_sparse_S_times", C.c_int, [_h, _dp, _dp]),
+    ("psba_sparse_S_times_many", C.c_int, [_h, C.c_int, _dp, _dp]),
+    ("psba_sparse_camera_covariance", C.c_int, [_h, C.c_double, C.c_double, C.c_int, C.c_int, _ip, _dp, _dp, _ip, _dp]),
     ("psba_sparse_pattern", C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.POINTER(C.c_ubyte)]),
     ("psba_set_sparse_pattern", C.c_int, [_h, C.POINTER(C.c_ubyte), C.c_longlong]),
     ("psba_set_camera_model", C.c_int, [_h, C.c_int]),
@@ -934,6 +936,36 @@ class Psba:
         y = np.empty(n)
         self._ck(lib.psba_sparse_S_times(self._h, _d(x), _d(y)))
         return y
+
+    def sparse_S_times_many(self, X):
+        """psba_sparse_S_times_many: Y = S X for panels X [n_panels, nA, 16], by the product kernel of
+        sparse_camera_covariance."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        n = self._sizes()[1]
+        if X.ndim != 3 or X.shape[1:] != (n, 16):
+            raise PsbaError(-1, f"sparse_S_times_many: X is {X.shape}, not [panels, {n}, 16]")
+        Y = np.empty_like(X)
+        self._ck(lib.psba_sparse_S_times_many(self._h, X.shape[0], _d(X), _d(Y)))
+        return Y
+
+    def sparse_camera_covariance(self, sel, mu=0.0, scale=1.0, reassemble=True, want_cols=False):
+        """psba_sparse_camera_covariance: (C, info) -- C [n cnp, n cnp] = scale (S(mu)^-1)[sel, sel], the joint covariance
+        of the chosen cameras under SOLVER_SPARSE on blocks of 11 / 16; info = dict(status (PSBA_OK, PSBA_NOT_SPD or
+        PSBA_PCG_MAXIT), iters [n cnp], relres [n cnp] and, with want_cols, cols [n cnp, nA]: the solved columns, not
+        scaled).  Raises on errors."""
+        sel = np.ascontiguousarray(np.asarray(sel).reshape(-1), dtype=np.int32)
+        cnp, nA, _ = self._sizes()
+        m = max(cnp * sel.size, 1)
+        Cm = np.zeros((m, m))
+        iters = np.zeros(m, dtype=np.int32)
+        relres = np.zeros(m)
+        cols = np.zeros((m, nA)) if want_cols else None
+        rc = self._ck(lib.psba_sparse_camera_covariance(self._h, float(mu), float(scale), int(bool(reassemble)), int(sel.size),
+                                                        _i(sel), _d(Cm), _d(cols), _i(iters), _d(relres)))
+        info = dict(status=rc, iters=iters, relres=relres)
+        if want_cols:
+            info["cols"] = cols
+        return Cm, info
 
     def set_sparse_pattern(self, flags):
         flags = np.ascontiguousarray(flags, dtype=np.uint8)

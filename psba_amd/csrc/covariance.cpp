@@ -210,6 +210,59 @@ int psba_get_free_sigmas(psba_handle h, double *sigma) {
   return rc;
 }
 
+// ---- chosen cameras under PSBA_SOLVER_SPARSE (kernels_free_pcg_many.hip) ----
+
+// what both verbs of the sparse route open with: an uploaded problem, no try in flight, a FREE_SPARSE handle
+static int need_free_sparse(psba_ctx *h, const char *verb) {
+  NEED_V(h, verb, h->uploaded, "no problem uploaded");
+  NEED_V(h, verb, !h->backsub_pending, "a damping try is in flight (psba_backsub_wait first)");
+  NEED_V(h, verb, h->cnp != 6,
+         "PSBA_SOLVER_SPARSE on free-intrinsics camera blocks only (six-parameter blocks: psba_covariance_compute)");
+  NEED_V(h, verb, FREE_SPARSE(h),
+         "PSBA_SOLVER_SPARSE only (psba_set_solver before the upload); the dense solver: psba_free_covariance_compute");
+  return PSBA_OK;
+}
+
+int psba_sparse_camera_covariance(psba_handle h, double mu, double scale, int reassemble, int n_sel, const int *sel, double *C,
+                                  double *cols, int *iters, double *relres) {
+  CHECK_H(h);
+  TRY(need_free_sparse(h, __func__));
+  if (!(std::isfinite(mu) && mu >= 0.0)) return fail(h, PSBA_E_INVALID, "%s: mu must be finite and >= 0 (got %.17g)", __func__, mu);
+  if (!(std::isfinite(scale) && scale > 0.0))
+    return fail(h, PSBA_E_INVALID, "%s: scale must be finite and > 0 (got %.17g)", __func__, scale);
+  if (n_sel < 1 || !sel) return fail(h, PSBA_E_INVALID, "%s: n_sel = %d (at least one chosen camera, and its list)", __func__, n_sel);
+  if (!C) return fail(h, PSBA_E_INVALID, "%s: C is a null pointer", __func__);
+  {
+    std::vector<int> at((size_t)h->d.nC, -1);
+    for (int a = 0; a < n_sel; a++) {
+      if (sel[a] < 0 || sel[a] >= h->d.nC)
+        return fail(h, PSBA_E_INVALID, "%s: sel[%d] = %d names a camera out of range (%d cameras)", __func__, a, sel[a], h->d.nC);
+      if (at[(size_t)sel[a]] >= 0)
+        return fail(h, PSBA_E_INVALID, "%s: camera %d is listed twice (sel[%d] and sel[%d])", __func__, sel[a], at[(size_t)sel[a]], a);
+      at[(size_t)sel[a]] = a;
+    }
+  }
+  if (!reassemble) NEED(h, h->assembled, "reassemble = 0 works on the blocks as they stand (psba_schur_assemble first)");
+  if (reassemble) {
+    if (!(h->linearized && h->coeff == 1.0 && h->coeff_g == 1.0)) TRY(psba_linearize(h, 1.0, 1.0));
+    TRY(psba_schur_assemble(h, mu));
+  }
+  const int rc = launch_fcovm_compute(h, scale, n_sel, sel, C, cols, iters, relres);
+  if (rc == PSBA_NOT_SPD)
+    h->err = std::string(__func__) + ": S is not positive definite on a chosen column (a pivot of a diagonal block, p.Sp <= 0, or a residual that is not finite)";
+  else if (rc == PSBA_PCG_MAXIT)
+    h->err = std::string(__func__) + ": a column used up max_iter (iters and relres say which)";
+  return rc;
+}
+
+int psba_sparse_S_times_many(psba_handle h, int n_panels, const double *X, double *Y) {
+  CHECK_H(h);
+  TRY(need_free_sparse(h, __func__));
+  NEED(h, h->assembled, "psba_schur_assemble first (the state of psba_get_sparse_S)");
+  if (n_panels < 1 || !X || !Y) return fail(h, PSBA_E_INVALID, "%s: n_panels = %d, or a null pointer", __func__, n_panels);
+  return launch_fbsr_times_many(h, n_panels, X, Y);
+}
+
 // test hook (psba_hip.h): V_i as the linearization stored it (undamped) and Y as k_free_Y stored it for the last assemble
 int psba_get_free_point_blocks(psba_handle h, double *V, double *Y) {
   CHECK_H(h);

@@ -328,9 +328,6 @@ __global__ __launch_bounds__(256) void k_fpcg_direction(const double *z, double 
   for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) p[t] = z[t] + beta * p[t];
 }
 
-static int fpcg_vec_grid(int n) { return (n + 255) / 256 < FPCG_CAP ? (n + 255) / 256 : FPCG_CAP; }
-static int fpcg_row_grid(int nC) { return (nC + 3) / 4 < FPCG_CAP ? (nC + 3) / 4 : FPCG_CAP; }
-
 template <class T>
 static int fbsr_finalize(psba_ctx *h, double mu, const double *D) {
   const int nC = h->d.nC;
@@ -418,9 +415,23 @@ static int fpcg_solve(psba_ctx *h) {
   return PSBA_OK;
 }
 
+// the block inverses alone, for a caller with scalars and a status word of its own (kernels_free_pcg_many.hip): a bad
+// pivot sets pc[PF_FAIL] and status[1] = stamp
+template <class T>
+static int fbsr_diag_inverse(psba_ctx *h, double *minv, double *pc, int *status, int stamp) {
+  const int nC = h->d.nC;
+  hipLaunchKernelGGL(k_fbsr_diag_inverse<T>, dim3((nC + FINV_CAMS - 1) / FINV_CAMS), dim3(16 * FINV_CAMS), 0, h->stream,
+                     h->bs_val, h->bs_diag, minv, nC, pc, status, stamp);
+  PSBA_HIP(h, hipGetLastError());
+  return PSBA_OK;
+}
+
 #define FPCG_DISPATCH(fn, ...) (h->cnp == KD_CNP ? fn<FreeKD>(__VA_ARGS__) : fn<FreeK>(__VA_ARGS__))
 int launch_fbsr_finalize(psba_ctx *h, double mu, const double *D) { return FPCG_DISPATCH(fbsr_finalize, h, mu, D); }
 int launch_fbsr_times(psba_ctx *h, const double *x_host, double *y_host) { return FPCG_DISPATCH(fbsr_times, h, x_host, y_host); }
 int launch_fpcg_solve(psba_ctx *h) { return FPCG_DISPATCH(fpcg_solve, h); }
+int launch_fbsr_diag_inverse(psba_ctx *h, double *minv, double *pc, int *status, int stamp) {
+  return FPCG_DISPATCH(fbsr_diag_inverse, h, minv, pc, status, stamp);
+}
 
 }  // namespace psba

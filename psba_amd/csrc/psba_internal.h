@@ -168,6 +168,9 @@ struct BlockRowsHost {
 void build_block_rows(int nCams, const BlockProdPlanHost &plan, BlockRowsHost &out);  // blockprod_plan.cpp
 constexpr int FBSR_ADDED = 1 << 30;  // flag in bs_diag on this route
 constexpr int FPCG_CAP = 128;        // workgroups of the persistent grids = partial sums per inner product
+inline int fpcg_vec_grid(int n) { return (n + 255) / 256 < FPCG_CAP ? (n + 255) / 256 : FPCG_CAP; }  // by unknowns
+inline int fpcg_row_grid(int nC) { return (nC + 3) / 4 < FPCG_CAP ? (nC + 3) / 4 : FPCG_CAP; }       // by block rows, four a workgroup
+constexpr int FCOVM_PANELS = 8;      // panels of 16 columns of a batch of psba_sparse_camera_covariance (kernels_free_pcg_many.hip)
 constexpr int KD_UNIT = 64;        // observations of a camera unit on this route: one wave, one observation per lane
 constexpr int KD_SEG_DEFAULT = 64; // products per segment (PSBA_FKD_SEG overrides)
 constexpr int KD_RED = 4 * 520;    // doubles of the reduction scratch: camera terms | up to 512 workgroups x 4 sums
@@ -305,6 +308,13 @@ struct ProblemState {
   psba::DevBuf<double> pcg_vec;   // r | z | p | q, nA each
   psba::DevBuf<double> pcg_minv;  // [nC][cnp^2] inverses of the diagonal blocks
   psba::DevBuf<double> pcg_scal;  // device scalars (their pinned mirror pcg_host lives with the handle)
+  // psba_sparse_camera_covariance / psba_sparse_S_times_many (kernels_free_pcg_many.hip): buffers of their own,
+  // allocated at first use -- the solve's dp, pcg_vec and pcg_scal are not touched
+  psba::DevBuf<double> fcm_vec;   // [6][fcm_cap][nA][16] x | r | z | p | q | r's second buffer
+  int fcm_cap = 0;                // panels fcm_vec holds (<= FCOVM_PANELS)
+  psba::DevBuf<double> fcm_scal;  // [FCOVM_PANELS] scalar blocks of the panels | 16 doubles of k_fbsr_diag_inverse
+  psba::DevBuf<int> fcm_status;   // [4] the status words k_fbsr_diag_inverse reports into
+  psba::PinnedBuf<double> fcm_host;  // pinned mirror of the panels' scalars
   // K2 owner route (many cameras): see OwnerPlanHost
   psba::DevBuf<int2> own_prod;
   psba::DevBuf<psba::OwnerWave> own_waves;
@@ -531,6 +541,9 @@ int launch_bsr_times(psba_ctx *h, const double *x_host, double *y_host);
 int launch_fbsr_finalize(psba_ctx *h, double mu, const double *D);
 int launch_fpcg_solve(psba_ctx *h);
 int launch_fbsr_times(psba_ctx *h, const double *x_host, double *y_host);
+int launch_fbsr_diag_inverse(psba_ctx *h, double *minv, double *pc, int *status, int stamp);
+int launch_fbsr_times_many(psba_ctx *h, int n_panels, const double *X, double *Y);  // kernels_free_pcg_many.hip
+int launch_fcovm_compute(psba_ctx *h, double scale, int n_sel, const int *sel, double *C, double *cols, int *iters, double *relres);
 // kernels_chol_graph.hip
 int launch_chol_graph(psba_ctx *h);
 int chol_dist_shape(psba_ctx *h, int *NB, int *blocked);
