@@ -907,12 +907,51 @@ int psba_sparse_S_times(psba_handle h, const double *x, double *y);
  * PSBA_SOLVER_SPARSE on blocks of 11 / 16 (dense free-intrinsics handles: psba_free_covariance_compute; six-parameter
  * blocks: psba_covariance_compute); PSBA_E_INVALID for a mu that is not finite and >= 0, a scale that is not finite
  * and > 0, n_sel < 1, an index out of range or listed twice, C == NULL.  A refused call changes nothing.
- * Not here: point covariances, shared intrinsics, rank layouts. */
+ * Not here: shared intrinsics, rank layouts.  Point covariances: psba_sparse_point_covariance. */
 int psba_sparse_camera_covariance(psba_handle h, double mu, double scale, int reassemble, int n_sel, const int *sel,
                                   double *C      /* (n_sel cnp)^2 row-major, may not be NULL */,
                                   double *cols   /* [n_sel cnp][nA]: row q = the column of S(mu)^-1 of chosen coordinate q, NOT scaled; may be NULL */,
                                   int *iters     /* [n_sel cnp], may be NULL */,
                                   double *relres /* [n_sel cnp], may be NULL */);
+/* ---- covariance of chosen points under PSBA_SOLVER_SPARSE on camera blocks of 11 / 16 ----------------
+ * The other half of psba_sparse_camera_covariance: how well chosen 3-D points (control, check and tie points) are
+ * determined.  psba_get_free_point_covariance needs the dense inverse and keeps refusing a sparse handle.  Here three
+ * right-hand sides per point are solved, five points to a panel of 16 columns (kernels_free_pcg_points.hip).
+ *   * The linearization is psba_linearize(h, 1, 1) at the current parameters, as for psba_sparse_camera_covariance: the
+ *     mask, the per-camera masks, held poses and points, priors, observation weighting and the damping rule are in S, V
+ *     and Y.
+ *   * For a chosen point i and c < 3 the right-hand side b_{i,c} holds, in its rows of camera j in cams(i), column c of
+ *     Y_ij (cnp x 3, as k_free_Y stored it for this mu); every other row is +0.0.  The column x_{i,c} solves
+ *     S(mu) x = b_{i,c} by the route's conjugate gradients: block-Jacobi preconditioning, psba_set_solver's tol and
+ *     max_iter, the stop rule of psba_schur_solve on this route with r.r judged against this column's own b.b.
+ *   * Block (a, b) of the chosen list is scale [ delta_ab V*_a^-1 + sum_{j in cams(a)} Y_aj^T x_b[rows of j] ], the sum
+ *     in ascending j.  V*_i = V_i + mu D_i is rebuilt with the route's own damping (D = I, or Marquardt's diagonal of
+ *     psba_set_damping) and inverted by the closed form; |det| < 1e-16 gives PSBA_SINGULAR_V.
+ *   * Block (a, b) with position a >= b is taken from the columns solved for sel_pts[b] and written to both sides;
+ *     inside a diagonal block the lower triangle is the matrix.  So C is bit-symmetric.
+ *   * A held point: nothing is solved; its rows and columns of C and its rows of cols are exactly +0.0, its iters 0 and
+ *     its relres 0.  A point without observations, and one whose blocks Y are all zero: b = 0, the columns start stopped
+ *     with x = 0 (iters 0, relres 0) and the diagonal block is scale V*^-1.
+ *   * Masked and held-pose coordinates need no case of their own: their rows of W, and hence of Y, are +0.0 by
+ *     construction, so b, every iterate and cols are zero there (cols: +0.0).
+ *   * C = scale (...); cols is not scaled.
+ *   * mu = 0 needs a gauge, held poses or priors; mu > 0 gives a regularised inverse and NOT a covariance.
+ * Columns are independent: a column's bits, iteration count and relres depend on none of: which other points are
+ * chosen, their order, the column's position in its panel, the batch (at most 8 panels = 40 points at a time); two calls
+ * on the same state return the same bits.
+ * State, arguments and reassemble are those of psba_sparse_camera_covariance; with reassemble == 0, mu must be the mu of
+ * the psba_schur_assemble whose blocks, V and Y stand (it rebuilds V*).  The verb uses that verb's panel buffers and
+ * touches none of dp, the solver's vectors and scalars or the try's status words: a later psba_schur_solve, psba_backsub
+ * or psba_levmar runs as on a handle that never called it.  Returns PSBA_OK, PSBA_NOT_SPD, PSBA_SINGULAR_V (a chosen
+ * V*_i) or PSBA_PCG_MAXIT (some column used up max_iter: iters and relres say which; C is still written), and
+ * synchronises.  PSBA_E_STATE as there; PSBA_E_INVALID for a mu that is not finite and >= 0, a scale that is not finite
+ * and > 0, n_sel < 1, a point out of range or listed twice, C == NULL.  A refused call changes nothing.
+ * Not here: the camera-point cross blocks C_ab, all points at once, shared intrinsics, rank layouts. */
+int psba_sparse_point_covariance(psba_handle h, double mu, double scale, int reassemble, int n_sel, const int *sel_pts,
+                                 double *C      /* (3 n_sel)^2 row-major, may not be NULL */,
+                                 double *cols   /* [3 n_sel][nA]: row 3 a + c = x_{sel_pts[a], c}, NOT scaled; may be NULL */,
+                                 int *iters     /* [3 n_sel], may be NULL */,
+                                 double *relres /* [3 n_sel], may be NULL */);
 /* mirror verb of the product kernel of psba_sparse_camera_covariance: Y = S X for n_panels panels [nA][16] (column
  * n of panel m at X[(m nA + r) 16 + n]), in the state of psba_sparse_S_times.  A panel's result does not depend on its
  * position. */

@@ -155,6 +155,7 @@ SIGNATURES = [
     ("psba_sparse_S_times", C.c_int, [_h, _dp, _dp]),
     ("psba_sparse_S_times_many", C.c_int, [_h, C.c_int, _dp, _dp]),
     ("psba_sparse_camera_covariance", C.c_int, [_h, C.c_double, C.c_double, C.c_int, C.c_int, _ip, _dp, _dp, _ip, _dp]),
+    ("psba_sparse_point_covariance", C.c_int, [_h, C.c_double, C.c_double, C.c_int, C.c_int, _ip, _dp, _dp, _ip, _dp]),
     ("psba_sparse_pattern", C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.POINTER(C.c_ubyte)]),
     ("psba_set_sparse_pattern", C.c_int, [_h, C.POINTER(C.c_ubyte), C.c_longlong]),
     ("psba_set_camera_model", C.c_int, [_h, C.c_int]),
@@ -962,6 +963,25 @@ class Psba:
         cols = np.zeros((m, nA)) if want_cols else None
         rc = self._ck(lib.psba_sparse_camera_covariance(self._h, float(mu), float(scale), int(bool(reassemble)), int(sel.size),
                                                         _i(sel), _d(Cm), _d(cols), _i(iters), _d(relres)))
+        info = dict(status=rc, iters=iters, relres=relres)
+        if want_cols:
+            info["cols"] = cols
+        return Cm, info
+
+    def sparse_point_covariance(self, sel, mu=0.0, scale=1.0, reassemble=True, want_cols=False):
+        """psba_sparse_point_covariance: (C, info) -- C [3 n, 3 n], the joint covariance of the chosen points under
+        SOLVER_SPARSE on blocks of 11 / 16: block (a, b) = scale (delta_ab V*_a^-1 + Y_a^T S(mu)^-1 Y_b); info =
+        dict(status (PSBA_OK, PSBA_NOT_SPD, PSBA_SINGULAR_V or PSBA_PCG_MAXIT), iters [3 n], relres [3 n] and, with
+        want_cols, cols [3 n, nA]: the solved columns S(mu)^-1 Y_b, not scaled).  Raises on errors."""
+        sel = np.ascontiguousarray(np.asarray(sel).reshape(-1), dtype=np.int32)
+        nA = self._sizes()[1]
+        m = max(3 * sel.size, 1)
+        Cm = np.zeros((m, m))
+        iters = np.zeros(m, dtype=np.int32)
+        relres = np.zeros(m)
+        cols = np.zeros((m, nA)) if want_cols else None
+        rc = self._ck(lib.psba_sparse_point_covariance(self._h, float(mu), float(scale), int(bool(reassemble)), int(sel.size),
+                                                       _i(sel), _d(Cm), _d(cols), _i(iters), _d(relres)))
         info = dict(status=rc, iters=iters, relres=relres)
         if want_cols:
             info["cols"] = cols

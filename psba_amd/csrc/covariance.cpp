@@ -263,6 +263,43 @@ int psba_sparse_S_times_many(psba_handle h, int n_panels, const double *X, doubl
   return launch_fbsr_times_many(h, n_panels, X, Y);
 }
 
+// ---- chosen points under PSBA_SOLVER_SPARSE (kernels_free_pcg_points.hip) ----
+
+int psba_sparse_point_covariance(psba_handle h, double mu, double scale, int reassemble, int n_sel, const int *sel_pts, double *C,
+                                 double *cols, int *iters, double *relres) {
+  CHECK_H(h);
+  TRY(need_free_sparse(h, __func__));
+  if (!(std::isfinite(mu) && mu >= 0.0)) return fail(h, PSBA_E_INVALID, "%s: mu must be finite and >= 0 (got %.17g)", __func__, mu);
+  if (!(std::isfinite(scale) && scale > 0.0))
+    return fail(h, PSBA_E_INVALID, "%s: scale must be finite and > 0 (got %.17g)", __func__, scale);
+  if (n_sel < 1 || !sel_pts) return fail(h, PSBA_E_INVALID, "%s: n_sel = %d (at least one chosen point, and its list)", __func__, n_sel);
+  if (!C) return fail(h, PSBA_E_INVALID, "%s: C is a null pointer", __func__);
+  {
+    std::vector<int> at((size_t)h->d.nP, -1);
+    for (int a = 0; a < n_sel; a++) {
+      if (sel_pts[a] < 0 || sel_pts[a] >= h->d.nP)
+        return fail(h, PSBA_E_INVALID, "%s: sel_pts[%d] = %d names a point out of range (%d points)", __func__, a, sel_pts[a], h->d.nP);
+      if (at[(size_t)sel_pts[a]] >= 0)
+        return fail(h, PSBA_E_INVALID, "%s: point %d is listed twice (sel_pts[%d] and sel_pts[%d])", __func__, sel_pts[a],
+                    at[(size_t)sel_pts[a]], a);
+      at[(size_t)sel_pts[a]] = a;
+    }
+  }
+  if (!reassemble) NEED(h, h->assembled, "reassemble = 0 works on the blocks, V and Y as they stand (psba_schur_assemble first)");
+  if (reassemble) {
+    if (!(h->linearized && h->coeff == 1.0 && h->coeff_g == 1.0)) TRY(psba_linearize(h, 1.0, 1.0));
+    TRY(psba_schur_assemble(h, mu));
+  }
+  const int rc = launch_fcovp_compute(h, mu, scale, n_sel, sel_pts, C, cols, iters, relres);
+  if (rc == PSBA_NOT_SPD)
+    h->err = std::string(__func__) + ": S is not positive definite on a chosen column (a pivot of a diagonal block, p.Sp <= 0, or a residual that is not finite)";
+  else if (rc == PSBA_SINGULAR_V)
+    h->err = std::string(__func__) + ": some chosen V_i + mu D_i is singular (D = I unless psba_set_damping chose Marquardt's rule)";
+  else if (rc == PSBA_PCG_MAXIT)
+    h->err = std::string(__func__) + ": a column used up max_iter (iters and relres say which)";
+  return rc;
+}
+
 // test hook (psba_hip.h): V_i as the linearization stored it (undamped) and Y as k_free_Y stored it for the last assemble
 int psba_get_free_point_blocks(psba_handle h, double *V, double *Y) {
   CHECK_H(h);

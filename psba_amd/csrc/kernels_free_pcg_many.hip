@@ -26,15 +26,10 @@
 
 #include "api_common.h"
 #include "free_blocks.h"
+#include "free_pcg_many.h"
 
 namespace psba {
 
-// the scalar block of one panel (doubles, device): sixteen of each of k_fpcg's scalars, one per column, then the partial
-// sums [slot][workgroup][16].  p.Sp, r.r and r.z of iteration `it` live in slot it % 4 (r.z of the next iteration in
-// slot (it + 1) % 4), as in kernels_free_pcg.hip.  The right-hand sides are unit vectors, so b.b (1) and the first r.z
-// (the diagonal entry of the block inverse) are written by the start kernel itself
-enum { MF_BB = 0, MF_FAIL = 16, MF_DONE = 32, MF_RRFIN = 48, MF_DEAD = 64, MF_ACT = 80, MF_RR = 96, MF_RZ = 160, MF_N = 224,
-       MF_PQP = MF_N, MF_RRP = MF_N + 64 * FPCG_CAP, MF_RZP = MF_N + 128 * FPCG_CAP, MF_ALL = MF_N + 192 * FPCG_CAP };
 constexpr int FSPMM_TRIP = 4;  // entries of a row whose loads are in flight together (k_fpcgm_spmm)
 
 template <class T>
@@ -42,26 +37,6 @@ __device__ __forceinline__ bool fcm_live(unsigned mask, const unsigned short *cm
   return k < T::NI ? ((kd_free_bits(mask, cmask, j) >> k) & 1u) != 0 : !(held && held[j]);
 }
 
-// the workgroup's 256 values are 16 strands (threadIdx.x >> 4) of 16 columns (threadIdx.x & 15): sOut[col] = the
-// strands' sum in ascending order
-__device__ __forceinline__ void fpcgm_block_sums(double v, double *sW, double *sOut) {
-  sW[threadIdx.x] = v;
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    double s = 0.0;
-#pragma unroll
-    for (int g = 0; g < 16; g++) s += sW[16 * g + threadIdx.x];
-    sOut[threadIdx.x] = s;
-  }
-  __syncthreads();
-}
-// the sums of n <= FPCG_CAP partials [n][16]: strand g adds the partials g, g + 16, ... of its column in ascending
-// order.  Every workgroup that calls this gets the same bits
-__device__ __forceinline__ void fpcgm_sum_partials(const double *part, int n, double *sW, double *sOut) {
-  double v = 0.0;
-  for (int i = threadIdx.x >> 4; i < n; i += 16) v += part[16 * i + (threadIdx.x & 15)];
-  fpcgm_block_sums(v, sW, sOut);
-}
 __device__ __forceinline__ bool fpcgm_converged_before(const double *pc, int col, int it, double rz, double bb, double tol2) {
   if (rz == 0.0) return true;
   return it > 0 && pc[MF_RR + 16 * ((it - 1) & 3) + col] <= tol2 * bb;
@@ -299,11 +274,11 @@ __global__ __launch_bounds__(256) void k_fcovm_gather(const double *x_all, size_
 // ---- host side ----
 
 // the vector kernels' grid: a panel has 16 nA entries; at most FPCG_CAP workgroups, a function of nA alone
-static int fcm_vec_grid(int n) { return ((size_t)16 * n + 255) / 256 < (size_t)FPCG_CAP ? (int)(((size_t)16 * n + 255) / 256) : FPCG_CAP; }
+int fcm_vec_grid(int n) { return ((size_t)16 * n + 255) / 256 < (size_t)FPCG_CAP ? (int)(((size_t)16 * n + 255) / 256) : FPCG_CAP; }
 
 // the verb's own buffers: six vectors [panels][nA][16] (x, r, z, p, q and r's second buffer), the panels' scalar blocks
 // and the small block the inverse kernel reports into; allocated at first use, dropped with the problem
-static int fcm_buffers(psba_ctx *h, int panels) {
+int fcm_buffers(psba_ctx *h, int panels) {
   if (h->fcm_cap < panels) {
     h->fcm_cap = 0;
     TRY(h->fcm_vec.alloc(h, (size_t)6 * panels * 16 * h->d.nA));
@@ -446,6 +421,27 @@ static int fcm_compute(psba_ctx *h, double scale, int n_sel, const int *sel, dou
   return not_spd ? PSBA_NOT_SPD : exhausted ? PSBA_PCG_MAXIT : PSBA_OK;
 }
 
+// for kernels_free_pcg_points.hip (free_pcg_many.h): iterations it0 .. it0 + burst - 1 on the first np panels of the
+// verbs' buffers, launched exactly as fcm_compute launches them
+template <class T>
+static int fcm_burst(psba_ctx *h, int np, int it0, int burst) {
+  const int n = h->d.nA, nC = h->d.nC, g = fcm_vec_grid(n), gs = fpcg_row_grid(nC);
+  const size_t vs = (size_t)16 * n, vc = vs * h->fcm_cap;
+  hipStream_t s = h->stream;
+  double *x = h->fcm_vec, *r0 = x + vc, *z = r0 + vc, *p = z + vc, *q = p + vc, *r1 = q + vc, *pc = h->fcm_scal;
+  const double tol2 = h->pcg_tol * h->pcg_tol;
+  for (int it = it0; it < it0 + burst; it++) {
+    double *rc = (it & 1) ? r1 : r0, *rn = (it & 1) ? r0 : r1;
+    hipLaunchKernelGGL(k_fpcgm_spmm<T>, dim3(gs, np), dim3(256), 0, s, h->bs_val, h->bs_rowptr, h->bs_rowent, nC, p, q, pc,
+                       it & 3, vs, 1);
+    hipLaunchKernelGGL(k_fpcgm_update<T>, dim3(g, np), dim3(256), 0, s, x, rc, rn, p, q, h->pcg_minv.get(), z, n, pc, it, gs,
+                       tol2, vs);
+    hipLaunchKernelGGL(k_fpcgm_direction, dim3(g, np), dim3(256), 0, s, z, p, n, pc, it, tol2, vs);
+  }
+  PSBA_HIP(h, hipGetLastError());
+  return PSBA_OK;
+}
+
 #define FPCGM_DISPATCH(fn, ...) (h->cnp == KD_CNP ? fn<FreeKD>(__VA_ARGS__) : fn<FreeK>(__VA_ARGS__))
 int launch_fbsr_times_many(psba_ctx *h, int n_panels, const double *X, double *Y) {
   return FPCGM_DISPATCH(fbsr_times_many, h, n_panels, X, Y);
@@ -453,5 +449,7 @@ int launch_fbsr_times_many(psba_ctx *h, int n_panels, const double *X, double *Y
 int launch_fcovm_compute(psba_ctx *h, double scale, int n_sel, const int *sel, double *C, double *cols, int *iters, double *relres) {
   return FPCGM_DISPATCH(fcm_compute, h, scale, n_sel, sel, C, cols, iters, relres);
 }
+
+int launch_fpcgm_burst(psba_ctx *h, int np, int it0, int burst) { return FPCGM_DISPATCH(fcm_burst, h, np, it0, burst); }
 
 }  // namespace psba

@@ -544,6 +544,8 @@ int launch_fbsr_times(psba_ctx *h, const double *x_host, double *y_host);
 int launch_fbsr_diag_inverse(psba_ctx *h, double *minv, double *pc, int *status, int stamp);
 int launch_fbsr_times_many(psba_ctx *h, int n_panels, const double *X, double *Y);  // kernels_free_pcg_many.hip
 int launch_fcovm_compute(psba_ctx *h, double scale, int n_sel, const int *sel, double *C, double *cols, int *iters, double *relres);
+int launch_fcovp_compute(psba_ctx *h, double mu, double scale, int n_sel, const int *sel, double *C, double *cols, int *iters,
+                         double *relres);  // kernels_free_pcg_points.hip
 // kernels_chol_graph.hip
 int launch_chol_graph(psba_ctx *h);
 int chol_dist_shape(psba_ctx *h, int *NB, int *blocked);
