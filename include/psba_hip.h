@@ -585,6 +585,26 @@ int psba_backsub_wait(psba_handle h, psba_try_scalars *out);
 /* update_p (PSBA/sba_func.h:138): the proposed parameters become current (pointer swap) */
 int psba_accept(psba_handle h);
 
+/* ---- how a try's scalars reach the host, and hooks to test it (psba_amd/csrc/scal_publish.h states the format) ----
+ * The device publishes a block of 104 words (doubles), a stamp and a check word over both into pinned memory;
+ * psba_backsub_wait copies the 106 words and accepts the copy iff it carries the wanted stamp and its own check.
+ * Everything is decided on bit patterns: NaN payloads and the sign of a zero count.
+ * psba_scal_block_check: *check = the check word (its bits, in a double) of block[104] under the stamp.
+ * psba_scal_block_take: the host's take applied to caller memory, words[106] = block, stamp, check; out[104] receives
+ * the private copy of the block; returns 1 accepted, 0 refused.  Neither needs a handle or a GPU. */
+int psba_scal_block_check(const double *block, double stamp, double *check);
+int psba_scal_block_take(const double *words, double want_stamp, double *out);
+/* Since psba_create: *takes = blocks psba_backsub_wait accepted from a linearization queued ahead (one rank, the
+ * default route; a try whose scalars travel behind an event is not counted), *torn = tries among them in which a
+ * reading carried the wanted stamp over a block that failed its check, and was read again. */
+int psba_publish_stats(psba_handle h, long long *takes, long long *torn);
+/* Test hook: one workgroup of threads = 64, 128 or 256 runs nothing but the publishing prologue of the linearization
+ * kernels with the next stamp, the stream is waited for and raw[106] receives the pinned words: block, stamp, check.
+ * block[104] stands in the device scalar block for that launch (the device's own block is put back behind it); NULL
+ * publishes the device's block as it is, which is how a test reads it.  PSBA_E_STATE while a try is in flight; the
+ * try's result is dropped (psba_accept needs a new try). */
+int psba_test_publish(psba_handle h, const double *block, int threads, double *raw);
+
 /* ---- 1:1 mirror of sba_func.h for per-kernel parity tests -----------------------------
  * Same names and argument meaning as the reference; the dimension arguments and
  * PSBA_structPtr collapse into the handle.  A NULL host pointer means "stay on device"

@@ -14,7 +14,7 @@ EXPERIMENTS = bool(os.environ.get("PSBA_BUILD_EXPERIMENTS"))
 if EXPERIMENTS:
     SOURCES += ["kernels_schur_ring.hip", "schur_ring_plan.cpp", "kernels_schur_modes.hip"]
 OUT = os.path.join(HERE, "libpsba_hip_exp.so" if EXPERIMENTS else "libpsba_hip.so")
-HEADERS = ["psba_internal.h", "api_common.h", "dev_buf.h", "camera_model.h", "free_blocks.h", "free_pcg_many.h", "chol_factor32.h", "schur_common.h", "schur_lds_args.h", os.path.join("..", "..", "include", "psba_hip.h")]
+HEADERS = ["psba_internal.h", "api_common.h", "dev_buf.h", "camera_model.h", "free_blocks.h", "free_pcg_many.h", "chol_factor32.h", "schur_common.h", "schur_lds_args.h", "scal_publish.h", os.path.join("..", "..", "include", "psba_hip.h")]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-result", "-x", "hip"] + (["-DPSBA_BUILD_EXPERIMENTS"] if EXPERIMENTS else [])

@@ -100,6 +100,10 @@ SIGNATURES = [
     ("psba_linearize_ahead", C.c_int, [_h]),
     ("psba_backsub_wait", C.c_int, [_h, C.POINTER(TryScalars)]),
     ("psba_accept", C.c_int, [_h]),
+    ("psba_scal_block_check", C.c_int, [_dp, C.c_double, _dp]),
+    ("psba_scal_block_take", C.c_int, [_dp, C.c_double, _dp]),
+    ("psba_publish_stats", C.c_int, [_h, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    ("psba_test_publish", C.c_int, [_h, _dp, C.c_int, _dp]),
     ("psba_compute_exQT", C.c_int, [_h, C.c_int, _dp]),
     ("psba_compute_jacobiQT", C.c_int, [_h, _dp, _dp]),
     ("psba_compute_U", C.c_int, [_h, C.c_double, _dp]),
@@ -433,6 +437,31 @@ def chol_dist_exchange_plan(n32, NB, nranks, JE):
     if n < 0:
         raise PsbaError(n, "psba_chol_dist_exchange_plan failed")
     return [tuple(int(v) for v in row) for row in out[:n]]
+
+
+SCAL_WORDS, SCAL_RAW = 104, 106  # the try's scalar block; with its stamp and check word (csrc/scal_publish.h)
+
+
+def scal_block_check(block, stamp):
+    """psba_scal_block_check (host only): the check word, as uint64, of a block of 104 words (float64 or uint64: bit
+    patterns) under the stamp `stamp`."""
+    b = np.ascontiguousarray(block).view(np.float64).reshape(SCAL_WORDS)
+    out = np.zeros(1)
+    rc = lib.psba_scal_block_check(_d(b), float(stamp), _d(out))
+    if rc < 0:
+        raise PsbaError(rc, "psba_scal_block_check failed")
+    return out.view(np.uint64)[0]
+
+
+def scal_block_take(raw, want_stamp):
+    """psba_scal_block_take (host only): (accepted, block) for the 106 raw words `raw` (block, stamp, check; float64 or
+    uint64), as psba_backsub_wait takes them from pinned memory; block: the 104 words of the private copy, uint64."""
+    r = np.ascontiguousarray(raw).view(np.float64).reshape(SCAL_RAW)
+    out = np.zeros(SCAL_WORDS)
+    rc = lib.psba_scal_block_take(_d(r), float(want_stamp), _d(out))
+    if rc < 0:
+        raise PsbaError(rc, "psba_scal_block_take failed")
+    return bool(rc), out.view(np.uint64)
 
 
 def ring_plan(n_cams, n_pts, iidx, jidx):
@@ -826,6 +855,22 @@ class Psba:
 
     def accept(self):
         self._ck(lib.psba_accept(self._h))
+
+    def publish_stats(self):
+        """(takes, torn) since the handle was created: scalar blocks backsub_wait accepted from a linearization queued
+        ahead, and tries among them that met a torn reading first (psba_publish_stats)."""
+        a, b = C.c_longlong(), C.c_longlong()
+        self._ck(lib.psba_publish_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def test_publish(self, block=None, threads=128):
+        """Test hook: the publishing prologue alone in one workgroup of `threads`; the 106 raw pinned words (block,
+        stamp, check) as uint64.  block: 104 words (float64 or uint64) that stand in the device scalar block for the
+        launch; None: the device's block as it is (psba_test_publish)."""
+        b = None if block is None else np.ascontiguousarray(block).view(np.float64).reshape(SCAL_WORDS)
+        raw = np.zeros(SCAL_RAW)
+        self._ck(lib.psba_test_publish(self._h, _d(b), int(threads), _d(raw)))
+        return raw.view(np.uint64)
 
     # ---- sba_func.h mirror ----
     def _out(self, fn, n, *pre):

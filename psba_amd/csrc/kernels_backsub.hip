@@ -332,12 +332,27 @@ __global__ __launch_bounds__(TILE_OBS) void k_backsub_long(BackArgs p, const int
 
 // the try's scalar block into pinned host memory: one small kernel instead of the runtime's
 // 768-byte device-to-host copy (3.9 us on the stream in front of the linearization queued ahead)
-__global__ __launch_bounds__(128) void k_publish_scal(const double *scal, double *host) {
-  if (threadIdx.x < NSCAL) host[threadIdx.x] = scal[threadIdx.x];
+// (the block, a fresh stamp and the check word, as the linearization queued ahead writes them: scal_publish.h -- the
+// host waits for this route's event and does not need them, but the pinned block has one format)
+__global__ __launch_bounds__(128) void k_publish_scal(const double *scal, double *host, double stamp) {
+  scal_publish(scal, host, stamp);
 }
 
 int launch_publish_scal(psba_ctx *h, hipStream_t s) {
-  hipLaunchKernelGGL(k_publish_scal, dim3(1), dim3(128), 0, s, h->scal, h->h_scal_dev);
+  h->pub_seq += 1.0;
+  hipLaunchKernelGGL(k_publish_scal, dim3(1), dim3(128), 0, s, h->scal, h->h_scal_dev, h->pub_seq);
+  PSBA_HIP(h, hipGetLastError());
+  return PSBA_OK;
+}
+
+// psba_test_publish: nothing but the shared prologue, in a workgroup of 64, 128 or 256 threads
+__global__ __launch_bounds__(256) void k_test_publish(const double *scal, double *host, double stamp) {
+  scal_publish(scal, host, stamp);
+}
+
+int launch_test_publish(psba_ctx *h, int threads) {
+  h->pub_seq += 1.0;
+  hipLaunchKernelGGL(k_test_publish, dim3(1), dim3(threads), 0, h->stream, h->scal, h->h_scal_dev, h->pub_seq);
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }

@@ -145,12 +145,7 @@ __global__ __launch_bounds__(64) void k_free_linearize(FreeArgs p) {
   constexpr int CNP = T::CNP, ROW = 2 * CNP + 3;
   __shared__ double sJ[KD_UNIT][ROW];
   const int lane = threadIdx.x;
-  if (p.pub_dst && blockIdx.x == 0) {
-    for (int t = lane; t < NSCAL; t += 64) p.pub_dst[t] = p.pub_src[t];
-    __threadfence_system();
-    __syncthreads();
-    if (lane == 0) p.pub_dst[NSCAL] = p.pub_stamp;
-  }
+  if (p.pub_dst && blockIdx.x == 0) scal_publish(p.pub_src, p.pub_dst, p.pub_stamp);
   const int4 u = p.cam_units[blockIdx.x];
   const int n = u.z - u.y;
   const unsigned mask = kd_free_bits(p.mask, p.cmask, u.x);  // (the unit's camera: one load per wave, none without a table)

@@ -49,13 +49,8 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize(LinArgs p, RobustLoss rl
   __shared__ double sW[(TILE_OBS / 2) * 19];  // W blocks of half a tile (staged in two halves: LDS for three workgroups per CU)
   extern __shared__ double sAcc[];     // [nC][27]
   const int tid = threadIdx.x;
-  if (p.pub_dst && blockIdx.x == 0) {
-    // (a kernel of its own for these 832 bytes sat 4 us on the stream between K3 and this kernel)
-    if (tid < NSCAL) p.pub_dst[tid] = p.pub_src[tid];
-    __threadfence_system();
-    __syncthreads();
-    if (tid == 0) p.pub_dst[NSCAL] = p.pub_stamp;
-  }
+  // (a kernel of its own for these 832 bytes sat 4 us on the stream between K3 and this kernel)
+  if (p.pub_dst && blockIdx.x == 0) scal_publish(p.pub_src, p.pub_dst, p.pub_stamp);
   const int nAcc = GACC ? 0 : p.nC * CAM_ACC;
   for (int t = tid; t < nAcc; t += TILE_OBS) sAcc[t] = 0.0;
   __syncthreads();
@@ -222,12 +217,7 @@ __global__ __launch_bounds__(TILE_OBS) void k_linearize2(LinArgs p, RobustLoss r
   __shared__ int sCarP[TILE_OBS / 64][3];       // point of the wave's first lane, of its last lane, whole wave one point?
   extern __shared__ double sAcc[];              // [nC][27]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (p.pub_dst && blockIdx.x == 0) {
-    if (tid < NSCAL) p.pub_dst[tid] = p.pub_src[tid];
-    __threadfence_system();
-    __syncthreads();
-    if (tid == 0) p.pub_dst[NSCAL] = p.pub_stamp;
-  }
+  if (p.pub_dst && blockIdx.x == 0) scal_publish(p.pub_src, p.pub_dst, p.pub_stamp);
   const int nAcc = GACC || LEAN ? 0 : p.nC * CAM_ACC;
   for (int t = tid; t < nAcc; t += TILE_OBS) sAcc[t] = 0.0;
   __syncthreads();

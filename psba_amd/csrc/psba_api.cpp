@@ -127,7 +127,7 @@ int psba_create(int device, psba_handle *out) {
     psba_destroy(h);
     return rc;
   }
-  if (h->scal.alloc(h, NSCAL) != PSBA_OK || h->h_scal.alloc(h, NSCAL + 8) != PSBA_OK) {  // (+ the publish stamp)
+  if (h->scal.alloc(h, NSCAL) != PSBA_OK || h->h_scal.alloc(h, NSCAL + 8) != PSBA_OK) {  // (+ the publish stamp and check word)
     int rc = fail(nullptr, PSBA_E_HIP, "psba_create: %s", h->err.c_str());
     psba_destroy(h);
     return rc;
@@ -141,7 +141,9 @@ int psba_create(int device, psba_handle *out) {
   // stamps and the partial sums of a try already running)
   (void)hipMemsetAsync(h->scal, 0, sizeof(double) * NSCAL, h->stream);
   (void)hipStreamSynchronize(h->stream);
-  h->h_scal[NSCAL] = 0.0;  // the publish stamp (psba_backsub_wait)
+  // the publish stamp, the check word and the spare words behind them (psba_backsub_wait): the first stamp waited for
+  // is 1.0, and zeros are not the check of any block that carries it
+  for (int k = NSCAL; k < NSCAL + 8; k++) h->h_scal[k] = 0.0;
   *out = h;
   return PSBA_OK;
 }
@@ -1043,20 +1045,36 @@ int psba_backsub_wait(psba_handle h, psba_try_scalars *out) {
     TRY(publish_scalars(h, h->stream));
     h->publish_deferred = false;
   }
+  // the host's own copy of the block: everything below is formed from it, never from pinned memory in place
+  union {
+    unsigned long long w[PUB_RAW];
+    double d[PUB_RAW];
+  } blk;
   if (h->publish_in_k1) {
-    // workgroup 0 of the linearization queued ahead writes the block and then the stamp: poll the
-    // stamp in pinned memory (a try is ~180 us of GPU work); should it not arrive, the stream's end
-    // tells why
-    volatile double *stamp = h->h_scal + NSCAL;
+    // workgroup 0 of the linearization queued ahead writes the block, the stamp and the check word
+    // (scal_publish.h): poll the stamp in pinned memory (a try is ~180 us of GPU work) and take the block
+    // behind it.  The wanted stamp over a block that fails its check is a torn reading -- the stamp reached
+    // host memory ahead of words written before it: read again.  Should no block be accepted, the
+    // stream's end tells why; every word has arrived by then
+    const volatile unsigned long long *raw = reinterpret_cast<const volatile unsigned long long *>(h->h_scal.get());
+    const unsigned long long want = pub_bits(h->pub_seq);
+    bool ok = false, torn = false, stamped = false;
     long long spin = 0;
-    while (*stamp != h->pub_seq && ++spin < 200000000LL) {
+    for (;;) {
+      if (raw[PUB_STAMP] == want) {
+        if ((ok = pub_take(raw, want, blk.w, &stamped))) break;
+        torn = torn || stamped;
+      }
+      if (++spin >= 200000000LL) break;
       if ((spin & 0xfffff) == 0 && hipStreamQuery(h->stream) != hipErrorNotReady) break;
     }
-    if (*stamp != h->pub_seq) {
+    if (!ok) {
       PSBA_HIP(h, hipStreamSynchronize(h->stream));
-      if (*stamp != h->pub_seq) return fail(h, PSBA_E_HIP, "the try's scalars did not reach the host");
+      ok = pub_take(raw, want, blk.w);
     }
-    __sync_synchronize();
+    if (torn) h->pub_torn++;
+    if (!ok) return fail(h, PSBA_E_HIP, "the try's scalars did not reach the host");
+    h->pub_takes++;
     h->publish_in_k1 = false;
   } else {
     // poll the event for a while before handing the thread to the runtime's wait (0.9 us per LM
@@ -1064,26 +1082,74 @@ int psba_backsub_wait(psba_handle h, psba_try_scalars *out) {
     for (int spin = 0; spin < 20000 && hipEventQuery(h->scal_event) == hipErrorNotReady; spin++) {
     }
     PSBA_HIP(h, hipEventSynchronize(h->scal_event));
+    memcpy(blk.d, h->h_scal.get(), sizeof(double) * NSCAL);
   }
   h->scal_side = false;  // the host has seen the side stream's work complete
   h->backsub_pending = false;
   // the four sums arrive as SC_NPART partial sets: add them up in a fixed order
+  double sum[4];
   for (int q = 0; q < 4; q++) {
     double v = 0.0;
-    for (int s = 0; s < SC_NPART; s++) v += h->h_scal[SC_PART + 4 * s + q];
-    h->h_scal[SC_DP_L2 + q] = v;
+    for (int s = 0; s < SC_NPART; s++) v += blk.d[SC_PART + 4 * s + q];
+    sum[q] = v;
   }
   // K3 publishes the status as flags (summed over ranks): > 0 <=> flagged on some rank
-  const int st0 = h->h_scal[SC_STATUS_V] > 0.0 ? h->try_id : 0;
-  const int st1 = h->h_scal[SC_STATUS_SPD] > 0.0 ? h->try_id : 0;
+  const int st0 = blk.d[SC_STATUS_V] > 0.0 ? h->try_id : 0;
+  const int st1 = blk.d[SC_STATUS_SPD] > 0.0 ? h->try_id : 0;
   h->backsubbed = true;
   if (out) {
     out->status = (st1 == h->try_id ? PSBA_NOT_SPD : 0) | (st0 == h->try_id ? PSBA_SINGULAR_V : 0);
-    out->dp_l2 = h->h_scal[SC_DP_L2];
-    out->gain_den = h->h_scal[SC_GAIN_DEN];
-    out->new_cost = h->h_scal[SC_NEW_COST];
-    out->newp_l2 = h->h_scal[SC_NEWP_L2];
+    out->dp_l2 = sum[0];
+    out->gain_den = sum[1];
+    out->new_cost = sum[2];
+    out->newp_l2 = sum[3];
   }
+  return PSBA_OK;
+}
+
+// ---- the handshake's test hooks (scal_publish.h) ----
+int psba_scal_block_check(const double *block, double stamp, double *check) {
+  if (!block || !check) return PSBA_E_INVALID;
+  unsigned long long w[PUB_WORDS];
+  memcpy(w, block, sizeof w);
+  const unsigned long long c = pub_check(w, pub_bits(stamp));
+  memcpy(check, &c, sizeof c);
+  return PSBA_OK;
+}
+
+int psba_scal_block_take(const double *words, double want_stamp, double *out) {
+  if (!words || !out) return PSBA_E_INVALID;
+  unsigned long long copy[PUB_RAW];
+  const bool ok = pub_take(reinterpret_cast<const volatile unsigned long long *>(words), pub_bits(want_stamp), copy);
+  memcpy(out, copy, sizeof(double) * PUB_WORDS);
+  return ok ? 1 : 0;
+}
+
+int psba_publish_stats(psba_handle h, long long *takes, long long *torn) {
+  CHECK_H_NOJOIN(h);
+  if (takes) *takes = h->pub_takes;
+  if (torn) *torn = h->pub_torn;
+  return PSBA_OK;
+}
+
+int psba_test_publish(psba_handle h, const double *block, int threads, double *raw) {
+  CHECK_H(h);
+  if (!raw || (threads != 64 && threads != 128 && threads != 256))
+    return fail(h, PSBA_E_INVALID, "psba_test_publish: raw[%d] and 64, 128 or 256 threads", PUB_RAW);
+  NEED(h, !h->backsub_pending, "a damping try is in flight (psba_backsub_wait first)");
+  NEED(h, h->h_scal_dev, "no device address of the pinned block");
+  h->backsubbed = false;  // the try's result goes: psba_accept needs a new try
+  // a given block stands in the device scalar block for the launch only: the block also holds the status stamps, the
+  // cost and the largest diagonal entry, which the next verbs read
+  double saved[NSCAL];
+  if (block) {
+    TRY(d2h(h, saved, h->scal, sizeof saved));
+    PSBA_HIP(h, hipMemcpyAsync(h->scal, block, sizeof saved, hipMemcpyHostToDevice, h->stream));
+  }
+  TRY(launch_test_publish(h, threads));
+  if (block) PSBA_HIP(h, hipMemcpyAsync(h->scal, saved, sizeof saved, hipMemcpyHostToDevice, h->stream));
+  PSBA_HIP(h, hipStreamSynchronize(h->stream));
+  memcpy(raw, h->h_scal.get(), sizeof(double) * PUB_RAW);
   return PSBA_OK;
 }
 

@@ -10,6 +10,7 @@
 
 #include "../../include/psba_hip.h"
 #include "dev_buf.h"
+#include "scal_publish.h"
 
 namespace psba {
 
@@ -19,6 +20,7 @@ constexpr int MAX_GROUPS = 128; // row-aligned groups of the LDS-resident S part
 constexpr int CAM_ACC = 27;     // per-camera accumulators: 21 (sym U) + 6 (g_a)
 constexpr int LEAN_REC = 20;    // doubles of an observation's record in the lean form: A (2 x 6) | B (2 x 3) | e (2); 160 bytes
 constexpr int NSCAL = 104;      // device scalar block (doubles)
+static_assert(NSCAL == PUB_WORDS, "scal_publish.h states the block's length");
 constexpr int SC_NPART = 16;    // K3's four sums arrive in 16 partial sets (same-address atomics serialise)
 
 // slots of the device scalar block
@@ -412,7 +414,8 @@ struct ProblemState {
   // the try's scalars travel to the host with the linearization queued ahead (its workgroup 0 copies
   // them and then writes a stamp the host polls) instead of through a kernel of their own between K3
   // and that linearization: publish_deferred = K3 queued, nothing published yet; publish_in_k1 = the
-  // queued K1 carries them, the host waits for pub_seq in h_scal[NSCAL]
+  // queued K1 carries them, the host takes the block once it carries the stamp pub_seq and its own check word
+  // (scal_publish.h)
   bool publish_deferred = false, publish_in_k1 = false;
   int cur = 0;                  // index of the current parameter set in cams[]/pts[]
   double coeff = 1.0, coeff_g = 1.0, mu = 0.0;
@@ -456,8 +459,11 @@ struct psba_ctx : ProblemState {
   // Cholesky kernels (written by the K2 reduce kernel).  Lives in scal[8..9]
   int *status = nullptr;
   int try_id = 0;
-  double pub_seq = 0.0;         // stamp of the last try whose scalars the linearization queued ahead carries (h_scal[NSCAL])
-  psba::PinnedBuf<double> h_scal;  // pinned mirror of scal
+  double pub_seq = 0.0;         // stamp of the last block a kernel published (scal_publish.h): h_scal[PUB_STAMP]
+  psba::PinnedBuf<double> h_scal;  // pinned mirror of scal, then the stamp and the check word (PUB_RAW of NSCAL + 8 words)
+  // psba_publish_stats: blocks psba_backsub_wait accepted from the linearization queued ahead, and tries among them
+  // that met a torn reading (the wanted stamp over a block that fails its check) before
+  long long pub_takes = 0, pub_torn = 0;
   int *h_status = nullptr;      // pinned mirror of status
 
   // kernels whose dynamic LDS exceeds 64 KiB need hipFuncSetAttribute once per device: kept per
@@ -558,6 +564,7 @@ int chol_dist_finish(psba_ctx *h);
 // kernels_backsub.hip
 int launch_backsub(psba_ctx *h, double mu, bool dump);
 int launch_publish_scal(psba_ctx *h, hipStream_t s);
+int launch_test_publish(psba_ctx *h, int threads);
 int launch_struct_only_try(psba_ctx *h, double mu);
 // kernels_cov.hip
 int launch_cov_cameras(psba_ctx *h, double scale, hipEvent_t *ev);
