@@ -191,6 +191,31 @@ int psba_camera_masks(psba_handle h, unsigned char *out10_per_cam /* 10 nCams */
  * may be NULL) and the number of groups (nCams without groups). */
 int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam);
 int psba_intrinsics_groups(psba_handle h, int *rep_of_cam, int *n_groups);
+/* ---- ... under PSBA_SOLVER_SPARSE on blocks of 16 ----
+ * The same model, labels, checks and state rules as psba_set_intrinsics_groups, on a PSBA_SOLVER_SPARSE handle, where
+ * that verb keeps returning PSBA_E_STATE; on any other handle this one returns PSBA_E_STATE with a text that names
+ * psba_set_intrinsics_groups.  Nothing is folded into the stored blocks.  Conjugate gradients need only the product
+ *     A x = P^T (S0 (P x)) + mu D x
+ * (P copies a representative's shared coordinates to its members, S0 is the undamped list, P^T sums over the members
+ * in ascending camera order), so with groups set
+ *   * psba_schur_assemble stores S0, the unfolded blocks WITHOUT damping, and the folded e_a (a representative's shared
+ *     entry is the sum over its members in ascending order, as on the dense route and with its bits; folded-away
+ *     entries are 0);
+ *   * psba_get_sparse_S / psba_set_sparse_S return and take these two objects (entries of ea at folded-away
+ *     coordinates are taken as 0);
+ *   * psba_schur_solve runs the recurrences, the stop rule and the bursts of the ungrouped solve on the embedded
+ *     operator: the search direction is kept expanded, a launch behind the block product folds q and adds mu D p.
+ *     mu and D are those of the last psba_schur_assemble.  The preconditioner is the block Jacobi of A: the diagonal
+ *     block of a representative is the folded one (cross-member blocks included), a folded-away coordinate is
+ *     coeff + mu D on the diagonal and zero elsewhere;
+ *   * psba_sparse_S_times returns A x for the embedded A (entries of x at folded-away coordinates meet their
+ *     placeholder alone: y = (coeff + mu D) x there);
+ *   * psba_sparse_camera_covariance, psba_sparse_point_covariance and psba_sparse_S_times_many return PSBA_E_STATE
+ *     with a text that names this verb: covariance under groups is not supported.
+ * The step is expanded and every reduction counts a shared parameter once, as on the dense route.  NULL or a labelling
+ * in which every camera is alone clears the tables: the handle then launches exactly what one that never called the
+ * verb launches, and gives the same bits.  No floating-point atomics: two runs stay bit-identical. */
+int psba_set_sparse_intrinsics_groups(psba_handle h, const int *group_of_cam);
 
 /* ---- the damping rule of the free-intrinsics models (PSBA_CAMERA_FREE_K / PSBA_CAMERA_FREE_KD) --------
  * A camera block with free intrinsics mixes scales: the diagonal of J^T J runs from about 1 (a focal length in
@@ -878,7 +903,8 @@ int psba_algorithmic_bytes(psba_handle h, int kernel, double *bytes);
  * PSBA_SOLVER_PCG; the intrinsics mask, held poses and points, observation weighting, priors and Marquardt damping
  * compose with it.  psba_set_intrinsics_groups, psba_free_covariance_compute and its getters, psba_get / set_reduce_buffer,
  * psba_SPDinv_matVec, psba_chol_dist_* and psba_get_cholmod_factor return PSBA_E_STATE with a text that names
- * PSBA_SOLVER_SPARSE, before any copy or launch. */
+ * PSBA_SOLVER_SPARSE, before any copy or launch.  Intrinsics shared between cameras have a verb of their own on this
+ * route, psba_set_sparse_intrinsics_groups (blocks of 16): the list stays unfolded and the solve folds. */
 #define PSBA_SOLVER_DENSE 0
 #define PSBA_SOLVER_PCG 1
 #define PSBA_SOLVER_SPARSE 2   /* block-sparse S of cnp x cnp blocks + block-Jacobi PCG, whatever the camera block */
@@ -896,6 +922,11 @@ int psba_set_sparse_S(psba_handle h, const double *val, const double *ea);
  * psba_schur_assemble and psba_schur_solve, PSBA_SOLVER_PCG, no structure-only try; PSBA_E_STATE otherwise);
  * changes neither the blocks nor e_a nor a later solve.  Synchronises. */
 int psba_sparse_S_times(psba_handle h, const double *x, double *y);
+/* test hook: M[cnp cnp nCams], the inverses of the diagonal blocks that the last psba_schur_solve preconditioned with
+ * (PSBA_SOLVER_SPARSE on blocks of 11 / 16; with psba_set_sparse_intrinsics_groups the inverses of the folded blocks).
+ * A device-to-host copy.  PSBA_E_STATE unless that solve still stands: a new assembly, psba_set_sparse_S, a covariance
+ * verb of this route and every setter of the model end it. */
+int psba_get_sparse_precond(psba_handle h, double *M);
 /* ---- covariance of chosen cameras under PSBA_SOLVER_SPARSE on camera blocks of 11 / 16 -------------
  * psba_free_covariance_compute inverts an nA x nA square that this route never allocates, and keeps refusing a sparse
  * handle.  Here the object is the joint covariance of a chosen set of cameras: C = scale (S(mu)^-1)[sel, sel], from

@@ -20,7 +20,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
          "-Wall", "-Wno-unused-result", "-x", "hip"] + (["-DPSBA_BUILD_EXPERIMENTS"] if EXPERIMENTS else [])
 
 # per-file flags: the multi-column kernels may not use scratch, so their build prints registers, LDS and scratch per kernel
-EXTRA = {"kernels_free_pcg_many.hip": ["-Rpass-analysis=kernel-resource-usage"],
+EXTRA = {"kernels_free_pcg.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         "kernels_free_pcg_many.hip": ["-Rpass-analysis=kernel-resource-usage"],
          "kernels_free_pcg_points.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 
 

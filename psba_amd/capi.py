@@ -157,6 +157,7 @@ SIGNATURES = [
     ("psba_get_sparse_S", C.c_int, [_h, _ip, _dp, _dp]),
     ("psba_set_sparse_S", C.c_int, [_h, _dp, _dp]),
     ("psba_sparse_S_times", C.c_int, [_h, _dp, _dp]),
+    ("psba_get_sparse_precond", C.c_int, [_h, _dp]),
     ("psba_sparse_S_times_many", C.c_int, [_h, C.c_int, _dp, _dp]),
     ("psba_sparse_camera_covariance", C.c_int, [_h, C.c_double, C.c_double, C.c_int, C.c_int, _ip, _dp, _dp, _ip, _dp]),
     ("psba_sparse_point_covariance", C.c_int, [_h, C.c_double, C.c_double, C.c_int, C.c_int, _ip, _dp, _dp, _ip, _dp]),
@@ -204,6 +205,7 @@ SIGNATURES = [
     ("psba_camera_masks", C.c_int, [_h, C.POINTER(C.c_ubyte)]),
     ("psba_set_intrinsics_groups", C.c_int, [_h, C.POINTER(C.c_int)]),
     ("psba_intrinsics_groups", C.c_int, [_h, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("psba_set_sparse_intrinsics_groups", C.c_int, [_h, C.POINTER(C.c_int)]),
     ("psba_set_damping", C.c_int, [_h, C.c_int, C.c_double, C.c_double]),
     ("psba_damping", C.c_int, [_h, _ip, _dp, _dp]),
     ("psba_get_damping_diag", C.c_int, [_h, _dp]),
@@ -596,6 +598,16 @@ class Psba:
             raise PsbaError(-1, f"set_intrinsics_groups: {g.size} labels for {self.nC} cameras")
         self._ck(lib.psba_set_intrinsics_groups(self._h, g.ctypes.data_as(C.POINTER(C.c_int))))
 
+    def set_sparse_intrinsics_groups(self, group_of_cam=None):
+        """psba_set_sparse_intrinsics_groups: set_intrinsics_groups for a SOLVER_SPARSE handle on blocks of 16 -- the
+        stored blocks stay unfolded and undamped, the solve folds.  None = no sharing."""
+        if group_of_cam is None:
+            return self._ck(lib.psba_set_sparse_intrinsics_groups(self._h, None))
+        g = np.ascontiguousarray(np.asarray(group_of_cam).reshape(-1), dtype=np.int32)
+        if g.size != self.nC:
+            raise PsbaError(-1, f"set_sparse_intrinsics_groups: {g.size} labels for {self.nC} cameras")
+        self._ck(lib.psba_set_sparse_intrinsics_groups(self._h, g.ctypes.data_as(C.POINTER(C.c_int))))
+
     def set_damping(self, kind=DAMPING_IDENTITY, dmin=0.0, dmax=0.0):
         """psba_set_damping: DAMPING_IDENTITY (N + mu I) or DAMPING_MARQUARDT (N + mu D, D = clamp(diag N, dmin, dmax));
         0 for a clamp = its default (1e-6, 1e32).  Free-intrinsics camera models only."""
@@ -982,6 +994,14 @@ class Psba:
         y = np.empty(n)
         self._ck(lib.psba_sparse_S_times(self._h, _d(x), _d(y)))
         return y
+
+    def get_sparse_precond(self):
+        """psba_get_sparse_precond (test hook): [nC, cnp, cnp], the inverses of the diagonal blocks the last schur_solve
+        under SOLVER_SPARSE on blocks of 11 / 16 preconditioned with."""
+        cnp = self.camera_block()
+        M = np.empty((getattr(self, "nC", 0) or 1, cnp, cnp))  # (before an upload the library refuses, nothing is written)
+        self._ck(lib.psba_get_sparse_precond(self._h, _d(M)))
+        return M
 
     def sparse_S_times_many(self, X):
         """psba_sparse_S_times_many: Y = S X for panels X [n_panels, nA, 16], by the product kernel of

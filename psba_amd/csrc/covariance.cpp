@@ -220,6 +220,9 @@ static int need_free_sparse(psba_ctx *h, const char *verb) {
          "PSBA_SOLVER_SPARSE on free-intrinsics camera blocks only (six-parameter blocks: psba_covariance_compute)");
   NEED_V(h, verb, FREE_SPARSE(h),
          "PSBA_SOLVER_SPARSE only (psba_set_solver before the upload); the dense solver: psba_free_covariance_compute");
+  NEED_V(h, verb, h->kd_rep_h.empty(),
+         "not with shared intrinsics (psba_set_sparse_intrinsics_groups): the stored blocks are unfolded and undamped, and "
+         "covariance under groups is not supported on this route");
   return PSBA_OK;
 }
 
@@ -247,6 +250,7 @@ int psba_sparse_camera_covariance(psba_handle h, double mu, double scale, int re
     if (!(h->linearized && h->coeff == 1.0 && h->coeff_g == 1.0)) TRY(psba_linearize(h, 1.0, 1.0));
     TRY(psba_schur_assemble(h, mu));
   }
+  h->precond_ok = false;  // (the block inverses go into the solve's buffer)
   const int rc = launch_fcovm_compute(h, scale, n_sel, sel, C, cols, iters, relres);
   if (rc == PSBA_NOT_SPD)
     h->err = std::string(__func__) + ": S is not positive definite on a chosen column (a pivot of a diagonal block, p.Sp <= 0, or a residual that is not finite)";
@@ -290,6 +294,7 @@ int psba_sparse_point_covariance(psba_handle h, double mu, double scale, int rea
     if (!(h->linearized && h->coeff == 1.0 && h->coeff_g == 1.0)) TRY(psba_linearize(h, 1.0, 1.0));
     TRY(psba_schur_assemble(h, mu));
   }
+  h->precond_ok = false;  // (the block inverses go into the solve's buffer)
   const int rc = launch_fcovp_compute(h, mu, scale, n_sel, sel_pts, C, cols, iters, relres);
   if (rc == PSBA_NOT_SPD)
     h->err = std::string(__func__) + ": S is not positive definite on a chosen column (a pivot of a diagonal block, p.Sp <= 0, or a residual that is not finite)";

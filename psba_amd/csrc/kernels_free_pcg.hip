@@ -6,7 +6,10 @@
 //     store each block once, k_fbsr_finalize adds U and the damping;
 //   * solve: conjugate gradients on S x = e_a, preconditioned with the inverses of the diagonal blocks, with the
 //     recurrences, the four-slot rotation of the scalars and the stop rule of kernels_pcg.hip (test before an
-//     iteration on the previous r.r, r.z == 0 counts as converged, bursts of 8 per host synchronisation).
+//     iteration on the previous r.r, r.z == 0 counts as converged, bursts of 8 per host synchronisation);
+//   * intrinsics shared between cameras (psba_set_sparse_intrinsics_groups, blocks of 16): the list stays
+//     unfolded and undamped and the solve folds -- p kept expanded, a launch behind the product that sums the members' q,
+//     the block Jacobi of the folded matrix.  Every launch site tests h->kd_rep: without groups nothing changes.
 // RULE OF THE ROUTE (kernels_free.hip): no floating-point atomics.  q = S p is formed by one wave per block row in the
 // order of the row walk; every inner product is written as one partial sum per workgroup of a persistent grid (at most
 // FPCG_CAP of them) and every workgroup of the consuming kernel adds the partials in the same order, so all agree
@@ -78,17 +81,40 @@ __global__ __launch_bounds__(256) void k_fbsr_finalize(double *val, const int *d
 // M = X^T X -- the loops of k_bsr_diag_inverse spread over 16 lanes, the block in LDS (a thread per camera would keep
 // three 16 x 16 arrays in scratch).  Lane r of a camera's 16 owns row r of L, column r of X and row r of M; every sum
 // runs in ascending k.  A coordinate whose row and column are zero off the diagonal (masked, held) keeps exact zeros
-// in its row and column of L, X and M.  A pivot that is not > 0 sets status[1] and the fail slot
-template <class T>
+// in its row and column of L, X and M.  A pivot that is not > 0 sets status[1] and the fail slot.
+// GRP (shared intrinsics; the list holds undamped blocks): the input block of a representative is the folded
+// one k_fgrp_sum built (mu D added there); every other camera's is its own plus mu D, with the rows and columns of the
+// folded-away coordinates of a member replaced by the placeholder coeff + mu D.  The three loops are the same
+struct FgInv {
+  KdGroups G;
+  const double *fblk;  // [nmg][256]
+  const double *D;     // null: I
+  double mu, coeff;
+};
+template <class T, bool GRP>
 __global__ __launch_bounds__(16 * FINV_CAMS) void k_fbsr_diag_inverse(const double *val, const int *diag, double *minv,
-                                                                       int nC, double *pc, int *status, int try_id) {
+                                                                       int nC, double *pc, int *status, int try_id, FgInv fi) {
   constexpr int CNP = T::CNP, C2 = CNP * CNP, LD = 17;
   __shared__ double sA[FINV_CAMS][16 * LD], sX[FINV_CAMS][16 * LD];
   const int g = threadIdx.x >> 4, r = threadIdx.x & 15;
   const int j = blockIdx.x * FINV_CAMS + g;
   const bool valid = j < nC;
   double *A = sA[g], *X = sX[g];
-  if (valid) {
+  if (valid && GRP) {
+    const int grp = fi.G.gidx[j];
+    const bool isrep = grp >= 0 && fi.G.rep[j] == j;
+    const unsigned away = grp >= 0 && !isrep ? kd_free_bits(fi.G.mask, fi.G.cmask, j) & 0x3FFu : 0u;
+    const double *a = isrep ? fi.fblk + (size_t)C2 * grp : val + (size_t)C2 * (diag[j] & ~FBSR_ADDED);
+    for (int e = r; e < C2; e += 16) {
+      const int i = e / CNP, c = e % CNP;
+      double v = a[e];
+      if (!isrep) {
+        if (((away >> i) | (away >> c)) & 1u) v = i == c ? fi.coeff : 0.0;
+        if (i == c) v += fi.D ? fi.mu * fi.D[CNP * (size_t)j + i] : fi.mu;
+      }
+      A[LD * i + c] = v;
+    }
+  } else if (valid) {
     const double *a = val + (size_t)C2 * (diag[j] & ~FBSR_ADDED);
     for (int e = r; e < C2; e += 16) A[LD * (e / CNP) + e % CNP] = a[e];  // (the strict upper triangle is never read back)
   } else {
@@ -215,10 +241,11 @@ __global__ __launch_bounds__(256) void k_fpcg_spmv(const double *val, const int 
 }
 
 // start: x = 0, r = b, z = M^-1 r, p = z, q = 0; the partials of r.z (slot 0) and b.b.  One thread per unknown in grid
-// stride (the grid of k_fpcg_update)
-template <class T>
+// stride (the grid of k_fpcg_update).  GRP (shared intrinsics): p is kept expanded -- the thread of a
+// folded-away entry forms its representative's z itself, from b and the inverses, which this launch does not write
+template <class T, bool GRP>
 __global__ __launch_bounds__(256) void k_fpcg_start(const double *b, const double *minv, double *x, double *r, double *z,
-                                                    double *p, double *q, int n, double *pc) {
+                                                    double *p, double *q, int n, double *pc, KdGroups G) {
   constexpr int CNP = T::CNP;
   __shared__ double sRed[4];
   double rz = 0.0, bb = 0.0;
@@ -230,10 +257,18 @@ __global__ __launch_bounds__(256) void k_fpcg_start(const double *b, const doubl
 #pragma unroll
     for (int c = 0; c < CNP; c++) zz += m[c] * bj[c];
     const double bt = b[t];
+    double pz = zz;
+    if (GRP && kd_folded(G, t)) {
+      const int jr = G.rep[j];
+      const double *mr = minv + (size_t)(CNP * CNP) * jr + CNP * row, *br = b + (size_t)CNP * jr;
+      pz = 0.0;
+#pragma unroll
+      for (int c = 0; c < CNP; c++) pz += mr[c] * br[c];
+    }
     x[t] = 0.0;
     r[t] = bt;
     z[t] = zz;
-    p[t] = zz;
+    p[t] = pz;
     q[t] = 0.0;
     rz += bt * zz;
     bb += bt * bt;
@@ -307,8 +342,12 @@ __global__ __launch_bounds__(256) void k_fpcg_update(double *x, const double *r,
 }
 
 // p = z + beta p with beta = r.z_new / r.z; the totals of this iteration's r.r and of the next r.z (zeros once the
-// solve has converged, so that it stays converged: k_fpcg_update wrote no partials then)
-__global__ __launch_bounds__(256) void k_fpcg_direction(const double *z, double *p, int n, double *pc, int it, double tol2) {
+// solve has converged, so that it stays converged: k_fpcg_update wrote no partials then).  GRP: a folded-away entry t
+// takes z[rep(t)] + beta p[t] -- p[t] has its representative's bits by induction, so the result has them too, and the
+// launch reads nothing that it writes but the entry's own p
+template <bool GRP>
+__global__ __launch_bounds__(256) void k_fpcg_direction(const double *z, double *p, int n, double *pc, int it, double tol2,
+                                                        KdGroups G) {
   __shared__ double sRed[4];
   const double rz = pc[PF_RZ + (it & 3)], bb = pc[PF_BB];
   if (fpcg_converged_before(pc, it, rz, bb, tol2)) {
@@ -325,29 +364,173 @@ __global__ __launch_bounds__(256) void k_fpcg_direction(const double *z, double 
     pc[PF_RZ + ((it + 1) & 3)] = rzn;
   }
   const double beta = rzn / rz;
-  for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) p[t] = z[t] + beta * p[t];
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) {
+    const int s = GRP && kd_folded(G, t) ? KD_CNP * G.rep[t / KD_CNP] + t % KD_CNP : t;
+    p[t] = z[s] + beta * p[t];
+  }
+}
+
+// ---- intrinsics shared between cameras under this solver (psba_set_sparse_intrinsics_groups) ----
+// Blocks of 16 only, and only on a handle with groups.  The list keeps S0, the unfolded blocks without damping; the
+// solve works on A = P^T S0 P + mu D, embedded at nA (a folded-away coordinate: coeff + mu D on the diagonal, zero
+// elsewhere, e_a = 0).  Every sum over the members of a group runs in ascending camera order.
+constexpr int FG_PART = 10 * KD_CNP;  // doubles of a member's partial: the ten intrinsic rows of the folded block
+
+// the placeholder's product, rounded operation by operation (no contraction: tests hold it to the bit)
+__device__ __forceinline__ double fg_placeholder(double coeff, double mu, const double *D, size_t t, double x) {
+#pragma clang fp contract(off)
+  const double d = coeff + (D ? mu * D[t] : mu);
+  return d * x;
+}
+
+// e_a folded, a launch behind k_fbsr_finalize: thread (group, k) sums the members' entries in the order of
+// k_kd_fold_cols on the e_a row (so the bits are those of the dense route) and clears the folded-away ones itself
+__global__ __launch_bounds__(256) void k_fbsr_fold_ea(double *ea, KdGroups G) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= 10 * G.nmg) return;
+  const int g = t / 10, k = t % 10;
+  const int m0 = G.gptr[g], m1 = G.gptr[g + 1];
+  if (!((kd_free_bits(G.mask, G.cmask, G.gmem[m0]) >> k) & 1u)) return;  // (the members carry equal rows)
+  double s = 0.0;
+  for (int q = m0; q < m1; q++) s += ea[KD_CNP * (size_t)G.gmem[q] + k];
+  ea[KD_CNP * (size_t)G.gmem[m0] + k] = s;
+  for (int q = m0 + 1; q < m1; q++) ea[KD_CNP * (size_t)G.gmem[q] + k] = 0.0;
+}
+
+// The folded diagonal block of a representative r, rows k < 10 shared: (k, c) = sum over the members m of
+// S0[(m, k)][(r, c)] for a column c that is not shared, sum over m and m' of S0[(m, k)][(m', c)] for one that is.
+// First step: one wave per member m walks m's block row in the order of bs_rowent and keeps, of every block whose other
+// camera is of m's group, the entries that belong to the sums -- lane (k = lane >> 4 (+ 4, + 8), c = lane & 15), the
+// diagonal block read through its lower triangle -- and writes its 10 x 16 partial.  A missing block is zero
+__global__ __launch_bounds__(256) void k_fgrp_partial(const double *val, const int *rowptr, const int2 *rowent, KdGroups G,
+                                                      int nmem, double *part) {
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= nmem) return;
+  const int lane = threadIdx.x & 63, kr = lane >> 4, c = lane & 15;
+  const int m = G.gmem[q], g = G.gidx[m], r = G.rep[m];
+  const unsigned bits = kd_free_bits(G.mask, G.cmask, m) & 0x3FFu;
+  const bool cshared = (bits >> c) & 1u;
+  double acc[3] = {0.0, 0.0, 0.0};
+  const int e1 = rowptr[m + 1];
+  for (int e = rowptr[m]; e < e1; e++) {
+    const int2 en = rowent[e];
+    const int o = en.y & 0x0fffffff, how = en.y >> 28;
+    if (G.gidx[o] != g) continue;
+    const bool take = cshared || o == r;
+    const double *B = val + (size_t)(KD_CNP * KD_CNP) * en.x;
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+      const int k = kr + 4 * t;  // (k < 12: inside the block)
+      const bool asrow = how == 0 || (how == 2 && k >= c);
+      const double v = B[asrow ? KD_CNP * k + c : KD_CNP * c + k];
+      acc[t] += take && ((bits >> k) & 1u) ? v : 0.0;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 3; t++) {
+    const int k = kr + 4 * t;
+    if (k < 10) part[(size_t)FG_PART * q + KD_CNP * k + c] = acc[t];
+  }
+}
+
+// Second step: thread (group, i, j <= i) adds the partials of the group in ascending member order -- row i of the
+// partials where i is shared, row j, column i where only j is -- or takes the representative's own entry where neither
+// is; mu D on the diagonal; the entry and its mirror
+__global__ __launch_bounds__(256) void k_fgrp_sum(const double *val, const int *diag, const double *part, KdGroups G, double mu,
+                                                  const double *D, double *blk) {
+  const int g = blockIdx.x, i = threadIdx.x >> 4, j = threadIdx.x & 15;
+  if (j > i) return;
+  const int m0 = G.gptr[g], m1 = G.gptr[g + 1], r = G.gmem[m0];
+  const unsigned bits = kd_free_bits(G.mask, G.cmask, r) & 0x3FFu;
+  const bool is = (bits >> i) & 1u, js = (bits >> j) & 1u;
+  double v;
+  if (!is && !js) {
+    v = val[(size_t)(KD_CNP * KD_CNP) * (diag[r] & ~FBSR_ADDED) + KD_CNP * i + j];
+  } else {
+    const int at = is ? KD_CNP * i + j : KD_CNP * j + i;
+    v = 0.0;
+    for (int q = m0; q < m1; q++) v += part[(size_t)FG_PART * q + at];
+  }
+  if (i == j) v += D ? mu * D[KD_CNP * (size_t)r + i] : mu;
+  double *b = blk + (size_t)(KD_CNP * KD_CNP) * g;
+  b[KD_CNP * i + j] = v;
+  b[KD_CNP * j + i] = v;
+}
+
+// q <- P^T q + mu D p behind k_fpcg_spmv, and the partials of p.q over the kept coordinates into the slot k_fpcg_update
+// reads (the grid of k_fpcg_update: its workgroups' count replaces the product kernel's).  The thread of a
+// representative's shared entry sums the members' q and clears the folded-away ones itself: no other thread touches
+// them.  xdiag (psba_sparse_S_times): a folded-away entry gets its placeholder times xdiag in the place of 0
+__global__ __launch_bounds__(256) void k_fpcg_fold(double *q, const double *p, KdGroups G, double coeff, double mu,
+                                                   const double *D, const double *xdiag, int n, double *pqpart) {
+  __shared__ double sRed[4];
+  double pq = 0.0;
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) {
+    const int j = t / KD_CNP, k = t % KD_CNP;
+    const bool sh = k < 10 && ((kd_free_bits(G.mask, G.cmask, j) >> k) & 1u);
+    const int g = sh ? G.gidx[j] : -1;
+    if (g >= 0 && G.rep[j] != j) continue;
+    double s = q[t];
+    if (g >= 0) {
+      const int m0 = G.gptr[g], m1 = G.gptr[g + 1];
+      s = 0.0;
+      for (int u = m0; u < m1; u++) s += q[KD_CNP * (size_t)G.gmem[u] + k];
+      for (int u = m0 + 1; u < m1; u++) {
+        const size_t tm = KD_CNP * (size_t)G.gmem[u] + k;
+        q[tm] = xdiag ? fg_placeholder(coeff, mu, D, tm, xdiag[tm]) : 0.0;
+      }
+    }
+    const double y = s + (D ? mu * D[t] : mu) * p[t];
+    q[t] = y;
+    pq += p[t] * y;
+  }
+  const double tot = fpcg_block_sum(pq, sRed);
+  if (threadIdx.x == 0) pqpart[blockIdx.x] = tot;
+}
+
+// psba_sparse_S_times under groups: p = P x (a folded-away entry takes its representative's x)
+__global__ __launch_bounds__(256) void k_fpcg_expand(const double *x, double *p, KdGroups G, int n) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t < n) p[t] = x[kd_folded(G, t) ? KD_CNP * G.rep[t / KD_CNP] + t % KD_CNP : t];
 }
 
 template <class T>
 static int fbsr_finalize(psba_ctx *h, double mu, const double *D) {
   const int nC = h->d.nC;
   const size_t n = (size_t)(T::CNP * T::CNP + T::CNP) * nC;
+  const bool grp = T::CNP == KD_CNP && h->kd_rep;  // shared intrinsics: S0 without damping, then e_a folded
+  h->bs_mu = mu;
+  h->bs_D = D;
   ProfScope ps(h, PSBA_K_SCHUR);
   hipLaunchKernelGGL(k_fbsr_finalize<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->bs_val, h->bs_diag,
-                     h->bs_ea, h->U, h->ga, h->free_eapart, h->free_cuptr, mu, D, nC, h->scal, h->status, h->try_id);
+                     h->bs_ea, h->U, h->ga, h->free_eapart, h->free_cuptr, grp ? 0.0 : mu, grp ? nullptr : D, nC, h->scal,
+                     h->status, h->try_id);
+  if (grp)
+    hipLaunchKernelGGL(k_fbsr_fold_ea, dim3((unsigned)((10 * h->kd_nmg + 255) / 256)), dim3(256), 0, h->stream, h->bs_ea,
+                       kd_groups(h));
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }
 
+// q = A p behind the block product under groups: the fold's launch (grid and partials of k_fpcg_update)
+static void fpcg_fold(psba_ctx *h, double *q, const double *p, const double *xdiag, int n, double *pqpart) {
+  hipLaunchKernelGGL(k_fpcg_fold, dim3(fpcg_vec_grid(n)), dim3(256), 0, h->stream, q, p, kd_groups(h), h->coeff, h->bs_mu,
+                     h->bs_D, xdiag, n, pqpart);
+}
+
 // y = S x with the solve's own product kernel (psba_sparse_S_times): x goes into the solve's p, the product into its q
-// (both free between solves), the partials of x.Sx into slot 0 -- launch_fpcg_solve clears the scalar block
+// (both free between solves), the partials of x.Sx into slot 0 -- launch_fpcg_solve clears the scalar block.  Under
+// groups y = A x with the solve's three steps: x into r's second buffer, p = P x, the block product, the fold
 template <class T>
 static int fbsr_times(psba_ctx *h, const double *x_host, double *y_host) {
   const int n = h->d.nA, nC = h->d.nC;
-  double *p = h->pcg_vec + 2 * (size_t)n, *q = p + n;
-  PSBA_HIP(h, hipMemcpyAsync(p, x_host, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+  double *p = h->pcg_vec + 2 * (size_t)n, *q = p + n, *x = q + n;
+  const bool grp = T::CNP == KD_CNP && h->kd_rep;
+  PSBA_HIP(h, hipMemcpyAsync(grp ? x : p, x_host, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+  if (grp) hipLaunchKernelGGL(k_fpcg_expand, dim3((n + 255) / 256), dim3(256), 0, h->stream, x, p, kd_groups(h), n);
   hipLaunchKernelGGL(k_fpcg_spmv<T>, dim3(fpcg_row_grid(nC)), dim3(256), 0, h->stream, h->bs_val, h->bs_rowptr, h->bs_rowent,
                      nC, p, q, h->pcg_scal + PF_PQP);
+  if (grp) fpcg_fold(h, q, p, x, n, h->pcg_scal + PF_PQP);
   PSBA_HIP(h, hipGetLastError());
   PSBA_HIP(h, hipMemcpyAsync(y_host, q, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
   PSBA_HIP(h, hipStreamSynchronize(h->stream));
@@ -355,17 +538,26 @@ static int fbsr_times(psba_ctx *h, const double *x_host, double *y_host) {
 }
 
 // S x = e_a by preconditioned conjugate gradients; dpa into dp[0 .. nA).  The host side of launch_pcg_solve; the
-// scalars of a burst are copied behind its last k_fpcg_direction, which is where this route's totals are written
-template <class T>
+// scalars of a burst are copied behind its last k_fpcg_direction, which is where this route's totals are written.
+// GRP (shared intrinsics): the folded diagonal blocks first, the fold behind every block product
+template <class T, bool GRP>
 static int fpcg_solve(psba_ctx *h) {
   const int n = h->d.nA, nC = h->d.nC, g = fpcg_vec_grid(n), gs = fpcg_row_grid(nC);
   hipStream_t s = h->stream;
   double *x = h->dp, *r0 = h->pcg_vec, *z = r0 + n, *p = z + n, *q = p + n, *r1 = q + n, *pc = h->pcg_scal;
+  FgInv fi = {};
+  if (GRP) fi = FgInv{kd_groups(h), h->fg_blk, h->bs_D, h->bs_mu, h->coeff};
   ProfScope ps(h, PSBA_K_CHOLESKY);
   PSBA_HIP(h, hipMemsetAsync(pc, 0, sizeof(double) * PF_ALL, s));
-  hipLaunchKernelGGL(k_fbsr_diag_inverse<T>, dim3((nC + FINV_CAMS - 1) / FINV_CAMS), dim3(16 * FINV_CAMS), 0, s, h->bs_val,
-                     h->bs_diag, h->pcg_minv, nC, pc, h->status, h->try_id);
-  hipLaunchKernelGGL(k_fpcg_start<T>, dim3(g), dim3(256), 0, s, h->bs_ea, h->pcg_minv, x, r0, z, p, q, n, pc);
+  if (GRP) {
+    hipLaunchKernelGGL(k_fgrp_partial, dim3((h->kd_nmem + 3) / 4), dim3(256), 0, s, h->bs_val, h->bs_rowptr, h->bs_rowent, fi.G,
+                       h->kd_nmem, h->fg_part);
+    hipLaunchKernelGGL(k_fgrp_sum, dim3(h->kd_nmg), dim3(256), 0, s, h->bs_val, h->bs_diag, h->fg_part, fi.G, fi.mu, fi.D,
+                       h->fg_blk);
+  }
+  hipLaunchKernelGGL((k_fbsr_diag_inverse<T, GRP>), dim3((nC + FINV_CAMS - 1) / FINV_CAMS), dim3(16 * FINV_CAMS), 0, s,
+                     h->bs_val, h->bs_diag, h->pcg_minv, nC, pc, h->status, h->try_id, fi);
+  hipLaunchKernelGGL((k_fpcg_start<T, GRP>), dim3(g), dim3(256), 0, s, h->bs_ea, h->pcg_minv, x, r0, z, p, q, n, pc, fi.G);
   double hs[PF_N];
   h->pcg_iters = 0;
   h->pcg_relres = 1.0;
@@ -378,9 +570,10 @@ static int fpcg_solve(psba_ctx *h) {
       double *rc = (it & 1) ? r1 : r0, *rn = (it & 1) ? r0 : r1;
       hipLaunchKernelGGL(k_fpcg_spmv<T>, dim3(gs), dim3(256), 0, s, h->bs_val, h->bs_rowptr, h->bs_rowent, nC, p, q,
                          pc + PF_PQP + FPCG_CAP * (it & 3));
-      hipLaunchKernelGGL(k_fpcg_update<T>, dim3(g), dim3(256), 0, s, x, rc, rn, p, q, h->pcg_minv, z, n, pc, it, gs, h->status,
-                         h->try_id, tol2);
-      hipLaunchKernelGGL(k_fpcg_direction, dim3(g), dim3(256), 0, s, z, p, n, pc, it, tol2);
+      if (GRP) fpcg_fold(h, q, p, nullptr, n, pc + PF_PQP + FPCG_CAP * (it & 3));
+      hipLaunchKernelGGL(k_fpcg_update<T>, dim3(g), dim3(256), 0, s, x, rc, rn, p, q, h->pcg_minv, z, n, pc, it, GRP ? g : gs,
+                         h->status, h->try_id, tol2);
+      hipLaunchKernelGGL(k_fpcg_direction<GRP>, dim3(g), dim3(256), 0, s, z, p, n, pc, it, tol2, fi.G);
       last = it;
     }
     PSBA_HIP(h, hipMemcpyAsync(h->pcg_host, pc, sizeof(double) * PF_N, hipMemcpyDeviceToHost, s));
@@ -420,8 +613,8 @@ static int fpcg_solve(psba_ctx *h) {
 template <class T>
 static int fbsr_diag_inverse(psba_ctx *h, double *minv, double *pc, int *status, int stamp) {
   const int nC = h->d.nC;
-  hipLaunchKernelGGL(k_fbsr_diag_inverse<T>, dim3((nC + FINV_CAMS - 1) / FINV_CAMS), dim3(16 * FINV_CAMS), 0, h->stream,
-                     h->bs_val, h->bs_diag, minv, nC, pc, status, stamp);
+  hipLaunchKernelGGL((k_fbsr_diag_inverse<T, false>), dim3((nC + FINV_CAMS - 1) / FINV_CAMS), dim3(16 * FINV_CAMS), 0,
+                     h->stream, h->bs_val, h->bs_diag, minv, nC, pc, status, stamp, FgInv{});
   PSBA_HIP(h, hipGetLastError());
   return PSBA_OK;
 }
@@ -429,7 +622,10 @@ static int fbsr_diag_inverse(psba_ctx *h, double *minv, double *pc, int *status,
 #define FPCG_DISPATCH(fn, ...) (h->cnp == KD_CNP ? fn<FreeKD>(__VA_ARGS__) : fn<FreeK>(__VA_ARGS__))
 int launch_fbsr_finalize(psba_ctx *h, double mu, const double *D) { return FPCG_DISPATCH(fbsr_finalize, h, mu, D); }
 int launch_fbsr_times(psba_ctx *h, const double *x_host, double *y_host) { return FPCG_DISPATCH(fbsr_times, h, x_host, y_host); }
-int launch_fpcg_solve(psba_ctx *h) { return FPCG_DISPATCH(fpcg_solve, h); }
+int launch_fpcg_solve(psba_ctx *h) {
+  if (h->cnp != KD_CNP) return fpcg_solve<FreeK, false>(h);
+  return h->kd_rep ? fpcg_solve<FreeKD, true>(h) : fpcg_solve<FreeKD, false>(h);
+}
 int launch_fbsr_diag_inverse(psba_ctx *h, double *minv, double *pc, int *status, int stamp) {
   return FPCG_DISPATCH(fbsr_diag_inverse, h, minv, pc, status, stamp);
 }

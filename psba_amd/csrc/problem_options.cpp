@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -23,6 +24,7 @@ void model_changed(psba_ctx *h) {
   h->free_obs = false;
   h->damp_ok = false;
   h->cov_ok = h->cov_pts_ok = false;
+  h->precond_ok = false;
   h->lean_cur = h->lean_alt = false;  // (the linearizations they describe are gone)
 }
 
@@ -323,11 +325,10 @@ int psba_camera_masks(psba_handle h, unsigned char *out10_per_cam) {
   return PSBA_OK;
 }
 
-// ---- intrinsics shared between cameras (PSBA_CAMERA_FREE_KD; DESIGN 7e) ----
-int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam) {
-  CHECK_H(h);
-  TRY(settable(h, __func__, FREE_KD));
-  NEED(h, !FREE_SPARSE(h), "not under PSBA_SOLVER_SPARSE: the fold sums rows and columns of a dense S");
+// ---- intrinsics shared between cameras (PSBA_CAMERA_FREE_KD; DESIGN 7e, 7q) ----
+// the body of both setters: labels -> rep / gidx / gptr / gmem, the checks of the masks and of the members' intrinsics,
+// the tables staged all or nothing.  sparse: also the buffers of the folded diagonal blocks (kernels_free_pcg.hip)
+static int set_groups(psba_ctx *h, const char *fn, const int *group_of_cam, bool sparse) {
   const int nC = h->d.nC;
   // the representative of a label is the first camera that carries it
   std::vector<int> rep((size_t)nC), order((size_t)nC);
@@ -342,13 +343,13 @@ int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam) {
   }
   std::vector<int> gidx, gptr, gmem;
   if (ngroups < nC) {
-    TRY(masks_split(h, __func__, rep, h->kd_cmask_h));  // (host tables: before anything is read from the device)
+    TRY(masks_split(h, fn, rep, h->kd_cmask_h));  // (host tables: before anything is read from the device)
     std::vector<double> c((size_t)h->d.nA);
     const double *src[2] = {h->cams[h->cur], h->params0};
-    const char *who[2] = {"psba_set_intrinsics_groups (current parameters)", "psba_set_intrinsics_groups (the psba_reset_params copy)"};
+    const std::string who[2] = {std::string(fn) + " (current parameters)", std::string(fn) + " (the psba_reset_params copy)"};
     for (int k = 0; k < 2; k++) {
       TRY(d2h(h, c.data(), src[k], sizeof(double) * c.size()));
-      TRY(groups_split(h, who[k], rep, c.data(), KD_CNP, 10, 0));
+      TRY(groups_split(h, who[k].c_str(), rep, c.data(), KD_CNP, 10, 0));
     }
     std::vector<int> count((size_t)nC, 0);
     for (int j = 0; j < nC; j++) count[rep[j]]++;
@@ -366,12 +367,37 @@ int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam) {
   } else {
     rep.clear();  // (every camera alone is no grouping: no tables, the ungrouped launches)
   }
+  const int nmg = rep.empty() ? 0 : (int)gptr.size() - 1;
+  DevBuf<double> part, blk;
+  if (sparse && nmg) {
+    TRY(part.alloc(h, (size_t)10 * KD_CNP * gmem.size()));
+    TRY(blk.alloc(h, (size_t)KD_CNP * KD_CNP * nmg));
+  }
   TRY(stage(h, Staged(h->kd_rep, rep), Staged(h->kd_gidx, gidx), Staged(h->kd_gptr, gptr), Staged(h->kd_gmem, gmem)));
+  h->fg_part = std::move(part);
+  h->fg_blk = std::move(blk);
   h->kd_ngroups = rep.empty() ? 0 : ngroups;
-  h->kd_nmg = rep.empty() ? 0 : (int)gptr.size() - 1;
+  h->kd_nmg = nmg;
+  h->kd_nmem = (int)gmem.size();
   h->kd_rep_h = std::move(rep);
   model_changed(h);
   return PSBA_OK;
+}
+
+int psba_set_intrinsics_groups(psba_handle h, const int *group_of_cam) {
+  CHECK_H(h);
+  TRY(settable(h, __func__, FREE_KD));
+  NEED(h, !FREE_SPARSE(h), "not under PSBA_SOLVER_SPARSE: the fold sums rows and columns of a dense S "
+                           "(psba_set_sparse_intrinsics_groups folds inside the solve)");
+  return set_groups(h, __func__, group_of_cam, false);
+}
+
+// ... on a PSBA_SOLVER_SPARSE handle: the same tables; the list stays unfolded and the solve folds
+int psba_set_sparse_intrinsics_groups(psba_handle h, const int *group_of_cam) {
+  CHECK_H(h);
+  TRY(settable(h, __func__, FREE_KD, "; the other camera blocks have no groups (as under psba_set_intrinsics_groups)"));
+  NEED(h, FREE_SPARSE(h), "PSBA_SOLVER_SPARSE only (psba_set_solver before the upload); the dense solver: psba_set_intrinsics_groups");
+  return set_groups(h, __func__, group_of_cam, true);
 }
 
 int psba_intrinsics_groups(psba_handle h, int *rep_of_cam, int *n_groups) {

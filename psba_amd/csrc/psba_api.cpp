@@ -846,6 +846,7 @@ int psba_schur_assemble(psba_handle h, double mu) {
     TRY(launch_schur(h, mu, false));
   h->assembled = true;
   h->solved = h->backsubbed = false;
+  h->precond_ok = false;
   return PSBA_OK;
 }
 
@@ -893,6 +894,7 @@ int psba_schur_solve(psba_handle h) {
     TRY(h->cnp != 6 ? launch_fpcg_solve(h) : launch_pcg_solve(h));
     h->assembled = false;
     h->solved = true;
+    h->precond_ok = h->cnp != 6;
     return h->pcg_exhausted ? PSBA_PCG_MAXIT : PSBA_OK;
   }
   TRY(launch_chol_solve(h));
@@ -1323,10 +1325,30 @@ int psba_set_sparse_S(psba_handle h, const double *val, const double *ea) {
   NEED(h, h->assembled && h->solver == PSBA_SOLVER_PCG, "psba_schur_assemble with PSBA_SOLVER_PCG first");
   NEED(h, !h->try_shortcut, "every camera is fixed: this try assembled no S (PSBA_FIXED_NO_SHORTCUT=1 keeps the general route)");
   if (val) PSBA_HIP(h, hipMemcpyAsync(h->bs_val, val, sizeof(double) * (size_t)(h->cnp * h->cnp) * (size_t)h->bs_nblk, hipMemcpyHostToDevice, h->stream));
+  std::vector<double> kept;
+  if (ea && h->cnp == KD_CNP && !h->kd_rep_h.empty()) {  // shared intrinsics: e_a is 0 at a folded-away coordinate
+    kept.assign(ea, ea + h->d.nA);
+    for (int j = 0; j < h->d.nC; j++)
+      for (int k = 0; k < 10 && h->kd_rep_h[j] != j; k++) {
+        const unsigned bits = h->kd_cmask_h.empty() ? h->kd_mask : h->kd_mask & h->kd_cmask_h[j];
+        if ((bits >> k) & 1u) kept[(size_t)KD_CNP * j + k] = 0.0;
+      }
+    ea = kept.data();
+  }
   if (ea) PSBA_HIP(h, hipMemcpyAsync(h->bs_ea, ea, sizeof(double) * (size_t)h->d.nA, hipMemcpyHostToDevice, h->stream));
   PSBA_HIP(h, hipStreamSynchronize(h->stream));
   h->solved = h->backsubbed = false;
+  h->precond_ok = false;
   return PSBA_OK;
+}
+
+// test hook (psba_hip.h): the inverses of the diagonal blocks the last solve of this route preconditioned with
+int psba_get_sparse_precond(psba_handle h, double *M) {
+  CHECK_H(h);
+  NEED(h, h->uploaded && FREE_SPARSE(h), "PSBA_SOLVER_SPARSE on camera blocks of 11 / 16 and an uploaded problem");
+  NEED(h, h->precond_ok, "psba_schur_solve first (a new assembly, psba_set_sparse_S, a covariance verb and every setter of the model end it)");
+  if (!M) return fail(h, PSBA_E_INVALID, "%s: null pointer", __func__);
+  return d2h(h, M, h->pcg_minv, sizeof(double) * (size_t)(h->cnp * h->cnp) * (size_t)h->d.nC);
 }
 
 // y = S x on the stored blocks, with the kernel the solve uses for its products (a mirror verb: how that kernel is judged

@@ -349,6 +349,15 @@ struct ProblemState {
   psba::DevBuf<int> kd_gptr;       // [kd_nmg + 1] CSR over kd_gmem of the groups with several members
   psba::DevBuf<int> kd_gmem;       // their members in ascending camera order (the first is the representative)
   int kd_nmg = 0;
+  // ... under PSBA_SOLVER_SPARSE (psba_set_sparse_intrinsics_groups; kernels_free_pcg.hip): the list keeps the
+  // unfolded, undamped blocks and the solve folds -- the folded diagonal blocks of the preconditioner are built into
+  // buffers of their own, allocated with the tables
+  int kd_nmem = 0;                 // entries of kd_gmem
+  psba::DevBuf<double> fg_part;    // [kd_nmem][10][16] each member's share of the intrinsic rows of its group's folded block
+  psba::DevBuf<double> fg_blk;     // [kd_nmg][256] the folded diagonal block of each representative, mu D added
+  double bs_mu = 0.0;              // mu and D (null: I) of the last k_fbsr_finalize: what the grouped solve adds after the fold
+  const double *bs_D = nullptr;    // (not owned)
+  bool precond_ok = false;         // pcg_minv holds the block inverses of the last psba_schur_solve (psba_get_sparse_precond)
   // held poses and points of this route (psba_set_held): byte masks on the device, both allocated while
   // either has a non-zero entry (has_held: the HELD kernel instantiations), none otherwise; an upload resets to none
   psba::DevBuf<unsigned char> held_poses, held_pts;  // [nC], [nP]
